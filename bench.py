@@ -2,7 +2,7 @@
 # -*- coding: utf-8 -*-
 """Benchmark of the WaveNet-vocoder TRAINING STEP on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,10 +14,18 @@ BASELINE.json configs[1]: 30-layer WaveNet, 64 residual / 256 skip channels, 80-
 mu-law softmax, batch 8 x batch_len 20000 per GPU (-> T = 23040 model inputs, 19970 loss
 positions per sequence).  Weak scaling: the per-GPU batch is fixed.
 
-The K timed steps are measured `--repeats` times (default 5; each region bracketed by barrier + synchronize, MAX over
-ranks); `ms_per_step` / `value` are the MEDIAN region, min / max are reported beside it.
+A plain run sets up, runs W warm-up steps, times exactly K steps as one region (bracketed by barrier + synchronize, MAX over
+ranks), writes the outputs of the last timed step if `--dump-outputs DIR` is given, and prints the result line: `ms_per_step`
+= region / K, `value` = audio samples per second of that region.  `--dump-outputs DIR` writes what the timed step hands its
+caller, from the last timed step (rank 0): DIR/loss.npy (float64, 1 value), DIR/grads.npy and DIR/weights.npy (float32, every
+parameter's gradient -- zeros for the dead last res_1x1 -- and every parameter after the Adam update, flattened and
+concatenated in named_parameters() order).  Inputs and initial weights are seeded, so equal arguments give equal inputs.
 
-Prints ONE JSON line (rank 0).  Extra blocks:
+`--full` adds everything that is not the headline figure: the K timed steps are measured `--repeats` times (default 5 there;
+`ms_per_step` / `value` are then the MEDIAN region, min / max beside it), per-launch HIP-event tables (`--profile-steps`), the
+exposed exchange of N > 1 (`comm`), and the blocks below.
+
+Prints ONE JSON line (rank 0).  Extra blocks (`--full`; `roofline` without `dominant_kernel` in a plain run too):
   roofline      bound = hbm (north_star's denominator).  `achieved` / `frac` are the WHOLE STEP against SURVEY.md 8(d):
                 timesteps/s x 78 356 algorithmic bytes per timestep vs 8 TB/s.  `traffic` = HBM bytes the step really
                 moved (rocprofv3 PMC passes of this launch mode, profiles/), `traffic_ratio` = traffic / algorithmic.
@@ -440,12 +448,33 @@ def load_pmc_traffic(flags):
     return None
 
 
+def dump_outputs(model, loss, out_dir):
+    """What the timed step hands its caller, after it ran: the mean loss, every parameter's gradient (p.grad, a view of the
+    flat gradient buffer; None -> zeros for the dead last res_1x1) and every parameter after the Adam update, flattened and
+    concatenated in named_parameters() order (6.4 MB each for the benchmark's model)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    with torch.no_grad():
+        named = list(model.named_parameters())
+        grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for _, p in named])
+        weights = torch.cat([p.detach().reshape(-1) for _, p in named])
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss.item())], dtype=np.float64))
+    np.save(os.path.join(out_dir, "grads.npy"), grads.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "weights.npy"), weights.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the K timed steps are measured (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated timing regions, per-launch tables, the exposed exchange (N > 1), CPU "
+                         "baseline + same-run parity, decode, other arithmetic modes and workloads (each --no-* flag still applies)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, gradients and updated weights of the last timed step to DIR/*.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times the K timed steps are measured (median reported; default 1, 5 with --full)")
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="sequences per GPU")
     ap.add_argument("--layers-per-bucket", type=int, default=LAYERS_PER_BUCKET,
                     help="gradient buckets = weight-gradient launch groups of this many layers (same for N = 1 and N > 1)")
@@ -459,10 +488,15 @@ def main():
                     help="aux-path gradients by the separate wn_aux_bwd launch instead of the partial sums inside the gate "
                          "kernel (WN_FLAG_AUX_FUSED, the engine's default)")
     ap.add_argument("--aux-fused", action="store_true", help=argparse.SUPPRESS)   # round-1 spelling: now the default
-    ap.add_argument("--profile-steps", type=int, default=2, help="extra untimed steps with per-launch HIP events")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="extra untimed steps with per-launch HIP events (default 0, 2 with --full)")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the two extra (non-headline) workloads: BASELINE configs[3] geometry and the recipe-size model")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.profile_steps is None:
+        args.profile_steps = 2 if args.full else 0
 
     import torch.distributed as dist
     from pytorchwavenetvocoder_amd import _lib
@@ -497,7 +531,7 @@ def main():
     model.apply(initialize)
     model.to(device)
     # the weights the timed steps start from: the same-run parity gate hands exactly these to the reference's module
-    want_parity = (world == 1 and not args.no_cpu_baseline and not args.no_parity)
+    want_parity = (world == 1 and args.full and not args.no_cpu_baseline and not args.no_parity)
     init_state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if want_parity else None
     if args.no_fused:
         model.engine.flags |= _lib.FLAG_NO_FUSED
@@ -544,6 +578,8 @@ def main():
         regions.append(elapsed)
     final_loss = float(loss.item())
     elapsed = sorted(regions)[len(regions) // 2]      # median region of K steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, loss, args.dump_outputs)
 
     ms_per_step = elapsed / args.steps * 1e3
     samples_per_s = world * B * (T - rf) * args.steps / elapsed
@@ -652,13 +688,13 @@ def main():
 
     # ---- the exchange, as the ranks saw it (N > 1: a few extra untimed steps with the exposed part measured) ----
     comm = None
-    if world > 1 and device.type == "cuda":
+    if args.full and world > 1 and device.type == "cuda":
         red.measure_exposed = True
         for _ in range(5):
             step()
         barrier()
         red.measure_exposed = False
-    if rank == 0:
+    if rank == 0 and args.full:
         comm = red.comm_report()
         comm["ranks_reported_by_backend"] = dist.get_world_size() if world > 1 else 1
         comm["note"] = ("exposed_ms_per_step = event behind the last backward launch -> event after the caller's stream joined the "
@@ -708,7 +744,7 @@ def main():
             "timesteps_per_sec": world * timesteps_per_s_gpu, "final_loss": final_loss,
             "roofline": roofline, "comm": comm, "kernels": kernels,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             inst = (init_state, x.cpu(), h.cpu(), t.cpu()) if want_parity else None
             out["cpu_baseline"], ref = cpu_baseline(bench_instance=inst)
             if ref is not None:
@@ -716,9 +752,9 @@ def main():
                 del ref
         else:
             out["cpu_baseline"] = None
-        if not args.no_decode and world == 1:
+        if args.full and not args.no_decode and world == 1:
             out["decode"] = decode_report(model, device, not args.no_cpu_baseline)
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             # the other arithmetic modes on the SAME step, beside the metric (every narrowed strand keeps its six-product
             # figure on the line): six bf16 products EVERYWHERE (fp32-equivalent to round-off: what every fp16 launch falls back to when
             # an operand leaves fp16's range), six products for the k_gemm6 contractions only (weight gradients stay fp16 pairs: round

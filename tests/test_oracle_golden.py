@@ -95,19 +95,38 @@ def test_oracle_generation_vs_reference(name):
 
 def test_restatement_equals_the_reference_module_copy():
     """oracle/_ref/wavenet.py (the reference's own model file, copied at build time by oracle/build_ref.py; absent from the
-    repository's history) under the reference's training loop == the restatement, bit for bit, incl. the Adam step."""
-    import pytest
+    repository's history) under the reference's training loop == the restatement, bit for bit, incl. the Adam step.  Always
+    against that module's recorded two steps (tests/golden/reference_module_steps.npz, make_reference_module_golden.py); live
+    as well where the build made the copy."""
     from oracle import ref_step as RS
-    if not RS.available():
-        pytest.skip("oracle/_ref/wavenet.py not built (needs /root/reference at build time)")
-    import torch
-    from oracle import wavenet_oracle as O
     old_threads = torch.get_num_threads()
     torch.set_num_threads(1)   # oneDNN's thread partition changes the summation order: one thread makes both runs the same program
     try:
-        _check_restatement_vs_reference(RS, O, torch)
+        _check_restatement_vs_recorded_reference(O, torch)
+        if RS.available():
+            _check_restatement_vs_reference(RS, O, torch)
     finally:
         torch.set_num_threads(old_threads)
+
+
+def _check_restatement_vs_recorded_reference(O, torch):
+    # recorded on another host: oneDNN may pick other kernels there, so logits / loss take the gates of SURVEY 8d (as the
+    # golden cases above); the weights after two Adam steps the same 1e-2 lr as the live comparison
+    z = np.load(os.path.join(GOLDEN_DIR, "reference_module_steps.npz"), allow_pickle=False)
+    lr, wd = float(z["lr"]), float(z["wd"])
+    assert int(z["n_cases"]) == 3
+    for i in range(int(z["n_cases"])):
+        cfg_t = tuple(int(v) for v in z["c%d/cfg" % i])
+        cfg = O.OracleConfig(*cfg_t)
+        pp = O.random_params(cfg, int(z["param_seed"]))
+        x, h, t = O.synthetic_batch(cfg, int(z["c%d/B" % i]), int(z["c%d/T" % i]), int(z["batch_seed"]))
+        opt = O.OracleAdam(lr=lr, weight_decay=wd)
+        for s in range(int(z["steps"])):
+            l, lg, _g = O.train_step(cfg, pp, opt, x, h, t)
+            assert abs(float(z["c%d/loss%d" % (i, s)]) - float(l)) <= 1e-5, (cfg_t, s)
+            assert float((torch.from_numpy(z["c%d/logits%d" % (i, s)]) - lg).abs().max()) <= 1e-4, (cfg_t, s)
+        for k, v in pp.items():
+            assert float((torch.from_numpy(z["c%d/after/%s" % (i, k)]) - v).abs().max()) <= 1e-2 * lr, (cfg_t, k)
 
 
 def _check_restatement_vs_reference(RS, O, torch):

@@ -30,7 +30,7 @@ if has pmc; then
   [ -n "$NEWEST" ] && [ -f $OUT/pmc_traffic.json ] && cp $OUT/pmc_traffic.json $NEWEST/pmc_traffic.json
 fi
 if has bench; then
-  timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-400 $OUT/bench.json
+  timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-400 $OUT/bench.json
 fi
 if has lpb; then
   # same-box A/B, interleaved, two rounds.  A variant is a comma-separated list of environment settings, e.g.
@@ -50,7 +50,7 @@ if has abk; then
   # like lpb, with the per-kernel HIP-event table of each variant (WN_AB_VARIANTS; WN_ABK_KERNELS = tags to print)
   for rep in 1 2; do
     for cfg in ${WN_AB_VARIANTS:-WN_X=1}; do
-      env $(echo $cfg | tr ',' ' ') timeout 200 python bench.py --repeats 3 --no-cpu-baseline --no-decode --no-extras > $OUT/bench_abk.json 2>> $OUT/bench.err
+      env $(echo $cfg | tr ',' ' ') timeout 200 python bench.py --full --repeats 3 --no-cpu-baseline --no-decode --no-extras > $OUT/bench_abk.json 2>> $OUT/bench.err
       python - <<P
 import json
 d = json.load(open("$OUT/bench_abk.json"))
@@ -64,7 +64,7 @@ P
 fi
 if has rocprof; then
   rm -rf $OUT/prof_stats
-  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -- python $ROOT/bench.py --steps 3 --warmup 1 --repeats 1 --no-cpu-baseline --no-decode --no-extras > $OUT/bench_rocprof.json 2> $OUT/rocprof.err); echo "rocprof rc=$?"
+  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -- python $ROOT/bench.py --full --steps 3 --warmup 1 --repeats 1 --no-cpu-baseline --no-decode --no-extras > $OUT/bench_rocprof.json 2> $OUT/rocprof.err); echo "rocprof rc=$?"
   find $OUT/prof_stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/rocprofv3_kernel_stats.csv
   python tools/kernel_gaps.py $OUT/prof_stats > $OUT/kernel_gaps.txt 2>&1; cat $OUT/kernel_gaps.txt
   find $OUT/prof_stats -name "*kernel_trace.csv" -delete
@@ -158,12 +158,12 @@ if has recipe; then
   timeout 300 bash tools/recipe_stage45.sh run > $OUT/recipe_stage45.txt 2>&1; echo "recipe rc=$?"; tail -3 $OUT/recipe_stage45.txt
 fi
 if has tworank; then
-  WN_BENCH_BACKEND=gloo timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --repeats 2 --no-cpu-baseline --no-decode --no-extras > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err; echo "2-rank gloo rc=$?"; cut -c1-300 $OUT/bench_2rank_gloo.json
+  WN_BENCH_BACKEND=gloo timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 5 --warmup 2 --repeats 2 --no-cpu-baseline --no-decode --no-extras > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err; echo "2-rank gloo rc=$?"; cut -c1-300 $OUT/bench_2rank_gloo.json
 fi
 if has eightrank; then
   # world 8 on ONE GPU (functional: the ranks share the device and rendezvous over gloo): bench.py's N = 8 control flow -- eight
   # processes, three gradient buckets each, the exposed-exchange measurement, the max-over-ranks timing -- and train.py --n_gpus 8
-  WN_BENCH_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --steps 3 --warmup 1 --repeats 1 --profile-steps 0 --no-cpu-baseline --no-decode --no-extras > $OUT/bench_8rank_gloo.json 2> $OUT/bench_8rank_gloo.err; echo "8-rank gloo rc=$?"; cut -c1-300 $OUT/bench_8rank_gloo.json
+  WN_BENCH_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 8 --steps 3 --warmup 1 --repeats 1 --profile-steps 0 --no-cpu-baseline --no-decode --no-extras > $OUT/bench_8rank_gloo.json 2> $OUT/bench_8rank_gloo.err; echo "8-rank gloo rc=$?"; cut -c1-300 $OUT/bench_8rank_gloo.json
 fi
 lscpu | grep -E "Model name|^CPU\(s\)|Socket" > $OUT/host.txt
 free -g | head -2 >> $OUT/host.txt
