@@ -101,7 +101,8 @@ enum {
 #define WN_FLAG_NO_CHAIN 64   /* wn_backward (fused split kernels, kernel_size <= 2): since ABI v4 the data chain runs as ONE launch
                                * per layer (dX_l and gate'_{l-1} fused, the skip part of dZ pre-contracted for all layers by
                                * one matrix-bound launch; csrc/wn_fused.hip k_chain64s).  This flag restores the former
-                               * gate' + dX launch pair per layer (kept for A/B measurements and as an independent check) */
+                               * gate' + dX launch pair per layer (kept for A/B measurements and as an independent check) where
+                               * its gate' kernel holds a layer's skip weights (n_skipch <= 352); ignored beyond */
 #define WN_FLAG_BWD_OVERLAP_HEAD 16 /* with WN_FLAG_BWD_OVERLAP: only the post-net / skip weight gradients run on the side
                                * stream; the per-layer groups stay on the caller's stream */
 #define WN_FLAG_FWD_OVERLAP 8 /* wn_forward (fused kernels): the skip-sum contraction is issued in three chunks of layers on

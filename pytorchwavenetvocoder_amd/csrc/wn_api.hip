@@ -961,7 +961,10 @@ static int forward_stack(const Ctx& c, const float* params, const int64_t* x, co
     const long BRT = (long)B * d.R * T;
 
     WN_TRY(pack_weights(c, params));
-    if (c.mm_f16 && c.dw_ovf) WN_TRY(wn_fill(c.ws + c.w.dw_ovf, 0.0f, 1, c.st));   // overflow word of the fp16 pair launches of this pass
+    // [0] the overflow word of the fp16 pair launches of this pass; [1] a_mul; [2] max |dlogits| of the last loss call: a new forward
+    // pass invalidates it (WN_FLAG_DW_F16_AMAX_WS after a forward with no loss call behind it forces the six-product redo,
+    // include/wavenet_hip.h) -- the loss calls, wn_forward_loss's epilogue included, write it after this
+    if (c.dw_ovf) WN_TRY(wn_fill(c.ws + c.w.dw_ovf, 0.0f, 3, c.st));
     // front: one-hot + causal conv as a gather  (wavenet.py:513-516)
     WN_TRY(wn_front_gather(x, ws + w.wc_f, params + y.causal_b, ws + w.X, B, T, d.Q, d.R, d.K, c.st));
     // frame-rate aux projection for all layers at once: G[b][l*2R+o'][f] = Waux_l . h[b][:, f]

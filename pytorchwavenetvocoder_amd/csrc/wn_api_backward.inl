@@ -167,7 +167,15 @@ extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float
     // the skip gradients wait for the data chain and are produced per bucket together with the res_1x1 gradients.
     // Only with ONE layer bucket, where the skip weights belong to that bucket (wn_bucket_range); with several, they are part of the
     // head bucket, whose event would then be the last one recorded and hold back the exchange of every layer bucket behind it.
-    const bool skipres = c.split_bf16 && c.dw_f16_mul != 0.0f && d.L > 1 && lpb >= d.L && wn_dw_skipres_supported(d.S, d.R, d.L, d.L - 1);
+    // And only with launch groups (fmax, below) of at least two layers: the top group's fused launch writes every skip bias, and a
+    // top group of the last layer alone ([L-1, L): no res_1x1 gradient) does not take it -- its skip gradients would stay unwritten.
+    // Weight gradients are issued for groups of walked layers: a whole bucket in serial mode (largest launches), at
+    // most WN_DW_FLUSH_DEFAULT layers in overlap mode so that they start while the chain is still running; flags bits
+    // 8..15 override the group size.  (The split-K plan, hence the rounding, depends on the group size.)
+    int fmax = (flags >> 8) & 0xff;
+    if (fmax == 0) fmax = (side.rt && !(flags & WN_FLAG_BWD_OVERLAP_HEAD)) ? WN_DW_FLUSH_DEFAULT : d.L;
+    const bool skipres = c.split_bf16 && c.dw_f16_mul != 0.0f && d.L > 1 && lpb >= d.L && fmax >= 2 &&
+                         wn_dw_skipres_supported(d.S, d.R, d.L, d.L - 1);
     if (!skipres) {   // d skip_1x1.l.weight for all layers in one contraction; bias = rowsum(dSkip) for every layer
         WnGemmArgs g = wn_gemm_default();
         g.M = d.S; g.N = d.L * d.R; g.K = Tw;
@@ -201,9 +209,10 @@ extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float
     const bool aux_fused = (flags & WN_FLAG_AUX_FUSED) && c.fused && c.split_bf16 && d.U >= 16 && d.U % 16 == 0 && w.dGp != w.qp;
     // Chain mode (default for the fused split kernels, kernel_size <= 2): one launch per layer computes dX_l AND, from it,
     // dP_{l-1}; the skip part of every layer's dZ is contracted up front, dZs[b][l*R + i][t] = sum_s Wskip_l[s][i] dSkip[b][s][t]
-    // (layers 0 .. L-2; the last layer's gate' takes dSkip itself, it has no dX input).  WN_FLAG_NO_CHAIN: the former pair.
-    const bool chain = c.fused && c.split_bf16 && !(flags & WN_FLAG_NO_CHAIN) && w.dZs_floats > 0 &&
-                       wn_fused_chain_supported(d.R, d.K, d.S);
+    // (layers 0 .. L-2; the last layer's gate' takes dSkip itself, it has no dX input).  WN_FLAG_NO_CHAIN: the former pair, where
+    // its gate' kernel holds the layer's skip weights (n_skipch <= 352); ignored beyond.
+    const bool chain = c.fused && c.split_bf16 && !((flags & WN_FLAG_NO_CHAIN) && wn_fused_gate_split_supported(d.S)) &&
+                       w.dZs_floats > 0 && wn_fused_chain_supported(d.R, d.K, d.S);
     const long zs_bstride = (long)d.L * d.R * T;
     if (chain) {
         WnGemmArgs g = wn_gemm_default();
@@ -343,11 +352,6 @@ extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float
         return 0;
     };
 
-    // Weight gradients are issued for groups of walked layers: a whole bucket in serial mode (largest launches), at
-    // most WN_DW_FLUSH_DEFAULT layers in overlap mode so that they start while the chain is still running; flags bits
-    // 8..15 override the group size.  (The split-K plan, hence the rounding, depends on the group size.)
-    int fmax = (flags >> 8) & 0xff;
-    if (fmax == 0) fmax = (side.rt && !(flags & WN_FLAG_BWD_OVERLAP_HEAD)) ? WN_DW_FLUSH_DEFAULT : d.L;
     int bucket_hi = d.L;  // layers [l, bucket_hi) have been walked but not flushed yet
     for (int l = d.L - 1; l >= 0; --l) {
         const int dil = dilation_of(cfg, l);

@@ -23,6 +23,8 @@ int wn_fused_resblock_fwd(const float* wd_f, const float* wres_f, const float* c
 // fused forward then does not store at all (Gt == NULL there); the kernels rebuild g = z / s (s = sigmoid > 0).
 int wn_fused_bwd_gate(const float* wskip, const float* wres, const float* dSk, const float* dXn, const float* S,
                       const float* Gt, int gt_is_z, float* dP, int B, int T, int Sch, int split, wn_stream_t st);
+// 1: the split form of the two launchers (the skip and res weights of a layer resident in LDS as bf16 pieces) holds Sch skip channels
+int wn_fused_gate_split_supported(int Sch);
 
 // The same plus the partial sums of the aux-path gradients (split kernels only; U % 16 == 0, T == U * F), so that dP
 // is not re-read for them (wn_aux_bwd):

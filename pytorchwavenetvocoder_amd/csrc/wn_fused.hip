@@ -1920,6 +1920,10 @@ static int launch_conv64(const ConvArgs& a, int split, wn_stream_t st) {
     return 1;
 }
 
+int wn_fused_gate_split_supported(int Sch) {
+    return Sch % 32 == 0 && (size_t)(Sch / 32 + 2) * 2 * 6144 <= 160 * 1024;   // launch_conv64's split LDS, with the res segment
+}
+
 int wn_fused_bwd_gate(const float* wskip, const float* wres, const float* dSk, const float* dXn, const float* S, const float* Gt,
                       int gt_is_z, float* dP, int B, int T, int Sch, int split, wn_stream_t st) {
     WN_PROF("fused_bwd_gate", 2.0 * (double)B * T * 64.0 * (Sch + (dXn ? 64.0 : 0.0)),

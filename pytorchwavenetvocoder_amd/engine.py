@@ -333,10 +333,15 @@ class WaveNetEngine(object):
         if t_first is None:
             t_first = self._fwd_window
         flags = self.flags
-        family = _lib.FLAG_NO_FUSED | _lib.FLAG_EXACT_MFMA | _lib.FLAG_MM_F16PAIR | _lib.FLAG_CHAIN_F16PAIR
-        if (flags ^ self._fwd_flags) & family and not repack:
-            raise _lib.WnError("engine.flags changed the kernel family (NO_FUSED / EXACT_MFMA / MM_F16PAIR) since the forward call: "
-                               "the families save different activations and weight sets -- run forward again")
+        # NO_FUSED / EXACT_MFMA: the kernel families save different ACTIVATIONS (the fused forward saves no Gt, the layered
+        # backward reads it) -- nothing rebuilds those, so a change always raises.  MM_F16PAIR / CHAIN_F16PAIR change only the
+        # weight images, which repack=True rebuilds from the parameters.
+        changed = flags ^ self._fwd_flags
+        if changed & (_lib.FLAG_NO_FUSED | _lib.FLAG_EXACT_MFMA) or (changed & (_lib.FLAG_MM_F16PAIR | _lib.FLAG_CHAIN_F16PAIR)
+                                                                      and not repack):
+            raise _lib.WnError("engine.flags changed the kernel family (NO_FUSED / EXACT_MFMA / MM_F16PAIR / CHAIN_F16PAIR) since the "
+                               "forward call: the families save different activations and weight sets -- run forward again "
+                               "(repack=True rebuilds the weight sets of MM_F16PAIR / CHAIN_F16PAIR, not the activations)")
         flags = self._dw_mode_flags(flags, dlogits, dlogits_bound)
         if repack:
             flags |= _lib.FLAG_REPACK
