@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 9
+#define WN_ABI_VERSION 10
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -282,6 +282,22 @@ int wn_backward(const WnConfig* cfg, int B, int T, const float* params, const in
 int wn_backward_window(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
                        const float* dlogits, int t_first, float* grads, void* ws, size_t ws_bytes, void* const* events,
                        int n_events, int layers_per_bucket, int flags, void* stream);
+
+/* wn_backward_window plus the gradient with respect to the aux features (since ABI v10): dh[b][a][f] = dL/dh, (B, n_aux, F)
+ * contiguous like h (F = T / upsampling_factor, or T without the upsampling layer), scaled like the weight gradients.
+ *   with the upsampling layer:  dh[b][a][f] = sum_l sum_c Waux_l[c][a] * dG_l[b][c][f],  dG_l[b][c][f] = sum_j w_up[j] dP_l[b][c][fU + j]
+ *   without it:                 dh[b][a][t] = sum_l sum_c Waux_l[c][a] * dP_l[b][c][t]
+ * (c: the 2 n_resch rows of aux_1x1_sigmoid then aux_1x1_tanh; the biases do not enter).  ONE contraction over all layers
+ * (K = L * 2 n_resch) on the fp32-input matrix cores after the last weight-gradient group, on its stream: exact fp32 products,
+ * every element a fixed-order sum -- the same bits on every call and under every launch plan that leaves dP itself unchanged.
+ *   dh == NULL:    exactly wn_backward_window (same launches, same results).
+ *   grads == NULL: a frozen model -- only what dh needs runs (the data chain, the post-net data gradients, dG); no weight
+ *                  gradient, no reduction of one and no scale scan for one (WN_FLAG_MM_F16PAIR keeps the one of its data
+ *                  contractions).  Requires dh != NULL and events == NULL, n_events == 0.
+ * Same workspace (wn_workspace_bytes) as wn_backward; the x gradient is not defined (x holds class indices). */
+int wn_backward_dh(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                   const float* dlogits, int t_first, float* grads, float* dh, void* ws, size_t ws_bytes, void* const* events,
+                   int n_events, int layers_per_bucket, int flags, void* stream);
 
 /* torch.optim.Adam step over the flat buffers (reference train.py:457-460,539): L2-in-gradient
  * weight decay, bias correction with `step` (1-based); [skip_lo, skip_hi) is left untouched. */

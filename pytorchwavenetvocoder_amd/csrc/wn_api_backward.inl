@@ -73,16 +73,19 @@ extern "C" int wn_backward(const WnConfig* cfg, int B, int T, const float* param
     return wn_backward_window(cfg, B, T, params, x, h, dlogits, 0, grads, wsp, ws_bytes, events, n_events, lpb, flags, stream);
 }
 
-extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
-                                  const float* dlogits, int t_first, float* grads, void* wsp, size_t ws_bytes,
-                                  void* const* events, int n_events, int lpb, int flags, void* stream) {
-    api_enter();
+// grads == NULL (wn_backward_dh only): the data gradients and dh alone -- no weight-gradient launch, no reduction of one, and no
+// scale of the fp16 pair weight gradients (the data contractions of WN_FLAG_MM_F16PAIR still take theirs).  dh != NULL: dL/dh
+// (wn_auxdh.inl) after the last flush group, on its stream; the flush groups then keep dG of every layer (at its own offset).
+static int backward_impl(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                         const float* dlogits, int t_first, float* grads, float* dh, void* wsp, size_t ws_bytes,
+                         void* const* events, int n_events, int lpb, int flags, void* stream) {
     Ctx c;
     WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, flags, stream));
-    if (!params || !x || !h || !dlogits || !grads) return fail(1, "NULL argument");
+    if (!params || !x || !h || !dlogits || (!grads && !dh)) return fail(1, "NULL argument");
     c.params = params;
     if (t_first < 0 || t_first >= T) return fail(1, "t_first=%d outside [0,%d)", t_first, T);
-    if (c.dw_f16_mode) {   // before the side stream forks: overflow word := 0, a_mul := the scale of this call's gradient (wn_elem.h)
+    const bool wgrad = grads != nullptr;
+    if (c.dw_f16_mode && (wgrad || c.mm_f16)) {   // before the side stream forks: overflow word := 0, a_mul := the scale of this call's gradient (wn_elem.h)
         const int tw0 = (t_first / 128) * 128;
         float* words = c.ws + c.w.dw_ovf;
         if (c.dw_f16_mode == 1) {
@@ -149,14 +152,14 @@ extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float
         if (t0 > 0) WN_TRY(wn_fill_cols(ws + w.dSk, (long)B * d.S, T, t0, c.st));
     }
     WN_TRY(side_link(side.rt, c.st, cs.st));  // fork: dO2, dSkip (and everything before this call) are ready
-    {   // d conv_post_2.{weight,bias}
+    if (wgrad) {   // d conv_post_2.{weight,bias}
         WnGemmArgs g = wn_gemm_default();
         g.M = d.Qo; g.N = d.S; g.K = Tw;
         g.A = dlogits + t0; g.lda = T; g.a_zstride = (long)d.Qo * T;
         g.B = ws + w.O2 + t0; g.ldb = T; g.b_zstride = (long)d.S * T; g.b_clen = Tw; g.tag = "dw_post2";
         WN_TRY(dw_gemm(cs, g, dw_out_plain(grads + y.post2_w, d.S, grads + y.post2_b)));
     }
-    {   // d conv_post_1.{weight,bias}
+    if (wgrad) {   // d conv_post_1.{weight,bias}
         WnGemmArgs g = wn_gemm_default();
         g.M = d.S; g.N = d.S; g.K = Tw;
         g.A = ws + w.dO2 + t0; g.lda = T; g.a_zstride = (long)d.S * T;
@@ -176,7 +179,7 @@ extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float
     if (fmax == 0) fmax = (side.rt && !(flags & WN_FLAG_BWD_OVERLAP_HEAD)) ? WN_DW_FLUSH_DEFAULT : d.L;
     const bool skipres = c.split_bf16 && c.dw_f16_mul != 0.0f && d.L > 1 && lpb >= d.L && fmax >= 2 &&
                          wn_dw_skipres_supported(d.S, d.R, d.L, d.L - 1);
-    if (!skipres) {   // d skip_1x1.l.weight for all layers in one contraction; bias = rowsum(dSkip) for every layer
+    if (wgrad && !skipres) {   // d skip_1x1.l.weight for all layers in one contraction; bias = rowsum(dSkip) for every layer
         WnGemmArgs g = wn_gemm_default();
         g.M = d.S; g.N = d.L * d.R; g.K = Tw;
         g.A = ws + w.dSk + t0; g.lda = T; g.a_zstride = (long)d.S * T;
@@ -232,6 +235,17 @@ extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float
         const int nl = hi - lo;
         const long lb_lo = layer_base(y, d, lo);
         float* dc = ws + w.dc + (long)lo * 2 * d.R;
+        float* dG = ws + w.dG + (dh ? (long)lo * B * 2 * d.R * F : 0);   // dh: every layer's dG stays for the dh launch
+        if (!wgrad) {   // dG alone (dh through the upsampling layer); without it dh reads dP
+            if (d.U > 0 && aux_fused)
+                WN_TRY(wn_aux_finish(ws + w.dGp + (long)lo * B * 2 * d.R * (T / 16), (long)B * 2 * d.R * (T / 16),
+                                     ws + w.qp + (long)lo * B * T, (long)B * T, dG,
+                                     ws + w.dw_partial + (long)lo * B * 2 * d.R * Ue, B, T, 2 * d.R, Ue, F, nl, c.st));
+            else if (d.U > 0)
+                WN_TRY(wn_aux_bwd(ws + w.P + (long)lo * P_L, P_L, ws + w.G + (long)lo * 2 * d.R * F, g_bstride, upw,
+                                  dG, ws + w.dw_partial + (long)lo * B * 2 * d.R * Ue, B, T, 2 * d.R, Ue, F, nl, c.st));
+            return 0;
+        }
         {   // d dil_{sigmoid,tanh}.l.conv.weight ; dc_l = rowsum(dP_l) -> conv + aux biases
             WnGemmArgs g = wn_gemm_default();
             g.M = 2 * d.R; g.N = d.K * d.R; g.K = T;
@@ -332,13 +346,13 @@ extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float
                 // through the upsampling layer: dG[f] = sum_j w[j] dP[fU+j]; dW = dG.h^T + b_up*dc (x) 1
                 if (aux_fused)
                     WN_TRY(wn_aux_finish(ws + w.dGp + (long)lo * B * 2 * d.R * (T / 16), (long)B * 2 * d.R * (T / 16),
-                                         ws + w.qp + (long)lo * B * T, (long)B * T, ws + w.dG,
+                                         ws + w.qp + (long)lo * B * T, (long)B * T, dG,
                                          ws + w.dw_partial + (long)lo * B * 2 * d.R * Ue, B, T, 2 * d.R, Ue, F, nl, c.st));
                 else
                     WN_TRY(wn_aux_bwd(ws + w.P + (long)lo * P_L, P_L, ws + w.G + (long)lo * 2 * d.R * F, g_bstride, upw,
-                                      ws + w.dG, ws + w.dw_partial + (long)lo * B * 2 * d.R * Ue, B, T, 2 * d.R, Ue, F, nl, c.st));
+                                      dG, ws + w.dw_partial + (long)lo * B * 2 * d.R * Ue, B, T, 2 * d.R, Ue, F, nl, c.st));
                 g.K = F;
-                g.A = ws + w.dG; g.lda = F; g.a_zstride = (long)2 * d.R * F; g.a_lstride = (long)B * 2 * d.R * F;
+                g.A = dG; g.lda = F; g.a_zstride = (long)2 * d.R * F; g.a_lstride = (long)B * 2 * d.R * F;
                 g.B = h; g.ldb = F; g.b_zstride = (long)d.A * F; g.b_lstride = 0; g.b_clen = F;
                 o.addend_m = dc; o.addend_scale_ptr = params + y.up_b; o.addend_lstride = 2 * d.R;
             } else {
@@ -457,6 +471,19 @@ extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float
             }
         }
     }
+    if (dh) {   // dL/dh = sum_l Waux_l^T dG_l (dP_l without the upsampling layer): every layer's operand is final on cl.st
+        const int N = d.U > 0 ? F : T;
+        // split-K scratch: written and read only here -- dZ (the layered path's per-layer scratch) with the upsampling layer,
+        // dG (unused without it) otherwise
+        float* scratch = d.U > 0 ? ws + w.dZ : ws + w.dG;
+        const long scratch_floats = d.U > 0 ? BRT : (long)d.L * B * 2 * d.R * F;
+        WN_TRY(wn_aux_dh(ws + w.waux_f, d.A, d.L * 2 * d.R, d.U > 0 ? ws + w.dG : ws + w.P, d.U > 0 ? (long)B * 2 * d.R * F : P_L,
+                         (long)2 * d.R * N, 2 * d.R, N, B, dh, scratch, scratch_floats, cl.st));
+    }
+    if (!wgrad) {
+        WN_TRY(side_link(side.rt, cs.st, c.st));
+        return rt_check("wn_backward_dh");
+    }
     const float* dXn = ws + w.dXall;  // dL/dx_0
     // ---- front conv: scatter over the token indices, or (large tables) the one-hot contraction ----
     if (wn_front_dw_supported(d.R, d.K, d.Q) &&
@@ -493,6 +520,22 @@ extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float
     bucket++;
     WN_TRY(side_link(side.rt, cs.st, c.st));  // join: the caller's stream continues after every gradient
     return rt_check("wn_backward");
+}
+
+extern "C" int wn_backward_window(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                                  const float* dlogits, int t_first, float* grads, void* wsp, size_t ws_bytes,
+                                  void* const* events, int n_events, int lpb, int flags, void* stream) {
+    api_enter();
+    return backward_impl(cfg, B, T, params, x, h, dlogits, t_first, grads, nullptr, wsp, ws_bytes, events, n_events, lpb, flags, stream);
+}
+
+extern "C" int wn_backward_dh(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                              const float* dlogits, int t_first, float* grads, float* dh, void* wsp, size_t ws_bytes,
+                              void* const* events, int n_events, int lpb, int flags, void* stream) {
+    api_enter();
+    if (!grads && !dh) return fail(1, "wn_backward_dh: grads and dh are both NULL");
+    if (!grads && (events || n_events)) return fail(1, "wn_backward_dh: bucket events need grads (no weight gradients are produced)");
+    return backward_impl(cfg, B, T, params, x, h, dlogits, t_first, grads, dh, wsp, ws_bytes, events, n_events, lpb, flags, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -97,6 +97,12 @@ int wn_aux_bwd(const float* dP, long dp_lstride, const float* G, long g_bstride,
 // dGp += l*dgp_lstride, qp += l*qp_lstride; dG / dw_partial laid out as wn_aux_bwd writes them.
 int wn_aux_finish(const float* dGp, long dgp_lstride, const float* qp, long qp_lstride, float* dG, float* dw_partial, int B,
                   int T, int R2, int U, int F, int nl, wn_stream_t st);
+// Gradient with respect to the aux features (wn_auxdh.inl), all layers in one contraction over k = l*R2 + c (K = L*R2):
+//   dh[b][m][n] = sum_k W[m][k] * S[k / R2][b][k % R2][n]        W: M x K row-major (waux_f), S += l*s_lstride + b*s_bstride, rows of N
+// dh is (B, M, N) contiguous.  Split-K partials (when the grid would be small) go to `scratch` (at most scratch_floats) and are
+// summed in a fixed order by a second launch; 0 on success.
+int wn_aux_dh(const float* W, int M, int K, const float* S, long s_lstride, long s_bstride, int R2, int N, int B, float* dh,
+              float* scratch, long scratch_floats, wn_stream_t st);
 
 // out[map(m,n)] (=|+=) scale * sum_z partial[z][m*N+n] (+ addend_m[m]*addend_scale)
 // map(m,n) = (m/m_seg)*m_seg_stride + (m%m_seg)*m_stride + (n/n_seg)*n_seg_stride + (n%n_seg)*n_stride

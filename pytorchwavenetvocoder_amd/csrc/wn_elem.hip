@@ -1580,3 +1580,5 @@ int wn_decode_fill_queues(const float* X, float* dst, int L, int B, int R, int T
               elem_stride, utt_stride);
     return 0;
 }
+
+#include "wn_auxdh.inl"

@@ -312,7 +312,8 @@ class WaveNetEngine(object):
         self._dlogits_bound = None   # (the mixture head's loss call measures no maximum: backward scans its gradient)
         return loss, dout
 
-    def backward(self, dlogits, events=None, layers_per_bucket=0, t_first=None, repack=False, dlogits_bound=None):
+    def backward(self, dlogits, events=None, layers_per_bucket=0, t_first=None, repack=False, dlogits_bound=None, dh=None,
+                 param_grads=True):
         """Backward of the last ``forward`` / ``forward_loss`` call; fills ``self.grads()`` completely.  ``t_first``: the
         caller guarantees ``dlogits[:, :, :t_first] == 0`` (the training loss covers ``[:, receptive_field:]``,
         train.py:534-536): the post-net / skip part of the backward pass then runs over the loss window only
@@ -327,7 +328,11 @@ class WaveNetEngine(object):
         ``dlogits_bound``: with ``FLAG_DW_F16PAIR`` in ``self.flags`` the weight gradients take the fp16 pair split
         (include/wavenet_hip.h), scaled by max |dlogits|.  Default (None): MEASURED -- by the loss call for the unmodified
         tensor ``forward_loss`` / ``loss`` returned (free), by one pass over any other gradient (autograd's grad_output, the
-        mixture-of-logistics head).  A number: the caller's own promise ``max |dlogits| <= dlogits_bound``, taken as given."""
+        mixture-of-logistics head).  A number: the caller's own promise ``max |dlogits| <= dlogits_bound``, taken as given.
+
+        ``dh``: a contiguous fp32 tensor shaped like the forward call's ``h`` (B, n_aux, T / upsampling_factor or T) on the
+        model's device; it receives dL/dh (``wn_backward_dh``).  ``param_grads=False`` (with ``dh``): no weight gradient is
+        computed (a frozen model), ``self.grads()`` is left as it is and the call returns None."""
         if self._last_shape is None:
             raise _lib.WnError("backward() without a preceding forward()")
         if t_first is None:
@@ -355,13 +360,29 @@ class WaveNetEngine(object):
         self._check_device(dlogits)
         if tuple(dlogits.shape) != (B, self.out_channels, T) or not dlogits.is_contiguous():
             raise ValueError("dlogits must be a contiguous (B,Q,T) tensor")
-        g = self.grads()
+        if dh is not None:
+            self._check_device(dh)
+            want = (B, self.cfg.n_aux, T // self.cfg.upsampling_factor if self.cfg.upsampling_factor > 0 else T)
+            if tuple(dh.shape) != want or dh.dtype != torch.float32 or not dh.is_contiguous():
+                raise ValueError("dh must be a contiguous float32 tensor of shape %s, got %s %s%s"
+                                 % (want, tuple(dh.shape), dh.dtype, "" if dh.is_contiguous() else " (not contiguous)"))
+        elif not param_grads:
+            raise ValueError("param_grads=False needs dh: the call would compute nothing")
+        if not param_grads and events:
+            raise ValueError("bucket events need the weight gradients (param_grads=True)")
+        g = self.grads() if param_grads else None
         ws = self.workspace(B, T)
         if events:
             arr = (ctypes.c_void_p * len(events))(*[ctypes.c_void_p(e) for e in events])
             n_ev = len(events)
         else:
             arr, n_ev = None, 0
+        if dh is not None or not param_grads:
+            rc = self.lib.wn_backward_dh(ctypes.byref(self.cfg), B, T, _ptr(self.flat_params), _ptr(x), _ptr(h), _ptr(dlogits),
+                                         int(t_first), _ptr(g), _ptr(dh), _ptr(ws), ws.numel() * 4, arr, n_ev,
+                                         int(layers_per_bucket), flags, _stream_handle(self.device))
+            self.lib.check(rc, "wn_backward_dh")
+            return g
         rc = self.lib.wn_backward_window(ctypes.byref(self.cfg), B, T, _ptr(self.flat_params), _ptr(x), _ptr(h),
                                          _ptr(dlogits), int(t_first), _ptr(g), _ptr(ws), ws.numel() * 4, arr, n_ev,
                                          int(layers_per_bucket), flags, _stream_handle(self.device))

@@ -227,7 +227,8 @@ class _UpSamplingFunction(torch.autograd.Function):
 
 
 class _WaveNetFunction(torch.autograd.Function):
-    """autograd bridge: forward = wn_forward, backward = wn_backward (one flat gradient buffer)."""
+    """autograd bridge: forward = wn_forward, backward = wn_backward (one flat gradient buffer); with h requiring a gradient
+    wn_backward_dh, which also writes dL/dh (without the weight gradients when no parameter requires one)."""
 
     @staticmethod
     def forward(ctx, model, x, h, *params):
@@ -236,6 +237,7 @@ class _WaveNetFunction(torch.autograd.Function):
         model._fwd_serial += 1
         ctx.model = model
         ctx.serial = model._fwd_serial
+        ctx.h_dtype = h.dtype
         return logits.transpose(1, 2)
 
     @staticmethod
@@ -252,11 +254,18 @@ class _WaveNetFunction(torch.autograd.Function):
             eng.lib.check(eng.lib.wn_op_transpose_last2(grad_out.data_ptr(), dl.data_ptr(), B, T, Q, st), "wn_op_transpose_last2")
         else:   # a view that already is (B, Q, T) underneath (e.g. the transposed logits themselves), or another dtype
             dl = grad_out.transpose(1, 2).contiguous().float()
-        flat = eng.backward(dl).clone()
+        dh = None
+        if ctx.needs_input_grad[2]:
+            h = eng._last_inputs[1]
+            dh = torch.empty(h.shape, dtype=torch.float32, device=h.device)
+        if not any(ctx.needs_input_grad[3:]):   # a frozen model: dh alone
+            eng.backward(dl, dh=dh, param_grads=False)
+            return (None, None, dh.to(ctx.h_dtype)) + (None,) * len(model._param_slices)
+        flat = eng.backward(dl, dh=dh).clone()
         grads = []
         for (off, n, shape, dead) in model._param_slices:
             grads.append(None if dead else flat[off:off + n].view(shape))
-        return (None, None, None) + tuple(grads)
+        return (None, None, None if dh is None else dh.to(ctx.h_dtype)) + tuple(grads)
 
 
 class WaveNet(nn.Module):
@@ -388,13 +397,14 @@ class WaveNet(nn.Module):
         params = tuple(self.parameters())
         return _WaveNetFunction.apply(self, x, h, *params)
 
-    def loss_and_backward(self, x, h, t, t_start=None, grad_scale=1.0, events=None, layers_per_bucket=0):
+    def loss_and_backward(self, x, h, t, t_start=None, grad_scale=1.0, events=None, layers_per_bucket=0, aux_grad=False):
         """Fused training half-step: forward -> CrossEntropy on ``[:, t_start:]`` -> backward
         (reference train.py:533-538) without an autograd graph.
 
         Leaves the gradients in the flat buffer (``p.grad`` of every parameter is a view of it;
         ``None`` for the dead last ``res_1x1``) and returns the mean loss as a 1-element device
-        tensor (no host sync).  ``grad_scale`` multiplies the gradients (1/world_size for DP)."""
+        tensor (no host sync).  ``grad_scale`` multiplies the gradients (1/world_size for DP).
+        ``aux_grad=True``: returns ``(loss, dh)`` with dh = d(loss)/dh (scaled by ``grad_scale`` as well)."""
         eng = self._engine
         if t_start is None:
             t_start = eng.receptive_field
@@ -402,17 +412,21 @@ class WaveNet(nn.Module):
         # never reach memory), and the backward pass runs its post-net part over the loss window only
         loss, dlogits = eng.forward_loss(x, h, t, t_start=t_start, grad_scale=grad_scale)
         self._fwd_serial += 1
-        flat = eng.backward(dlogits, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start)
+        dh = self._aux_grad_buffer(h) if aux_grad else None
+        flat = eng.backward(dlogits, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh)
         for p, (off, n, shape, dead) in zip(self.parameters(), self._param_slices):
             p.grad = None if dead else flat[off:off + n].view(shape)
-        return loss
+        return (loss, dh) if aux_grad else loss
+
+    def _aux_grad_buffer(self, h):
+        return torch.empty(h.shape, dtype=torch.float32, device=self._engine.device)
 
     def mol_loss_and_backward(self, x, h, y, t_start=None, grad_scale=1.0, num_classes=65536, log_scale_min=None,
-                              events=None, layers_per_bucket=0):
+                              events=None, layers_per_bucket=0, aux_grad=False):
         """Training half-step of the mixture-of-logistics head (``n_mixture > 0``): forward -> mean negative
         log-likelihood of the waveform ``y`` (B, T) in [-1, 1] (the value of the NEXT sample at every position,
         like ``t`` of the softmax head) on ``[:, t_start:]`` -> backward.  Gradients land as in
-        ``loss_and_backward``."""
+        ``loss_and_backward``; ``aux_grad=True`` returns ``(loss, dh)`` as there."""
         if self.n_mixture <= 0:
             raise ValueError("this model has the softmax head (n_mixture = 0)")
         # ONE clamp for the likelihood and for sampling: the constructor's value (it travels in model.conf; a per-call
@@ -429,10 +443,11 @@ class WaveNet(nn.Module):
             t_start = eng.receptive_field
         loss, dout = eng.mol_loss(out, y, t_start=t_start, grad_scale=grad_scale, num_classes=num_classes,
                                   log_scale_min=log_scale_min)
-        flat = eng.backward(dout, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start)
+        dh = self._aux_grad_buffer(h) if aux_grad else None
+        flat = eng.backward(dout, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh)
         for p, (off, n, shape, dead) in zip(self.parameters(), self._param_slices):
             p.grad = None if dead else flat[off:off + n].view(shape)
-        return loss
+        return (loss, dh) if aux_grad else loss
 
     # ---- generation (reference wavenet.py:243-511) --------------------------------------------
     def _window_logits(self, x, h_up):
