@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 10
+#define WN_ABI_VERSION 11
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -258,6 +258,30 @@ int wn_forward_loss(const WnConfig* cfg, int B, int T, const float* params, cons
                     const int64_t* target, int t_start, float grad_scale, float loss_scale, float* loss, float* dlogits,
                     float* logits_scratch, void* ws, size_t ws_bytes, int flags, void* stream);
 
+/* The loss of a PADDED batch of sequences of unequal length (since ABI v11; additions only): wn_softmax_ce_loss and
+ * wn_forward_loss with a per-sequence end.  It is nn.CrossEntropyLoss() -- the reference's own loss object, train.py:461 -- on
+ * [:, t_start:] with the targets set to its default ignore_index (-100) from t_end[b] on:
+ *   t_end   : (B,) int32 on the DEVICE, 1 <= t_end[b] <= T: sequence b carries loss on the positions [t_start, t_end[b]);
+ *             a sequence with t_end[b] <= t_start carries none.  NULL = T for every sequence: the dense entry point, bit for bit.
+ *   n_loss  : N = sum_b max(t_end[b] - t_start, 0), counted by the CALLER on the host (the lengths are host integers, so the
+ *             step gains no device-to-host synchronisation); the library does not read t_end back to check it.
+ *             n_loss <= 0, n_loss > B * (T - t_start), and t_end == NULL with n_loss != B * (T - t_start) are errors.
+ *   loss    = loss_scale * (sum of the per-position losses over the loss positions) / N
+ *   dlogits = grad_scale / N * d(sum)/d(logits) on the loss positions and EXACTLY 0.0f on every other position, the padding
+ *             included -- so the backward entry points need no lengths: wn_backward_window / wn_backward_dh with
+ *             t_first = t_start contract zeros there, every parameter gradient is that of the valid positions alone, and
+ *             dh is exactly zero on frames wholly behind a sequence's end (the network is causal).
+ * The padding -- x, h, target behind t_end[b] -- may hold anything finite; targets there are still read modulo n_quantize,
+ * they carry no loss.  The fused form is taken exactly where the dense entry point takes it (wn_forward_loss_fused); the
+ * residual stack and the backward pass still compute every position of the (B, T) rectangle. */
+int wn_softmax_ce_loss_ragged(const WnConfig* cfg, int B, int T, const float* logits, const int64_t* target, int t_start,
+                              const int32_t* t_end, int64_t n_loss, float grad_scale, float loss_scale, float* loss,
+                              float* dlogits, void* ws, size_t ws_bytes, void* stream);
+int wn_forward_loss_ragged(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                           const int64_t* target, int t_start, const int32_t* t_end, int64_t n_loss, float grad_scale,
+                           float loss_scale, float* loss, float* dlogits, float* logits_scratch, void* ws, size_t ws_bytes,
+                           int flags, void* stream);
+
 /* Backward of wn_forward (what autograd does for train.py:538): writes EVERY element of the flat
  * gradient buffer `grads` (the dead range gets zeros).  `ws` must still hold the matching
  * wn_forward call, made with the same WN_FLAG_NO_FUSED / WN_FLAG_EXACT_MFMA choice (the two kernel
@@ -344,6 +368,12 @@ int wn_op_gemm(const struct WnGemmArgs* args, void* stream);
 int wn_mol_loss(const WnConfig* cfg, int B, int T, const float* out, const float* y, int t_start, float grad_scale,
                 float loss_scale, int num_classes, float log_scale_min, float* loss, float* dout, void* workspace,
                 size_t workspace_bytes, void* stream);
+
+/* wn_mol_loss for a padded batch of unequal lengths (since ABI v11): t_end / n_loss, the mask and the divisor exactly as
+ * wn_softmax_ce_loss_ragged defines them; y behind t_end[b] may hold anything finite, dout is exactly 0.0f there. */
+int wn_mol_loss_ragged(const WnConfig* cfg, int B, int T, const float* out, const float* y, int t_start, const int32_t* t_end,
+                       int64_t n_loss, float grad_scale, float loss_scale, int num_classes, float log_scale_min, float* loss,
+                       float* dout, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- autoregressive decode (BASELINE config 5) -------------------------------------------------
  * Replaces WaveNet.fast_generate / batch_fast_generate / _generate_residual_forward

@@ -112,7 +112,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -123,6 +123,7 @@ EXPORTS = [
     "wn_decode_steps", "wn_decode_stream_bytes",
     "wn_decode_layered_state_floats", "wn_decode_layered_error_offset", "wn_decode_layered_prepare", "wn_decode_layered_steps", "wn_mol_loss",
     "wn_decode_ctx_aux", "wn_decode_prefill_workspace_bytes", "wn_decode_prefill",
+    "wn_softmax_ce_loss_ragged", "wn_forward_loss_ragged", "wn_mol_loss_ragged",
 ]
 
 
@@ -164,6 +165,9 @@ class WnLibrary(object):
         L.wn_softmax_ce_loss.argtypes = [cfgp, i, i, vp, vp, i, f, f, vp, vp, vp, sz, vp]
         L.wn_forward_loss_fused.argtypes = [cfgp, i, i, i]
         L.wn_forward_loss.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, f, f, vp, vp, vp, vp, sz, i, vp]
+        # the ragged forms: (.., t_start, t_end (device int32 or NULL), n_loss, ..)
+        L.wn_softmax_ce_loss_ragged.argtypes = [cfgp, i, i, vp, vp, i, vp, i64, f, f, vp, vp, vp, sz, vp]
+        L.wn_forward_loss_ragged.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, i64, f, f, vp, vp, vp, vp, sz, i, vp]
         L.wn_backward.argtypes = [cfgp, i, i, vp, vp, vp, vp, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
         L.wn_backward_window.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
         L.wn_backward_dh.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
@@ -190,6 +194,7 @@ class WnLibrary(object):
         L.wn_decode_aux.argtypes = [cfgp, i, i, vp, vp, vp, vp]
         L.wn_decode_steps.argtypes = [cfgp, i, vp, vp, vp, i, i, vp, i64, vp, vp, i, i, vp, vp, vp, i, vp, f, vp]
         L.wn_mol_loss.argtypes = [cfgp, i, i, vp, vp, i, f, f, i, f, vp, vp, vp, sz, vp]
+        L.wn_mol_loss_ragged.argtypes = [cfgp, i, i, vp, vp, i, vp, i64, f, f, i, f, vp, vp, vp, sz, vp]
         L.wn_decode_layered_state_floats.argtypes = [cfgp, i, i]
         L.wn_decode_layered_state_floats.restype = i64
         L.wn_decode_layered_error_offset.argtypes = [cfgp, i, i]

@@ -139,7 +139,9 @@ def train_generator(wav_list, feat_list, receptive_field,
                     shard=None,
                     with_wave=False,
                     workers=None,
-                    transforms_elementwise=False):
+                    transforms_elementwise=False,
+                    pad_utterances=False,
+                    n_quantize=256):
     """Minibatch generator with the reference's four batching modes (train.py:67-312).
 
     Yields ``((batch_x, batch_h), batch_t)``: x/t int64 (B, T) with t the next sample of x, h float
@@ -152,6 +154,17 @@ def train_generator(wav_list, feat_list, receptive_field,
     skipped instead of being done ``world`` times).
     ``with_wave=True`` (mixture-of-logistics head): additionally yields ``batch_y`` float (B, T), the waveform
     value of the next sample at every position (the un-quantised counterpart of ``batch_t``).
+
+    ``pad_utterances=True`` (NOT a reference mode; only with ``batch_length=None`` and ``batch_size > 1``, where the reference
+    falls back to a batch size of 1 because its loss has no mask): ``batch_size`` consecutive utterances of the list are
+    padded to the longest of them and yielded as ONE minibatch, followed by ``lengths`` and ``all_lengths`` (CPU int64
+    tensors): the valid positions of the rows yielded, for ``loss_and_backward(lengths=)``, and of all ``batch_size``
+    rows of the minibatch.  Tokens and targets pad with ``n_quantize // 2``, features by repeating the utterance's last
+    frame, the waveform of ``with_wave`` with 0; with the upsampling layer an utterance is a whole number of frames, so T
+    stays a multiple of ``upsampling_factor``.  ``shard=(rank, world)``: a rank takes its ``_shard_range`` rows of every
+    minibatch and pads to ITS OWN longest utterance (ranks may run different T); every rank reads every utterance in this
+    mode already, so ``all_lengths`` -- and with it the global count of loss positions -- needs no communication.  A
+    group left incomplete at the end of a walk of the list is dropped, like a partly filled minibatch of the windowed modes.
 
     ``workers`` (default ``slicer_workers()``): the reference's generator is ONE numpy thread behind a queue that is in effect one
     deep (train.py:67, utils.py:216) -- at 8.7 ms per minibatch on an MI355X that thread (file reads 3 ms, mu-law 1.5 ms, scaler,
@@ -180,7 +193,8 @@ def train_generator(wav_list, feat_list, receptive_field,
         logging.warning("batch length is decreased due to upsampling (%d -> %d)" % (
             batch_length, batch_length - batch_mod))
         batch_length -= batch_mod
-    if batch_length is None and batch_size > 1:
+    padded = bool(pad_utterances) and batch_length is None and batch_size > 1
+    if batch_length is None and batch_size > 1 and not padded:
         logging.warning("in utterance batch mode, batchsize will be 1.")
     pre = bool(transforms_elementwise)
     n_workers = slicer_workers() if workers is None else max(0, int(workers))
@@ -229,6 +243,26 @@ def train_generator(wav_list, feat_list, receptive_field,
             ys.append(raw[1:])
         return _to_batch(xs, hs, ts, device, ys if with_wave else None)
 
+    def assemble_padded(window_jobs, all_lengths, lo):
+        """one minibatch of whole utterances (this rank's rows [lo, lo + len(window_jobs)) of it), padded to the longest row"""
+        xs, hs, ts, ys = [], [], [], []
+        for job in window_jobs:
+            x_, h_, raw = job.result()
+            hs.append(h_.transpose(0, 1) if use_upsampling_layer else h_[:-1].transpose(0, 1))
+            xs.append(x_[:-1])
+            ts.append(x_[1:])
+            ys.append(raw[1:])
+        lengths = torch.tensor([int(v.numel()) for v in xs], dtype=torch.int64)
+        assert lengths.tolist() == all_lengths[lo:lo + len(xs)]
+        T = int(lengths.max())
+        F = max(int(v.size(1)) for v in hs)
+        fill = int(n_quantize) // 2
+        xs = [torch.nn.functional.pad(v, (0, T - v.numel()), value=fill) for v in xs]
+        ts = [torch.nn.functional.pad(v, (0, T - v.numel()), value=fill) for v in ts]
+        ys = [torch.nn.functional.pad(v, (0, T - v.numel()), value=0.0) for v in ys]
+        hs = [torch.cat([v, v[:, -1:].expand(-1, F - v.size(1))], dim=1) if v.size(1) < F else v for v in hs]
+        return _to_batch(xs, hs, ts, device, ys if with_wave else None) + (lengths, torch.tensor(all_lengths, dtype=torch.int64))
+
     def utterances():
         """(x, h) of the utterances in list order, epoch after epoch, ``None`` between two epochs (the reference's generator starts
         every walk of the list with an empty minibatch, train.py:196-200); the list is reshuffled where the reference reshuffles
@@ -250,7 +284,8 @@ def train_generator(wav_list, feat_list, receptive_field,
 
     # window sharding only exists in the windowed modes; utterance batches (batch_length None, effective batch size 1)
     # are dealt round-robin by utterance below, so a batch_size below the world size is fine there
-    my_lo, my_hi = _shard_range(batch_size, shard) if batch_length is not None else (0, batch_size)
+    my_lo, my_hi = _shard_range(batch_size, shard) if (batch_length is not None or padded) else (0, batch_size)
+    group_lengths = []                  # padded utterance batches: valid positions of every row of the minibatch being filled
     ready = deque()                     # minibatch jobs in the order they will be yielded
     max_ready = 2 * n_workers + 1 if pool is not None else 1
     x_buffer = h_buffer = xt_buffer = ht_buffer = None
@@ -261,6 +296,7 @@ def train_generator(wav_list, feat_list, receptive_field,
         for utt in utterances():
             if utt is None:             # a new walk of the list: the reference drops a partly filled minibatch here (the buffers stay)
                 window_jobs = []
+                group_lengths = []
                 n_in_batch = 0
                 n_seen = 0
                 continue
@@ -310,7 +346,7 @@ def train_generator(wav_list, feat_list, receptive_field,
             else:
                 # one utterance per batch; with several ranks utterance i goes to rank i mod world
                 n_seen += 1
-                if shard is not None and (n_seen - 1) % shard[1] != shard[0]:
+                if not padded and shard is not None and (n_seen - 1) % shard[1] != shard[0]:
                     continue
                 if use_upsampling_layer:
                     h = h[:-1]
@@ -318,6 +354,20 @@ def train_generator(wav_list, feat_list, receptive_field,
                     if pre:
                         ht = ht[:-1]
                         xt = xt[:-upsampling_factor + 1]
+                if padded:
+                    # batch_size consecutive utterances per minibatch; rows of other ranks only contribute their length
+                    if my_lo <= n_in_batch < my_hi:
+                        window_jobs.append(submit(prep, x, h, xt, ht) if pre else submit(prep, x, h))
+                    group_lengths.append(len(x) - 1)
+                    n_in_batch += 1
+                    if n_in_batch == batch_size:
+                        ready.append(submit(assemble_padded, window_jobs, group_lengths, my_lo))
+                        window_jobs = []
+                        group_lengths = []
+                        n_in_batch = 0
+                        while len(ready) >= max_ready:
+                            yield ready.popleft().result()
+                    continue
                 ready.append(submit(assemble, [submit(prep, x, h, xt, ht) if pre else submit(prep, x, h)]))
                 while len(ready) >= max_ready:
                     yield ready.popleft().result()
@@ -380,6 +430,9 @@ def get_parser():
     parser.add_argument("--n_mixture", default=0, type=int, help="mixture-of-logistics components (0: softmax head)")
     parser.add_argument("--log_scale_min", default=-7.0, type=float,
                         help="mixture head: clamp of the log-scales (saved in model.conf, so decode.py samples with it)")
+    # extension (not a reference flag): whole utterances, --batch_size of them per minibatch, padded to the longest one
+    parser.add_argument("--utterance_batch", default=False, type=strtobool,
+                        help="train on padded minibatches of --batch_size whole utterances (--batch_length is ignored)")
     parser.add_argument("--resume", default=None, nargs="?", type=str, help="checkpoint to continue from")
     return parser
 
@@ -465,11 +518,14 @@ def _worker(rank, world, args, port):
         sys.exit(1)
     assert len(wav_list) == len(feat_list)
     logging.info("number of training data = %d." % len(wav_list))
+    utterance_batch = bool(getattr(args, "utterance_batch", False))
     generator = train_generator(
         wav_list, feat_list,
         receptive_field=model.receptive_field,
-        batch_length=args.batch_length,
+        batch_length=None if utterance_batch else args.batch_length,
         batch_size=args.batch_size,
+        pad_utterances=utterance_batch,
+        n_quantize=args.n_quantize,
         feature_type=args.feature_type,
         wav_transform=wav_transform,
         feat_transform=feat_transform,
@@ -506,8 +562,18 @@ def _worker(rank, world, args, port):
         # sum over ranks the mean over the whole minibatch -- what the reference's single CrossEntropyLoss over the
         # gathered logits computes (train.py:534-536) -- also when batch_size is not a multiple of the rank count.
         share = batch_x.size(0) / float(args.batch_size) if (world > 1 and args.batch_length is not None) else 1.0 / world
+        ragged = {}
+        if utterance_batch and args.batch_size > 1:
+            # padded whole utterances: the loss is the mean over the valid positions behind the receptive field.  This rank's
+            # share of the minibatch is N_local / N_global loss positions (every rank knows every length: no communication).
+            lengths, all_lengths = item[-2], item[-1]
+            rf = model.receptive_field
+            n_local = int((lengths - rf).clamp_(min=0).sum())
+            n_global = int((all_lengths - rf).clamp_(min=0).sum())
+            ragged["lengths"] = lengths
+            share = n_local / float(max(n_global, 1))
         batch_loss = reducer.loss_and_backward(batch_x, batch_h, batch_t, y=item[2] if args.n_mixture > 0 else None,
-                                               grad_scale=share)
+                                               grad_scale=share, **ragged)
         optimizer.step()
         loss_acc += batch_loss.detach() * (share * world)
         if args.verbose > 1:
@@ -542,7 +608,7 @@ def main(argv=None):
     args = get_parser().parse_args(argv)
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     n_ranks = world_env if world_env > 1 else args.n_gpus
-    if n_ranks > 1 and args.batch_length is not None and args.batch_size < n_ranks:
+    if n_ranks > 1 and (args.batch_length is not None or args.utterance_batch) and args.batch_size < n_ranks:
         # every rank must own at least one window of each minibatch (the reference scatters the same way)
         logging.error("--batch_size (%d) must be >= the number of GPUs (%d)." % (args.batch_size, n_ranks))
         sys.exit(1)

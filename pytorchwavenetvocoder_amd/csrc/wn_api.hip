@@ -756,6 +756,8 @@ static bool fw_gemm_split_ok(const Ctx& c, const WnGemmArgs& g) {
 struct CeEpi {   // softmax cross-entropy as the epilogue of the contraction that produces the logits (wn_gemm6.h)
     const int64_t* target;
     int t_start;
+    const int32_t* t_end;   // nullable, device, B entries: sequence b carries loss on [t_start, t_end[b]) (ragged batch)
+    int t_origin;           // position of column 0 of the launch; t_end holds positions of the caller's (B, T) tensor
     float gs;
     float* partial;
     float* amax;
@@ -796,6 +798,7 @@ static int fw_gemm(const Ctx& c, const WnGemmArgs& g, const GateEpi* ge = nullpt
     a.n_phase = (n_origin / WN_G6_BN) & 1;
     if (ce) {
         a.ce_target = reinterpret_cast<const long long*>(ce->target); a.ce_tstride = g.ldc; a.ce_t_start = ce->t_start;
+        a.ce_t_end = ce->t_end; a.ce_t_origin = ce->t_origin;
         a.ce_gs = ce->gs; a.ce_partial = ce->partial; a.ce_amax = ce->amax;
     }
     // WN_FLAG_MM_F16PAIR: the fp16 pair split with the conditional six-product redo behind it -- for the weight sets pack_weights
@@ -1098,6 +1101,7 @@ static int forward_impl(const WnConfig* cfg, int B, int T, const float* params, 
             CeEpi ce = *ce_in;
             ce.target = ce_in->target + t0;     // column j of the window is position t0 + j (row stride T)
             ce.t_start = ce_in->t_start - t0;
+            ce.t_origin = t0;                   // t_end stays the caller's array of positions: the kernel subtracts the origin
             ce.partial = ws + w.loss_partial;
             ce.amax = ws + w.amax_partial;
             g.tag = "fwd_post2_ce";
@@ -1129,68 +1133,107 @@ extern "C" int wn_forward_loss_fused(const WnConfig* cfg, int B, int T, int flag
             wn_gemm6_apk_elems(d.Qo, d.S) <= 2 * w.apk_floats && (long)d.Qo * T * 4 < 0x7ffffff0L) ? 1 : 0;
 }
 
-extern "C" int wn_forward_loss(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
-                               const int64_t* target, int t_start, float grad_scale, float loss_scale, float* loss,
-                               float* dlogits, float* logits_scratch, void* wsp, size_t ws_bytes, int flags, void* stream) {
+// Divisor of the mean and the argument checks shared by the three ragged loss entry points.  Dense (t_end == NULL): the
+// rectangle B * (T - t_start), formed as the dense entry points always formed it.  Ragged: the caller's n_loss.
+static int loss_count(int B, int T, int t_start, const int32_t* t_end, int64_t n_loss, float* count) {
+    if (t_start < 0 || t_start >= T) return fail(1, "t_start=%d outside [0,%d)", t_start, T);
+    if (n_loss <= 0) return fail(1, "n_loss=%lld: no position carries loss", (long long)n_loss);
+    if (!t_end && n_loss != (int64_t)B * (int64_t)(T - t_start))
+        return fail(1, "n_loss=%lld with t_end == NULL: the dense loss covers B * (T - t_start) = %lld positions", (long long)n_loss,
+                    (long long)B * (long long)(T - t_start));
+    if (n_loss > (int64_t)B * (int64_t)(T - t_start))
+        return fail(1, "n_loss=%lld exceeds B * (T - t_start) = %lld", (long long)n_loss, (long long)B * (long long)(T - t_start));
+    *count = t_end ? (float)n_loss : (float)B * (float)(T - t_start);
+    return 0;
+}
+
+extern "C" int wn_forward_loss_ragged(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                                      const int64_t* target, int t_start, const int32_t* t_end, int64_t n_loss, float grad_scale,
+                                      float loss_scale, float* loss, float* dlogits, float* logits_scratch, void* wsp,
+                                      size_t ws_bytes, int flags, void* stream) {
     api_enter();
     if (!target || !loss) return fail(1, "NULL argument");
-    if (t_start < 0 || t_start >= T) return fail(1, "t_start=%d outside [0,%d)", t_start, T);
+    float count = 0.f;
+    WN_TRY(loss_count(B, T, t_start, t_end, n_loss, &count));
     if (!wn_forward_loss_fused(cfg, B, T, flags)) {
         if (!logits_scratch) return fail(1, "this model / flag set needs the logits scratch buffer (wn_forward_loss_fused() == 0)");
         WN_TRY(forward_impl(cfg, B, T, params, x, h, logits_scratch, nullptr, wsp, ws_bytes, flags, stream, "wn_forward_loss"));
-        return wn_softmax_ce_loss(cfg, B, T, logits_scratch, target, t_start, grad_scale, loss_scale, loss, dlogits, wsp, ws_bytes,
-                                  stream);
+        return wn_softmax_ce_loss_ragged(cfg, B, T, logits_scratch, target, t_start, t_end, n_loss, grad_scale, loss_scale, loss,
+                                         dlogits, wsp, ws_bytes, stream);
     }
     CeEpi ce;
-    ce.target = target; ce.t_start = t_start; ce.gs = grad_scale / ((float)B * (float)(T - t_start)); ce.partial = nullptr; ce.amax = nullptr;
+    ce.target = target; ce.t_start = t_start; ce.t_end = t_end; ce.t_origin = 0; ce.gs = grad_scale / count; ce.partial = nullptr; ce.amax = nullptr;
     WN_TRY(forward_impl(cfg, B, T, params, x, h, dlogits, &ce, wsp, ws_bytes, flags, stream, "wn_forward_loss"));
     Ctx c;
     WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, flags, stream));
     const int t0w = (t_start / 128) * 128;   // the column window forward_impl ran the loss epilogue over
     const int np = ((T - t0w + WN_G6_BN - 1) / WN_G6_BN) * B;
-    WN_TRY(wn_sum_partials(c.ws + c.w.loss_partial, np, loss_scale / ((float)B * (float)(T - t_start)), loss,
+    WN_TRY(wn_sum_partials(c.ws + c.w.loss_partial, np, loss_scale / count, loss,
                            dlogits ? c.ws + c.w.amax_partial : nullptr, c.ws + c.w.dw_ovf + 2, c.st));   // + max |dlogits| (WN_FLAG_DW_F16_AMAX_WS)
     return rt_check("wn_forward_loss");
+}
+
+extern "C" int wn_forward_loss(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                               const int64_t* target, int t_start, float grad_scale, float loss_scale, float* loss,
+                               float* dlogits, float* logits_scratch, void* wsp, size_t ws_bytes, int flags, void* stream) {
+    return wn_forward_loss_ragged(cfg, B, T, params, x, h, target, t_start, nullptr, (int64_t)B * (int64_t)(T - t_start), grad_scale,
+                                  loss_scale, loss, dlogits, logits_scratch, wsp, ws_bytes, flags, stream);
 }
 
 // ------------------------------------------------------------------------------------------
 // loss
 // ------------------------------------------------------------------------------------------
-extern "C" int wn_softmax_ce_loss(const WnConfig* cfg, int B, int T, const float* logits, const int64_t* target, int t_start,
-                                  float grad_scale, float loss_scale, float* loss, float* dlogits, void* wsp, size_t ws_bytes,
-                                  void* stream) {
+extern "C" int wn_softmax_ce_loss_ragged(const WnConfig* cfg, int B, int T, const float* logits, const int64_t* target,
+                                         int t_start, const int32_t* t_end, int64_t n_loss, float grad_scale, float loss_scale,
+                                         float* loss, float* dlogits, void* wsp, size_t ws_bytes, void* stream) {
     api_enter();
     Ctx c;
     WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, 0, stream));
     if (!logits || !target || !loss) return fail(1, "NULL argument");
-    if (t_start < 0 || t_start >= T) return fail(1, "t_start=%d outside [0,%d)", t_start, T);
+    float count = 0.f;
+    WN_TRY(loss_count(B, T, t_start, t_end, n_loss, &count));
     int np = 0;
-    const float gs = grad_scale / ((float)B * (float)(T - t_start));
+    const float gs = grad_scale / count;
     WN_TRY(wn_softmax_ce(logits, target, dlogits, c.ws + c.w.loss_partial, &np, B, T, c.d.Qo, t_start, gs,
-                         dlogits ? c.ws + c.w.amax_partial : nullptr, c.st));
-    WN_TRY(wn_sum_partials(c.ws + c.w.loss_partial, np, loss_scale / ((float)B * (float)(T - t_start)), loss,
+                         dlogits ? c.ws + c.w.amax_partial : nullptr, t_end, c.st));
+    WN_TRY(wn_sum_partials(c.ws + c.w.loss_partial, np, loss_scale / count, loss,
                            dlogits ? c.ws + c.w.amax_partial : nullptr, c.ws + c.w.dw_ovf + 2, c.st));   // + max |dlogits| (WN_FLAG_DW_F16_AMAX_WS)
     return rt_check("wn_softmax_ce_loss");
+}
+
+extern "C" int wn_softmax_ce_loss(const WnConfig* cfg, int B, int T, const float* logits, const int64_t* target, int t_start,
+                                  float grad_scale, float loss_scale, float* loss, float* dlogits, void* wsp, size_t ws_bytes,
+                                  void* stream) {
+    return wn_softmax_ce_loss_ragged(cfg, B, T, logits, target, t_start, nullptr, (int64_t)B * (int64_t)(T - t_start), grad_scale,
+                                     loss_scale, loss, dlogits, wsp, ws_bytes, stream);
 }
 
 // Mixture-of-logistics head (BASELINE configs[3]; absent from the reference): mean negative log-likelihood of
 // the target waveform y (B,T) in [-1,1] under the 3*n_mix output channels, over positions t >= t_start,
 // and its gradient in the layout wn_backward takes.
-extern "C" int wn_mol_loss(const WnConfig* cfg, int B, int T, const float* out, const float* y, int t_start, float grad_scale,
-                           float loss_scale, int num_classes, float log_scale_min, float* loss, float* dout, void* wsp,
-                           size_t ws_bytes, void* stream) {
+extern "C" int wn_mol_loss_ragged(const WnConfig* cfg, int B, int T, const float* out, const float* y, int t_start,
+                                  const int32_t* t_end, int64_t n_loss, float grad_scale, float loss_scale, int num_classes,
+                                  float log_scale_min, float* loss, float* dout, void* wsp, size_t ws_bytes, void* stream) {
     api_enter();
     Ctx c;
     WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, 0, stream));
     if (!out || !y || !loss) return fail(1, "NULL argument");
     if (c.d.Qo % 3 != 0) return fail(1, "out_channels=%d is not 3 * n_mixture", c.d.Qo);
-    if (t_start < 0 || t_start >= T) return fail(1, "t_start=%d outside [0,%d)", t_start, T);
+    float count = 0.f;
+    WN_TRY(loss_count(B, T, t_start, t_end, n_loss, &count));
     int np = 0;
-    const float gs = grad_scale / ((float)B * (float)(T - t_start));
-    WN_TRY(wn_mol_nll(out, y, dout, c.ws + c.w.loss_partial, &np, B, T, c.d.Qo / 3, t_start, gs, num_classes, log_scale_min, c.st));
+    const float gs = grad_scale / count;
+    WN_TRY(wn_mol_nll(out, y, dout, c.ws + c.w.loss_partial, &np, B, T, c.d.Qo / 3, t_start, gs, num_classes, log_scale_min, t_end, c.st));
     // (no measured maximum for this head: a backward call with WN_FLAG_DW_F16PAIR scans the gradient it is given)
-    WN_TRY(wn_sum_partials(c.ws + c.w.loss_partial, np, loss_scale / ((float)B * (float)(T - t_start)), loss, nullptr, c.ws + c.w.dw_ovf + 2, c.st));
+    WN_TRY(wn_sum_partials(c.ws + c.w.loss_partial, np, loss_scale / count, loss, nullptr, c.ws + c.w.dw_ovf + 2, c.st));
     return rt_check("wn_mol_loss");
+}
+
+extern "C" int wn_mol_loss(const WnConfig* cfg, int B, int T, const float* out, const float* y, int t_start, float grad_scale,
+                           float loss_scale, int num_classes, float log_scale_min, float* loss, float* dout, void* wsp,
+                           size_t ws_bytes, void* stream) {
+    return wn_mol_loss_ragged(cfg, B, T, out, y, t_start, nullptr, (int64_t)B * (int64_t)(T - t_start), grad_scale, loss_scale,
+                              num_classes, log_scale_min, loss, dout, wsp, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------

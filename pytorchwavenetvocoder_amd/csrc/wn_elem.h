@@ -23,11 +23,13 @@ int wn_gate_bwd(const float* dZ, const float* S, const float* Gt, float* dP, int
 //   loss = mean_{b,t>=t_start} ( logsumexp_q - logit[target] );  dlogits = (softmax - onehot) * grad_scale
 // (zero for t < t_start).  loss_partial has one float per launched block; wn_loss_finalize sums
 // them in a fixed order and multiplies by loss_scale.
+// t_end (nullable, device, B int32): sequence b carries loss on [t_start, t_end[b]) only (a padded batch of unequal lengths);
+// dlogits is exactly 0 and the partials take nothing from t >= t_end[b].  NULL = T for every sequence.
 // amax_partial (nullable): one float per launched block = the block's max |dlogits| (for the measured scale of the fp16 pair
 // split of the weight gradients, WN_FLAG_DW_F16PAIR).
 int wn_softmax_ce(const float* logits, const int64_t* target, float* dlogits /*nullable*/,
                   float* loss_partial, int* n_partial /*out: host*/, int B, int T, int Q, int t_start,
-                  float grad_scale, float* amax_partial, wn_stream_t st);
+                  float grad_scale, float* amax_partial, const int* t_end, wn_stream_t st);
 // out[0] = scale * sum(partial[0..n)); amax_out (nullable): amax_out[0] = max(amax_partial[0..n)) (0 without amax_partial)
 int wn_sum_partials(const float* partial, int n, float scale, float* out /*device scalar*/, const float* amax_partial,
                     float* amax_out, wn_stream_t st);
@@ -195,9 +197,9 @@ int wn_dl_sum(const float* part, int nz, long zstride, int M, int nb, const floa
 // out (B, 3*nm, T): rows [0,nm) mixture logits, [nm,2nm) means, [2nm,3nm) log-scales (clamped at log_scale_min);
 // y (B, T) target waveform in [-1, 1]; num_classes = quantisation levels of the waveform (65536 for 16 bit).
 // loss_partial gets one partial sum of the negative log-likelihood per block over t >= t_start; dout (nullable)
-// gets d(sum nll * grad_scale)/d(out), zero for t < t_start.
+// gets d(sum nll * grad_scale)/d(out), zero for t < t_start.  t_end as wn_softmax_ce.
 int wn_mol_nll(const float* out, const float* y, float* dout, float* loss_partial, int* n_partial, int B, int T, int nm,
-               int t_start, float grad_scale, int num_classes, float log_scale_min, wn_stream_t st);
+               int t_start, float grad_scale, int num_classes, float log_scale_min, const int* t_end, wn_stream_t st);
 // Decode-side draw of the MoL head for every utterance from out [3*nm][nb]: component by Gumbel max with the
 // uniforms u[0..nm), value = mean + scale*(log u_nm - log(1-u_nm)) clipped to [-1,1]; the value is mu-law
 // encoded (levels Q) into the token fed back to the one-hot front end; wave_out (nb, Ttot) keeps the float.

@@ -212,13 +212,15 @@ int wn_gate_bwd(const float* dZ, const float* S, const float* Gt, float* dP, int
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WN_TPB) void k_softmax_ce(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                        float* __restrict__ dlogits, float* __restrict__ loss_partial, int T,
-                                                       int Q, int t_start, float grad_scale, float* __restrict__ amax_partial) {
+                                                       int Q, int t_start, float grad_scale, float* __restrict__ amax_partial,
+                                                       const int* __restrict__ t_end) {
     __shared__ float red[4];
     float my_amax = 0.0f;
     const int t = blockIdx.x * WN_TPB + threadIdx.x;
     const int b = blockIdx.y;
     float my_loss = 0.0f;
-    const bool live = (t < T) && (t >= t_start);
+    const int te = (t_end && t_end[b] < T) ? t_end[b] : T;   // ragged batch: the sequence's own end (block-uniform)
+    const bool live = (t < te) && (t >= t_start);
     const float* lg = logits + (long)b * Q * T + t;
     if (live) {
         // online softmax in chunks of 8 channels: the 8 strided loads of a chunk are independent and in
@@ -274,11 +276,12 @@ __global__ __launch_bounds__(WN_TPB) void k_softmax_ce(const float* __restrict__
 int wn_softmax_ce_nblocks(int B, int T) { return ((T + WN_TPB - 1) / WN_TPB) * B; }
 
 int wn_softmax_ce(const float* logits, const int64_t* target, float* dlogits, float* loss_partial, int* n_partial, int B,
-                  int T, int Q, int t_start, float grad_scale, float* amax_partial, wn_stream_t st) {
+                  int T, int Q, int t_start, float grad_scale, float* amax_partial, const int* t_end, wn_stream_t st) {
     WN_PROF("softmax_ce", 0.0, 0.0, st);
     dim3 grid((T + WN_TPB - 1) / WN_TPB, B);
     if (n_partial) *n_partial = (int)(grid.x * grid.y);
-    WN_LAUNCH(k_softmax_ce, grid, dim3(WN_TPB), 0, st, logits, target, dlogits, loss_partial, T, Q, t_start, grad_scale, amax_partial);
+    WN_LAUNCH(k_softmax_ce, grid, dim3(WN_TPB), 0, st, logits, target, dlogits, loss_partial, T, Q, t_start, grad_scale, amax_partial,
+              t_end);
     return 0;
 }
 
@@ -1423,12 +1426,13 @@ static __device__ __forceinline__ float mol_component(float y, float mean, float
 __global__ __launch_bounds__(WN_TPB) void k_mol_nll(const float* __restrict__ out, const float* __restrict__ yv,
                                                     float* __restrict__ dout, float* __restrict__ loss_partial, int T, int nm,
                                                     int t_start, float grad_scale, float half_bin, float log_half_classes,
-                                                    float log_scale_min) {
+                                                    float log_scale_min, const int* __restrict__ t_end) {
     __shared__ float red[4];
     const int t = blockIdx.x * WN_TPB + threadIdx.x;
     const int b = blockIdx.y;
     float my = 0.0f;
-    const bool live = (t < T) && (t >= t_start);
+    const int te = (t_end && t_end[b] < T) ? t_end[b] : T;   // ragged batch: the sequence's own end (block-uniform)
+    const bool live = (t < te) && (t >= t_start);
     const float* o = out + (long)b * 3 * nm * T + t;
     float* d = dout ? dout + (long)b * 3 * nm * T + t : nullptr;
     if (live) {
@@ -1478,13 +1482,13 @@ __global__ __launch_bounds__(WN_TPB) void k_mol_nll(const float* __restrict__ ou
 }
 
 int wn_mol_nll(const float* out, const float* y, float* dout, float* loss_partial, int* n_partial, int B, int T, int nm,
-               int t_start, float grad_scale, int num_classes, float log_scale_min, wn_stream_t st) {
+               int t_start, float grad_scale, int num_classes, float log_scale_min, const int* t_end, wn_stream_t st) {
     WN_PROF("mol_nll", 0.0, 0.0, st);
     if (nm < 1 || num_classes < 2) return 1;
     dim3 grid((T + WN_TPB - 1) / WN_TPB, B);
     if (n_partial) *n_partial = (int)(grid.x * grid.y);
     WN_LAUNCH(k_mol_nll, grid, dim3(WN_TPB), 0, st, out, y, dout, loss_partial, T, nm, t_start, grad_scale,
-              1.0f / (float)(num_classes - 1), logf((float)(num_classes - 1) * 0.5f), log_scale_min);
+              1.0f / (float)(num_classes - 1), logf((float)(num_classes - 1) * 0.5f), log_scale_min, t_end);
     return 0;
 }
 

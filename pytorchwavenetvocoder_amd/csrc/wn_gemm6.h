@@ -60,9 +60,14 @@ typedef struct WnGemm6Args {
     //   logit = acc + bias never goes to memory; C (nullable) receives d(mean loss)/d(logit) * ce_gs = (softmax - onehot) * ce_gs
     //   for columns >= ce_t_start and 0 in front of them; ce_partial[z * gridDim.x + x] = sum over the block's columns
     //   >= ce_t_start of (logsumexp - logit[target]).  target[z * ce_tstride + column] is taken modulo M.
+    //   ce_t_end (nullable, device, nbatch int32): batch z carries loss on the columns [ce_t_start, ce_t_end[z] - ce_t_origin)
+    //   only -- C is exactly 0, and ce_partial / ce_amax take nothing, from the others.  The array holds positions of the
+    //   caller's full tensor (it is the caller's own device array); ce_t_origin = the position of column 0 of this launch.
     const long long* ce_target;
     long ce_tstride;
     int ce_t_start;
+    const int* ce_t_end;
+    int ce_t_origin;
     float ce_gs;
     float* ce_partial;
     float* ce_amax;             // nullable, indexed like ce_partial: the block's max |d(mean loss)/d(logit) * ce_gs|
@@ -78,7 +83,7 @@ typedef struct WnGemm6Args {
 static inline void wn_gemm6_no_gate(WnGemm6Args* a) {
     a->gate_R = 0; a->gate_S = 0; a->gate_Gt = 0; a->gate_Z = 0; a->gate_G = 0; a->gate_gb = 0; a->gate_F = 0; a->gate_U = 1;
     a->gate_upw = 0; a->gate_cvec = 0; a->gbw_S = 0; a->gbw_Gt = 0; a->gbw_dP = 0; a->no_interior = 0; a->stagger = 0; a->n_phase = 0;
-    a->ce_target = 0; a->ce_tstride = 0; a->ce_t_start = 0; a->ce_gs = 0.f; a->ce_partial = 0; a->ce_amax = 0;
+    a->ce_target = 0; a->ce_tstride = 0; a->ce_t_start = 0; a->ce_t_end = 0; a->ce_t_origin = 0; a->ce_gs = 0.f; a->ce_partial = 0; a->ce_amax = 0;
     a->f16 = 0; a->b_mul = 0.f; a->ovf = 0;
 }
 

@@ -556,11 +556,13 @@ __global__ __launch_bounds__(G6_T, 2) void k_gemm6(WnGemm6Args g, int order G6_D
         float mx[2], sm[2], vt[2];
         int tq[2];
         bool okc[2], live[2];
+        // ragged batch: the sequence's own end, one scalar load per block (b = blk.z is uniform); no array = every column to N
+        const int ce_te = g.ce_t_end ? g.ce_t_end[b] - g.ce_t_origin : 0x7fffffff;
         WN_UNROLL
         for (int j = 0; j < 2; ++j) {
             const int col = n0 + 64 * wn + 32 * j + li;
             okc[j] = col < g.N;
-            live[j] = okc[j] && col >= g.ce_t_start;
+            live[j] = okc[j] && col >= g.ce_t_start && col < ce_te;
             // class index modulo M like k_softmax_ce; the 64-bit division only runs for a target outside [0, M)
             long long tg = okc[j] ? g.ce_target[(long)b * g.ce_tstride + col] : 0;
             if ((unsigned long long)tg >= (unsigned long long)g.M) {

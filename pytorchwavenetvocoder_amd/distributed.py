@@ -77,23 +77,28 @@ class GradientReducer(object):
             return self.model.mol_loss_and_backward(x, h, y, **kw)
         return self.model.loss_and_backward(x, h, t, **kw)
 
-    def loss_and_backward(self, x, h, t, t_start=None, y=None, grad_scale=None):
+    def loss_and_backward(self, x, h, t, t_start=None, y=None, grad_scale=None, lengths=None):
         """forward + loss + backward with the bucketed all-reduce overlapped; returns the local
         mean loss (device tensor).  ``y`` (B, T) float selects the mixture-of-logistics loss.
         ``grad_scale``: this rank's share of the global minibatch (default 1/world = equal shards; pass
-        B_local / B_global when the shards are uneven, so that the summed gradient is the global-batch mean)."""
+        B_local / B_global when the shards are uneven, so that the summed gradient is the global-batch mean).
+        ``lengths``: this rank's padded shard of sequences of unequal length (``WaveNet.loss_and_backward``).  The local loss
+        is then the mean over the rank's own N_local = sum_b max(lengths[b] - t_start, 0) loss positions, so the right share
+        is ``grad_scale = N_local / N_global`` (N_global: the same count over every rank's shard): the summed gradient is the
+        gradient of the mean over all N_global positions.  Ranks may run different T."""
+        kw = {} if lengths is None else {"lengths": lengths}
         if self.world == 1 and not self.exchange_alone:   # same launch structure as N > 1 (weight gradients flushed per bucket), no exchange
-            return self._step(x, h, t, y, t_start=t_start, layers_per_bucket=self.lpb)
+            return self._step(x, h, t, y, t_start=t_start, layers_per_bucket=self.lpb, **kw)
         gscale = self.grad_scale if grad_scale is None else float(grad_scale)
         if not self.cuda:
-            loss = self._step(x, h, t, y, t_start=t_start, grad_scale=gscale)
+            loss = self._step(x, h, t, y, t_start=t_start, grad_scale=gscale, **kw)
             flat = self.eng.grads()
             for lo, hi in self.ranges:
                 dist.all_reduce(flat[lo:hi], group=self.group)
             return loss
         handles = [e.cuda_event for e in self.events]
         loss = self._step(x, h, t, y, t_start=t_start, grad_scale=gscale, events=handles,
-                          layers_per_bucket=self.lpb)
+                          layers_per_bucket=self.lpb, **kw)
         flat = self.eng.grads()
         main = torch.cuda.current_stream(self.eng.device)
         pair = None

@@ -87,6 +87,8 @@ class WaveNetEngine(object):
         self.flat_grads = None
         self._ws = None
         self._ws_key = None
+        self._lengths_key = None  # (lengths, device) of the int32 array _lengths_arg uploaded last
+        self._lengths_dev = None
         self._last_shape = None
         self._fwd_window = 0      # first loss position of the last forward_loss (0: a full forward)
         self._fwd_version = None  # parameter version the last forward packed its weight sets from
@@ -210,11 +212,16 @@ class WaveNetEngine(object):
         self._fwd_flags = self.flags
         return logits
 
-    def forward_loss(self, x, h, target, t_start=None, grad_scale=1.0, loss_scale=1.0, want_grad=True):
+    def forward_loss(self, x, h, target, t_start=None, grad_scale=1.0, loss_scale=1.0, want_grad=True, lengths=None):
         """``forward`` + ``loss`` of a training step in one call (reference train.py:533-536).  Softmax head with at most
         256 classes on the split contractions: the cross-entropy is the EPILOGUE of the conv_post_2 contraction, the
         (B, Q, T) logits never reach memory (``wn_forward_loss``); otherwise the two calls back to back.
-        Returns (loss, dlogits) exactly as ``loss`` does."""
+        Returns (loss, dlogits) exactly as ``loss`` does.
+
+        ``lengths`` (B host integers, see ``_lengths_arg``): a padded batch of sequences of unequal length -- the loss is the
+        mean over the positions [t_start, lengths[b]) of every sequence, nn.CrossEntropyLoss() with the targets behind each
+        end set to -100; ``dlogits`` is exactly zero on the padding, whatever finite values x, h and target hold there.  The
+        fused form is kept (``wn_forward_loss_ragged``).  None: every sequence runs to T, the dense call."""
         self._check_device(x, h, target)
         if x.dtype != torch.int64 or x.dim() != 2:
             raise ValueError("x must be a LongTensor (B, T)")
@@ -233,11 +240,20 @@ class WaveNetEngine(object):
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         dlogits = torch.empty((B, self.out_channels, T), dtype=torch.float32, device=self.device) if want_grad else None
         scratch = None if fused else torch.empty((B, self.out_channels, T), dtype=torch.float32, device=self.device)
-        rc = self.lib.wn_forward_loss(cfg, B, T, _ptr(self.flat_params), _ptr(x), _ptr(h), _ptr(target), int(t_start),
-                                      float(grad_scale), float(loss_scale), _ptr(loss), _ptr(dlogits), _ptr(scratch),
-                                      _ptr(ws), ws.numel() * 4, self.flags | (_lib.FLAG_WS_FINITE if self.ws_finite else 0),
-                                      _stream_handle(self.device))
-        self.lib.check(rc, "wn_forward_loss")
+        call_flags = self.flags | (_lib.FLAG_WS_FINITE if self.ws_finite else 0)
+        count = B * (T - int(t_start))
+        if lengths is None:
+            rc = self.lib.wn_forward_loss(cfg, B, T, _ptr(self.flat_params), _ptr(x), _ptr(h), _ptr(target), int(t_start),
+                                          float(grad_scale), float(loss_scale), _ptr(loss), _ptr(dlogits), _ptr(scratch),
+                                          _ptr(ws), ws.numel() * 4, call_flags, _stream_handle(self.device))
+            self.lib.check(rc, "wn_forward_loss")
+        else:
+            t_end, count = self._lengths_arg(lengths, B, T, t_start)
+            rc = self.lib.wn_forward_loss_ragged(cfg, B, T, _ptr(self.flat_params), _ptr(x), _ptr(h), _ptr(target),
+                                                 int(t_start), _ptr(t_end), count, float(grad_scale), float(loss_scale),
+                                                 _ptr(loss), _ptr(dlogits), _ptr(scratch), _ptr(ws), ws.numel() * 4,
+                                                 call_flags, _stream_handle(self.device))
+            self.lib.check(rc, "wn_forward_loss_ragged")
         self._last_shape = (B, T)
         self._last_inputs = (x, h)
         # the fused form ran the skip sum / post-net over the loss window only (saved(WS_RELU_*) is valid from
@@ -245,8 +261,45 @@ class WaveNetEngine(object):
         self._fwd_window = int(t_start) if fused else 0
         self._fwd_version = self.params_version()
         self._fwd_flags = self.flags
-        self._note_bound(dlogits, grad_scale, B * (T - int(t_start)))
+        self._note_bound(dlogits, grad_scale, count)
         return loss, dlogits
+
+    def _lengths_arg(self, lengths, B, T, t_start):
+        """``lengths`` of a padded batch -> (device int32 array for the ragged C entry points, N).  ``lengths[b]`` is the number of
+        valid positions of sequence b, 1 <= lengths[b] <= T; the loss positions of b are [t_start, lengths[b]) and
+        N = sum_b max(lengths[b] - t_start, 0) is their count -- known here, on the host, because the lengths are host
+        integers (a sequence of ints or a CPU integer tensor): the step gains no device-to-host synchronisation."""
+        if isinstance(lengths, torch.Tensor):
+            if lengths.device.type != "cpu":
+                raise ValueError("lengths must be host integers (a sequence of ints or a CPU integer tensor), got a tensor on "
+                                 "%s: the loss divisor N is computed on the host" % lengths.device)
+            if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+                raise ValueError("lengths must be integers, got %s" % lengths.dtype)
+            lens = [int(v) for v in lengths.reshape(-1).tolist()] if lengths.dim() == 1 else None
+        else:
+            try:
+                lens = list(lengths)
+            except TypeError:
+                lens = None
+            if lens is not None:
+                for v in lens:
+                    if isinstance(v, bool) or int(v) != v:
+                        raise ValueError("lengths must be integers, got %r" % (v,))
+                lens = [int(v) for v in lens]
+        if lens is None or len(lens) != B:
+            raise ValueError("lengths must have one entry per sequence (B = %d), got %s"
+                             % (B, "%d" % len(lens) if lens is not None else "shape %s" % (tuple(getattr(lengths, "shape", ())),)))
+        for b, v in enumerate(lens):
+            if v < 1 or v > T:
+                raise ValueError("lengths[%d] = %d outside [1, T = %d]" % (b, v, T))
+        n = sum(max(v - int(t_start), 0) for v in lens)
+        if n == 0:
+            raise ValueError("lengths %s leave no loss position behind t_start = %d (N == 0)" % (lens, int(t_start)))
+        key = (tuple(lens), str(self.device))
+        if self._lengths_key != key:   # an upload of B integers, not a launch; the same lengths step after step upload once
+            self._lengths_dev = torch.tensor(lens, dtype=torch.int32).to(self.device, non_blocking=True)
+            self._lengths_key = key
+        return self._lengths_dev, n
 
     def _note_bound(self, dlogits, grad_scale, count):
         # The loss calls leave max |dlogits| of the tensor they wrote in the workspace (measured in their epilogue); backward() may
@@ -274,8 +327,9 @@ class WaveNetEngine(object):
             return flags | _lib.FLAG_DW_F16_AMAX_WS
         return flags
 
-    def loss(self, logits, target, t_start=None, grad_scale=1.0, loss_scale=1.0, want_grad=True):
-        """Softmax-CE over positions >= t_start (default: receptive field).  Returns (loss, dlogits)."""
+    def loss(self, logits, target, t_start=None, grad_scale=1.0, loss_scale=1.0, want_grad=True, lengths=None):
+        """Softmax-CE over positions >= t_start (default: receptive field).  Returns (loss, dlogits).  ``lengths``: as
+        ``forward_loss`` (positions [t_start, lengths[b]) of every sequence; ``dlogits`` exactly zero elsewhere)."""
         self._check_device(logits, target)
         B, Q, T = logits.shape
         if t_start is None:
@@ -284,17 +338,26 @@ class WaveNetEngine(object):
         ws = self.workspace(B, T)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         dlogits = torch.empty_like(logits) if want_grad else None
-        rc = self.lib.wn_softmax_ce_loss(ctypes.byref(self.cfg), B, T, _ptr(logits), _ptr(target), int(t_start),
-                                         float(grad_scale), float(loss_scale), _ptr(loss), _ptr(dlogits), _ptr(ws),
-                                         ws.numel() * 4, _stream_handle(self.device))
-        self.lib.check(rc, "wn_softmax_ce_loss")
-        self._note_bound(dlogits, grad_scale, B * (T - int(t_start)))
+        count = B * (T - int(t_start))
+        if lengths is None:
+            rc = self.lib.wn_softmax_ce_loss(ctypes.byref(self.cfg), B, T, _ptr(logits), _ptr(target), int(t_start),
+                                             float(grad_scale), float(loss_scale), _ptr(loss), _ptr(dlogits), _ptr(ws),
+                                             ws.numel() * 4, _stream_handle(self.device))
+            self.lib.check(rc, "wn_softmax_ce_loss")
+        else:
+            t_end, count = self._lengths_arg(lengths, B, T, t_start)
+            rc = self.lib.wn_softmax_ce_loss_ragged(ctypes.byref(self.cfg), B, T, _ptr(logits), _ptr(target), int(t_start),
+                                                    _ptr(t_end), count, float(grad_scale), float(loss_scale), _ptr(loss),
+                                                    _ptr(dlogits), _ptr(ws), ws.numel() * 4, _stream_handle(self.device))
+            self.lib.check(rc, "wn_softmax_ce_loss_ragged")
+        self._note_bound(dlogits, grad_scale, count)
         return loss, dlogits
 
     def mol_loss(self, out, y, t_start=None, grad_scale=1.0, loss_scale=1.0, want_grad=True, num_classes=65536,
-                 log_scale_min=-7.0):
+                 log_scale_min=-7.0, lengths=None):
         """Mixture-of-logistics head: mean NLL of the waveform ``y`` (B,T) in [-1,1] under ``out`` (B, 3*n_mix, T)
-        over positions >= t_start, and d(loss)/d(out) for ``backward``.  Not in the reference (see include/)."""
+        over positions >= t_start, and d(loss)/d(out) for ``backward``.  Not in the reference (see include/).
+        ``lengths``: the same mask and the same divisor as ``forward_loss`` gives the softmax head."""
         self._check_device(out, y)
         B, C, T = out.shape
         if C != self.out_channels or C % 3 != 0:
@@ -305,10 +368,17 @@ class WaveNetEngine(object):
         ws = self.workspace(B, T)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         dout = torch.empty_like(out) if want_grad else None
-        rc = self.lib.wn_mol_loss(ctypes.byref(self.cfg), B, T, _ptr(out), _ptr(y), int(t_start), float(grad_scale),
-                                  float(loss_scale), int(num_classes), float(log_scale_min), _ptr(loss), _ptr(dout),
-                                  _ptr(ws), ws.numel() * 4, _stream_handle(self.device))
-        self.lib.check(rc, "wn_mol_loss")
+        if lengths is None:
+            rc = self.lib.wn_mol_loss(ctypes.byref(self.cfg), B, T, _ptr(out), _ptr(y), int(t_start), float(grad_scale),
+                                      float(loss_scale), int(num_classes), float(log_scale_min), _ptr(loss), _ptr(dout),
+                                      _ptr(ws), ws.numel() * 4, _stream_handle(self.device))
+            self.lib.check(rc, "wn_mol_loss")
+        else:
+            t_end, count = self._lengths_arg(lengths, B, T, t_start)
+            rc = self.lib.wn_mol_loss_ragged(ctypes.byref(self.cfg), B, T, _ptr(out), _ptr(y), int(t_start), _ptr(t_end), count,
+                                             float(grad_scale), float(loss_scale), int(num_classes), float(log_scale_min),
+                                             _ptr(loss), _ptr(dout), _ptr(ws), ws.numel() * 4, _stream_handle(self.device))
+            self.lib.check(rc, "wn_mol_loss_ragged")
         self._dlogits_bound = None   # (the mixture head's loss call measures no maximum: backward scans its gradient)
         return loss, dout
 

@@ -397,20 +397,29 @@ class WaveNet(nn.Module):
         params = tuple(self.parameters())
         return _WaveNetFunction.apply(self, x, h, *params)
 
-    def loss_and_backward(self, x, h, t, t_start=None, grad_scale=1.0, events=None, layers_per_bucket=0, aux_grad=False):
+    def loss_and_backward(self, x, h, t, t_start=None, grad_scale=1.0, events=None, layers_per_bucket=0, aux_grad=False,
+                          lengths=None):
         """Fused training half-step: forward -> CrossEntropy on ``[:, t_start:]`` -> backward
         (reference train.py:533-538) without an autograd graph.
 
         Leaves the gradients in the flat buffer (``p.grad`` of every parameter is a view of it;
         ``None`` for the dead last ``res_1x1``) and returns the mean loss as a 1-element device
         tensor (no host sync).  ``grad_scale`` multiplies the gradients (1/world_size for DP).
-        ``aux_grad=True``: returns ``(loss, dh)`` with dh = d(loss)/dh (scaled by ``grad_scale`` as well)."""
+        ``aux_grad=True``: returns ``(loss, dh)`` with dh = d(loss)/dh (scaled by ``grad_scale`` as well).
+
+        ``lengths``: a padded batch of sequences of unequal length -- B host integers (a sequence of ints or a CPU integer
+        tensor), ``1 <= lengths[b] <= T``.  The loss is the mean over the positions ``[t_start, lengths[b])`` of every
+        sequence, i.e. ``nn.CrossEntropyLoss()`` with the targets behind each end set to -100; x, h and t may hold anything
+        finite on the padding.  Only the loss knows the lengths: the network is causal, so the padding reaches no valid
+        position, its ``dlogits`` is exactly zero and so is ``dh`` on every frame wholly behind a sequence's end.  The
+        residual stack still computes the whole (B, T) rectangle.  None: every sequence runs to T."""
         eng = self._engine
         if t_start is None:
             t_start = eng.receptive_field
         # forward + loss in one call: the cross-entropy is the epilogue of conv_post_2 where the model allows it (the logits
         # never reach memory), and the backward pass runs its post-net part over the loss window only
-        loss, dlogits = eng.forward_loss(x, h, t, t_start=t_start, grad_scale=grad_scale)
+        ragged = {} if lengths is None else {"lengths": lengths}
+        loss, dlogits = eng.forward_loss(x, h, t, t_start=t_start, grad_scale=grad_scale, **ragged)
         self._fwd_serial += 1
         dh = self._aux_grad_buffer(h) if aux_grad else None
         flat = eng.backward(dlogits, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh)
@@ -422,11 +431,11 @@ class WaveNet(nn.Module):
         return torch.empty(h.shape, dtype=torch.float32, device=self._engine.device)
 
     def mol_loss_and_backward(self, x, h, y, t_start=None, grad_scale=1.0, num_classes=65536, log_scale_min=None,
-                              events=None, layers_per_bucket=0, aux_grad=False):
+                              events=None, layers_per_bucket=0, aux_grad=False, lengths=None):
         """Training half-step of the mixture-of-logistics head (``n_mixture > 0``): forward -> mean negative
         log-likelihood of the waveform ``y`` (B, T) in [-1, 1] (the value of the NEXT sample at every position,
         like ``t`` of the softmax head) on ``[:, t_start:]`` -> backward.  Gradients land as in
-        ``loss_and_backward``; ``aux_grad=True`` returns ``(loss, dh)`` as there."""
+        ``loss_and_backward``; ``aux_grad=True`` returns ``(loss, dh)`` and ``lengths`` masks the padding as there."""
         if self.n_mixture <= 0:
             raise ValueError("this model has the softmax head (n_mixture = 0)")
         # ONE clamp for the likelihood and for sampling: the constructor's value (it travels in model.conf; a per-call
@@ -441,8 +450,9 @@ class WaveNet(nn.Module):
         self._fwd_serial += 1
         if t_start is None:
             t_start = eng.receptive_field
+        ragged = {} if lengths is None else {"lengths": lengths}
         loss, dout = eng.mol_loss(out, y, t_start=t_start, grad_scale=grad_scale, num_classes=num_classes,
-                                  log_scale_min=log_scale_min)
+                                  log_scale_min=log_scale_min, **ragged)
         dh = self._aux_grad_buffer(h) if aux_grad else None
         flat = eng.backward(dout, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh)
         for p, (off, n, shape, dead) in zip(self.parameters(), self._param_slices):

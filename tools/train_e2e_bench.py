@@ -59,6 +59,9 @@ def main():
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--batch_size", type=int, default=8)
     ap.add_argument("--batch_length", type=int, default=20000)
+    ap.add_argument("--utterance_batch", action="store_true",
+                    help="train.py --utterance_batch true: padded minibatches of --batch_size whole utterances (at --batch_size 1: the "
+                         "reference's utterance mode, batch_length None is not reachable from the CLI otherwise)")
     ap.add_argument("--producer-only", action="store_true")
     ap.add_argument("--batches", type=int, default=60, help="minibatches timed with --producer-only")
     ap.add_argument("--workers", type=int, default=None, help="WN_SLICER_WORKERS for the run")
@@ -109,7 +112,8 @@ def main():
             "--n_aux", "80", "--n_resch", "64", "--n_skipch", "256", "--dilation_depth", "10", "--dilation_repeat", "3",
             "--kernel_size", "2", "--upsampling_factor", "80", "--batch_size", str(args.batch_size),
             "--batch_length", str(args.batch_length), "--iters", str(args.iters), "--intervals", "50",
-            "--checkpoint_interval", "1000000", "--verbose", "1"])
+            "--checkpoint_interval", "1000000", "--verbose", "1"]
+           + (["--utterance_batch", "true"] if args.utterance_batch else []))
     out["wall_s"] = time.time() - t0
     secs = [float(m.group(1)) for m in re.finditer(r"\(([0-9.]+) sec / batch\)", stream.getvalue())]
     out["sec_per_batch_by_interval"] = secs
@@ -117,6 +121,13 @@ def main():
     out["host_ms_per_iteration_as_logged"] = 1e3 * sum(steady) / max(len(steady), 1)   # train.py's own figure: host time, launches are asynchronous
     gaps = [b - a for a, b in zip(stamps[:-1], stamps[1:])]
     out["end_to_end_ms_per_iteration"] = (1e3 * sum(gaps) / (50.0 * len(gaps))) if gaps else None   # wall time between log lines (device synchronised there)
+    if args.utterance_batch and out["end_to_end_ms_per_iteration"]:
+        # loss-bearing samples of an average minibatch: an utterance of f frames trains on (f - 1) * 80 - 3070 positions
+        from pytorchwavenetvocoder_amd.utils import read_txt, shape_hdf5
+        per_utt = [(shape_hdf5(f, "/melspc")[0] - 1) * SHIFT - 3070 for f in read_txt(feat_scp)]
+        out["utterance_batch"] = True
+        out["loss_samples_per_iteration"] = args.batch_size * sum(per_utt) / float(len(per_utt))
+        out["loss_samples_per_s"] = out["loss_samples_per_iteration"] / (1e-3 * out["end_to_end_ms_per_iteration"])
     print(json.dumps(out))
 
 
