@@ -206,7 +206,12 @@ int wn_bucket_range(const WnConfig* cfg, int layers_per_bucket, int bucket, int6
 int wn_dead_param_range(const WnConfig* cfg, int64_t* lo, int64_t* hi);
 
 /* Bytes of caller-provided scratch for batch B x T model inputs (forward + backward); 0 for an invalid
- * configuration or shape (wn_last_error()). */
+ * configuration or shape (wn_last_error()).
+ * No entry point reads a word of the workspace that was not written earlier in the same call or in the forward / loss call the
+ * backward call belongs to, so nothing depends on what the buffer held before: a buffer of at least this size may be reused
+ * from step to step, across (B, T) shapes (size it for the largest) and across flag sets, without clearing it in between.  The
+ * two assumptions on earlier contents are opt-in flags: WN_FLAG_WS_FINITE (wn_forward_loss) and WN_FLAG_DW_F16_AMAX_WS
+ * (wn_backward: the maximum the last loss call on THIS workspace left).  tests/workspace_common.py holds the library to this. */
 size_t wn_workspace_bytes(const WnConfig* cfg, int B, int T);
 
 /* Introspection for parity tests (since ABI v4; the training path never calls it): offset and length, in floats, of
