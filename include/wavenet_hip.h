@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 11
+#define WN_ABI_VERSION 12
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -333,6 +333,47 @@ int wn_backward_dh(const WnConfig* cfg, int B, int T, const float* params, const
 int wn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step,
                  float lr, float beta1, float beta2, float eps, float weight_decay, int64_t skip_lo, int64_t skip_hi,
                  void* stream);
+
+/* ---- global-norm gradient clipping and the non-finite-step guard (since ABI v12) ----
+ * Device-resident state of the guarded optimizer step: 56 bytes, 8-byte aligned, owned by the caller (zero it once; the two
+ * step counters are the only words that carry over from call to call, everything else is rewritten by every wn_grad_norm).
+ * Nothing here is read by the host on the training path: the Adam launch takes its scalars from this block. */
+typedef struct WnOptState {
+    double sumsq;          /*  0: sum of grads[i]^2 outside the skip range, accumulated in double */
+    float total_norm;      /*  8: (float)sqrt(sumsq): the norm BEFORE clipping (torch's clip_grad_norm_ return value) */
+    float clip_coef;       /* 12: min(1, max_norm / (total_norm + 1e-6)) in double, cast; exactly 1 when clipping is off */
+    int32_t apply;         /* 16: 1 = the Adam launch updates; 0 = guard on and the gradient is not finite: it writes nothing */
+    int32_t reserved;      /* 20: written as 0 */
+    int64_t steps_applied; /* 24: STATE: number of applied steps == the `step` of Adam's bias correction */
+    int64_t steps_skipped; /* 32: STATE: number of skipped steps */
+    float lr_over_bc1;     /* 40: lr / (1 - beta1^steps_applied) of this step (0 when it does not apply) */
+    float sqrt_bc2;        /* 44: sqrt(1 - beta2^steps_applied) of this step (0 when it does not apply) */
+    float beta1;           /* 48: as given to the norm call */
+    float beta2;           /* 52 */
+} WnOptState;
+
+/* Floats of scratch the norm needs for a buffer of n elements (one double per block of a grid that depends on n alone). */
+int64_t wn_grad_norm_scratch_floats(int64_t n);
+/* Two launches on `stream`, no host synchronisation:
+ *   1. sum of squares of grads[0, n) without [skip_lo, skip_hi), 16-byte loads with a scalar head / tail (grads needs 4-byte
+ *      alignment only), double accumulation per thread, wave and block, one partial per block, no atomics.  The grid is a
+ *      function of n alone and every sum has a fixed order: the same buffer (same address modulo 16) gives the same bits on
+ *      every device, so data-parallel ranks holding the same reduced gradient derive the same coefficient;
+ *   2. one block sums the partials in double and fills `state`: total_norm, clip_coef (max_norm <= 0 or infinite: measure
+ *      only, clip_coef = 1), apply, the counters, and lr / bc1 and sqrt(bc2) from the double formulas of the unguarded step
+ *      with the device's count of applied steps.
+ * Finiteness is judged on the double sum: finite elements of any magnitude never make it non-finite, a NaN or +-inf outside the
+ * skip range always does.  guard != 0: a non-finite gradient sets apply = 0, counts a skipped step and leaves the applied count;
+ * guard == 0: the step applies whatever the gradient holds (NaN reaches the weights, as in torch).
+ * scratch (8-byte aligned) and `state` influence no result through what they held before, the two counters excepted. */
+int wn_grad_norm(const float* grads, int64_t n, int64_t skip_lo, int64_t skip_hi, float max_norm, int guard, float lr,
+                 float beta1, float beta2, float* scratch, WnOptState* state, void* stream);
+/* The Adam step above with lr / bc1, sqrt(bc2), beta1, beta2, clip_coef and apply read from `state` as the preceding norm call
+ * on the same stream left them: g = clip_coef * grads[i] BEFORE the weight-decay term (torch clips the raw gradient; the
+ * optimizer adds L2 decay afterwards); `grads` itself is NOT modified (it keeps the unclipped values, unlike torch's in-place
+ * clip); when apply == 0 nothing is written to params, exp_avg or exp_avg_sq. */
+int wn_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float eps,
+                         float weight_decay, int64_t skip_lo, int64_t skip_hi, const WnOptState* state, void* stream);
 
 /* ---- op-level entry points (used by the composite calls above; exported for parity tests) ---- */
 

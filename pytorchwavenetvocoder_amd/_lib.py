@@ -60,6 +60,14 @@ class WnGemmArgs(ctypes.Structure):
         return g
 
 
+class WnOptState(ctypes.Structure):
+    """Mirror of ``struct WnOptState`` (include/wavenet_hip.h): the device-resident state of the guarded optimizer step."""
+    _fields_ = [("sumsq", ctypes.c_double), ("total_norm", ctypes.c_float), ("clip_coef", ctypes.c_float),
+                ("apply", ctypes.c_int32), ("reserved", ctypes.c_int32), ("steps_applied", ctypes.c_int64),
+                ("steps_skipped", ctypes.c_int64), ("lr_over_bc1", ctypes.c_float), ("sqrt_bc2", ctypes.c_float),
+                ("beta1", ctypes.c_float), ("beta2", ctypes.c_float)]
+
+
 # tensor kinds (include/wavenet_hip.h)
 (P_CAUSAL_W, P_CAUSAL_B, P_UP_W, P_UP_B, P_DSIG_W, P_DSIG_B, P_DTANH_W, P_DTANH_B, P_ASIG_W, P_ASIG_B,
  P_ATANH_W, P_ATANH_B, P_SKIP_W, P_SKIP_B, P_RES_W, P_RES_B, P_POST1_W, P_POST1_B, P_POST2_W, P_POST2_B) = range(20)
@@ -112,7 +120,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -124,6 +132,7 @@ EXPORTS = [
     "wn_decode_layered_state_floats", "wn_decode_layered_error_offset", "wn_decode_layered_prepare", "wn_decode_layered_steps", "wn_mol_loss",
     "wn_decode_ctx_aux", "wn_decode_prefill_workspace_bytes", "wn_decode_prefill",
     "wn_softmax_ce_loss_ragged", "wn_forward_loss_ragged", "wn_mol_loss_ragged",
+    "wn_grad_norm_scratch_floats", "wn_grad_norm", "wn_adam_step_guarded",
 ]
 
 
@@ -172,6 +181,10 @@ class WnLibrary(object):
         L.wn_backward_window.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
         L.wn_backward_dh.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
         L.wn_adam_step.argtypes = [vp, vp, vp, vp, i64, i64, f, f, f, f, f, i64, i64, vp]
+        L.wn_grad_norm_scratch_floats.argtypes = [i64]
+        L.wn_grad_norm_scratch_floats.restype = i64
+        L.wn_grad_norm.argtypes = [vp, i64, i64, i64, f, i, f, f, f, vp, vp, vp]
+        L.wn_adam_step_guarded.argtypes = [vp, vp, vp, vp, i64, f, f, i64, i64, vp, vp]
         L.wn_op_front.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.wn_op_causal_conv.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.wn_op_causal_conv_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]

@@ -433,6 +433,12 @@ def get_parser():
     # extension (not a reference flag): whole utterances, --batch_size of them per minibatch, padded to the longest one
     parser.add_argument("--utterance_batch", default=False, type=strtobool,
                         help="train on padded minibatches of --batch_size whole utterances (--batch_length is ignored)")
+    # extensions (not reference flags): global-norm gradient clipping and the non-finite-step guard of FusedAdam, both on the
+    # device (no synchronisation is added to the loop)
+    parser.add_argument("--max_grad_norm", default=0.0, type=float,
+                        help="clip the global gradient norm to this value before the Adam step (0: off)")
+    parser.add_argument("--skip_nonfinite_steps", default=False, type=strtobool,
+                        help="skip (and count) a step whose gradient holds a NaN or an inf instead of applying it")
     parser.add_argument("--resume", default=None, nargs="?", type=str, help="checkpoint to continue from")
     return parser
 
@@ -538,7 +544,10 @@ def _worker(rank, world, args, port):
         device=device,
         transforms_elementwise=True)   # mu-law and the standard scaler are per-sample / per-frame maps
 
-    optimizer = FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay)
+    max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
+    optimizer = FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay,
+                          max_grad_norm=max_grad_norm if max_grad_norm > 0.0 else None,
+                          skip_nonfinite=bool(getattr(args, "skip_nonfinite_steps", False)))
     if args.resume is not None and len(args.resume) != 0:
         checkpoint = torch.load(args.resume, map_location=lambda storage, loc: storage, weights_only=False)
         iterations = checkpoint["iterations"]
@@ -553,6 +562,8 @@ def _worker(rank, world, args, port):
         dist.broadcast(model.engine.flat_params, src=0)
 
     loss_acc = torch.zeros(1, device=device)
+    norm_acc = torch.zeros(1, device=device)     # guarded optimizer: sum of the finite pre-clip gradient norms of the interval
+    skipped_seen = optimizer.steps_skipped()
     total = 0.0
     for i in range(iterations, args.iters):
         start = time.time()
@@ -576,6 +587,8 @@ def _worker(rank, world, args, port):
                                                grad_scale=share, **ragged)
         optimizer.step()
         loss_acc += batch_loss.detach() * (share * world)
+        if optimizer.guarded:   # device-side accumulation, read at the interval's synchronisation below
+            norm_acc += torch.nan_to_num(optimizer.grad_norm, nan=0.0, posinf=0.0)
         if args.verbose > 1:
             logging.debug("batch loss = %.3f (%.3f sec / batch)" % (batch_loss.item(), time.time() - start))
         total += time.time() - start
@@ -589,6 +602,15 @@ def _worker(rank, world, args, port):
                 logging.info("(iter:%d) average loss = %.6f (%.3f sec / batch)" % (
                     i + 1, loss_acc.item() / args.intervals, total / args.intervals))
                 logging.info("estimated required time = " + _fmt_eta((args.iters - (i + 1)) * (total / args.intervals)))
+            if optimizer.guarded:
+                # every rank holds the same reduced gradient, hence the same norm: nothing to exchange
+                skipped_total = optimizer.steps_skipped()
+                skipped, skipped_seen = skipped_total - skipped_seen, skipped_total
+                if is_main:
+                    finite = max(args.intervals - skipped, 1)   # a skipped step's norm is not finite: it is left out of the mean
+                    logging.info("(iter:%d) average gradient norm before clipping = %.6f, skipped steps = %d" % (
+                        i + 1, norm_acc.item() / finite, skipped))
+                norm_acc.zero_()
             loss_acc.zero_()
             total = 0.0
         if (i + 1) % args.checkpoint_interval == 0 and is_main:

@@ -551,3 +551,32 @@ extern "C" int wn_adam_step(float* params, const float* grads, float* exp_avg, f
     return rt_check("wn_adam_step");
 }
 
+// ------------------------------------------------------------------------------------------
+// Global-norm clipping / non-finite-step guard (ABI v12): the norm (two launches) and the Adam launch that reads its scalars from
+// the device state block.  No host synchronisation anywhere.
+extern "C" int64_t wn_grad_norm_scratch_floats(int64_t n) {
+    return n > 0 ? 2 * (int64_t)wn_grad_sumsq_blocks((long)n) : 0;   // one double per block
+}
+
+extern "C" int wn_grad_norm(const float* grads, int64_t n, int64_t skip_lo, int64_t skip_hi, float max_norm, int guard, float lr,
+                            float beta1, float beta2, float* scratch, WnOptState* state, void* stream) {
+    api_enter();
+    if (!grads || !scratch || !state || n <= 0) return fail(1, "bad wn_grad_norm argument");
+    if (skip_lo < 0 || skip_hi > n || skip_lo > skip_hi) return fail(1, "wn_grad_norm: skip range outside [0, n]");
+    if ((reinterpret_cast<uintptr_t>(grads) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 7) || (reinterpret_cast<uintptr_t>(state) & 7))
+        return fail(1, "wn_grad_norm: grads needs 4-byte, scratch and state 8-byte alignment");
+    double* partial = reinterpret_cast<double*>(scratch);
+    WN_TRY(wn_grad_sumsq(grads, (long)n, (long)skip_lo, (long)skip_hi, partial, (wn_stream_t)stream));
+    WN_TRY(wn_grad_norm_finalize(partial, wn_grad_sumsq_blocks((long)n), max_norm, guard != 0, lr, beta1, beta2, state,
+                                 (wn_stream_t)stream));
+    return rt_check("wn_grad_norm");
+}
+
+extern "C" int wn_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float eps,
+                                    float weight_decay, int64_t skip_lo, int64_t skip_hi, const WnOptState* state, void* stream) {
+    api_enter();
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || n <= 0) return fail(1, "bad wn_adam_step_guarded argument");
+    WN_TRY(wn_adam_guarded(params, grads, exp_avg, exp_avg_sq, (long)n, eps, weight_decay, (long)skip_lo, (long)skip_hi, state,
+                           (wn_stream_t)stream));
+    return rt_check("wn_adam_step_guarded");
+}

@@ -49,6 +49,20 @@ int wn_softmax_ce_nblocks(int B, int T);
 int wn_adam(float* p, const float* g, float* m, float* v, long n, float lr_over_bc1, float inv_sqrt_bc2,
             float beta1, float beta2, float eps, float weight_decay, long skip_lo, long skip_hi, wn_stream_t st);
 
+// Global gradient norm for clipping / the non-finite-step guard (struct WnOptState: include/wavenet_hip.h).
+//   wn_grad_sumsq:         partial[b] = sum of g[i]^2 in double over block b's share of [0, n) minus [skip_lo, skip_hi);
+//                          wn_grad_sumsq_blocks(n) partials, a function of n alone (never of the device)
+//   wn_grad_norm_finalize: the partials in a fixed order -> norm, clip coefficient, apply flag, step counters and this step's
+//                          lr / bc1, sqrt(bc2) in the state block
+//   wn_adam_guarded:       wn_adam with those scalars read from the state block; writes nothing when the step does not apply
+struct WnOptState;
+int wn_grad_sumsq_blocks(long n);
+int wn_grad_sumsq(const float* g, long n, long skip_lo, long skip_hi, double* partial, wn_stream_t st);
+int wn_grad_norm_finalize(const double* partial, int nb, float max_norm, int guard, float lr, float beta1, float beta2,
+                          struct WnOptState* state, wn_stream_t st);
+int wn_adam_guarded(float* p, const float* g, float* m, float* v, long n, float eps, float weight_decay, long skip_lo, long skip_hi,
+                    const struct WnOptState* state, wn_stream_t st);
+
 // dst[d_off + i0*d0 + i1*d1 + i2*d2 + l*dl] = src[s_off + i0*s0 + i1*s1 + i2*s2 + l*sl]
 typedef struct WnCopy4 {
     int n0, n1, n2, nl;

@@ -27,6 +27,15 @@ def rccl_footprint_defaults():
 
 
 class GradientReducer(object):
+    """Bucketed all-reduce of the flat gradient buffer beside the backward kernels.
+
+    ``loss_and_backward`` returns after the caller's stream has joined the side stream, so what ``FusedAdam.step()`` reads is
+    already the GLOBAL gradient.  With ``FusedAdam(max_grad_norm=...)`` / ``skip_nonfinite=True`` the norm the optimizer clips by
+    (``optimizer.grad_norm``) and the finiteness it judges are therefore the global gradient's, on every rank.  The ranks agree
+    on the clip coefficient to the last bit without exchanging it: the all-reduce leaves the same bits in every rank's buffer,
+    and the norm's reduction is device-independent (its grid depends on the buffer's length alone and every partial sum has a
+    fixed order, include/wavenet_hip.h), so identical buffers give identical coefficients and the weights cannot drift apart."""
+
     def __init__(self, model, process_group=None, layers_per_bucket=None, exchange_when_alone=False):
         """``layers_per_bucket``: residual layers per gradient bucket = per weight-gradient launch group of wn_backward.
         Default (None): chosen by the size of the gradient.

@@ -468,6 +468,48 @@ class WaveNetEngine(object):
         self.lib.check(rc, "wn_adam_step")
         self._params_epoch += 1
 
+    # ---- global-norm clipping / non-finite-step guard (include/wavenet_hip.h, ABI v12) ---------------
+    OPT_STATE_WORDS = ctypes.sizeof(_lib.WnOptState) // 8   # the state block as int64 words (8-byte aligned)
+
+    def new_opt_state(self):
+        """A zeroed ``WnOptState`` on the engine's device (an int64 tensor; ``opt_state_views`` names its fields).  Allocate it,
+        and the scratch of ``grad_norm_scratch``, once per optimizer -- not per step."""
+        return torch.zeros(self.OPT_STATE_WORDS, dtype=torch.int64, device=self.device)
+
+    @staticmethod
+    def opt_state_views(state):
+        """0-dim views of the fields of a state block: no copies, no synchronisation."""
+        f, i32 = state.view(torch.float32), state.view(torch.int32)
+        return {"sumsq": state.view(torch.float64)[0], "total_norm": f[2], "clip_coef": f[3], "apply": i32[4],
+                "steps_applied": state[3], "steps_skipped": state[4], "lr_over_bc1": f[10], "sqrt_bc2": f[11]}
+
+    def grad_norm_scratch(self, n=None):
+        n = self.n_params if n is None else int(n)
+        return torch.empty(int(self.lib.wn_grad_norm_scratch_floats(n)), dtype=torch.float32, device=self.device)
+
+    def grad_norm(self, state, scratch, max_norm=0.0, guard=False, lr=1e-3, betas=(0.9, 0.999), grads=None, skip=None):
+        """Global L2 norm of the flat gradient (without the dead range) into ``state``, together with everything the guarded
+        Adam launch reads: two launches, no host synchronisation.  ``max_norm`` None / <= 0 / inf: measure only."""
+        g = self.grads() if grads is None else grads
+        self._check_device(g, scratch, state)
+        lo, hi = self.dead_range if skip is None else skip
+        if grads is not None and skip is None:
+            lo = hi = 0
+        rc = self.lib.wn_grad_norm(_ptr(g), g.numel(), int(lo), int(hi), float(max_norm) if max_norm else 0.0, int(bool(guard)),
+                                   float(lr), float(betas[0]), float(betas[1]), _ptr(scratch), _ptr(state),
+                                   _stream_handle(self.device))
+        self.lib.check(rc, "wn_grad_norm")
+
+    def adam_step_guarded(self, exp_avg, exp_avg_sq, state, eps=1e-8, weight_decay=0.0):
+        """``adam_step`` with its scalars (lr / bc1, sqrt(bc2), clip coefficient, apply flag) read from ``state`` as the
+        preceding ``grad_norm`` on the same stream left them.  The gradient buffer keeps its unclipped values."""
+        self._check_device(exp_avg, exp_avg_sq, state)
+        rc = self.lib.wn_adam_step_guarded(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                           self.n_params, float(eps), float(weight_decay), self.dead_range[0],
+                                           self.dead_range[1], _ptr(state), _stream_handle(self.device))
+        self.lib.check(rc, "wn_adam_step_guarded")
+        self._params_epoch += 1
+
     # ---- autoregressive decode (reference wavenet.py:309-511) ---------------------------------
     def decode_supported(self):
         return bool(self.lib.wn_decode_supported(ctypes.byref(self.cfg)))

@@ -7,6 +7,17 @@ parameters without a gradient are skipped (the dead last ``res_1x1``), and ``sta
 ``load_state_dict()`` use torch.optim.Adam's format (``{"state": {idx: {"step", "exp_avg",
 "exp_avg_sq"}}, "param_groups": [...]}``) so checkpoints written by either optimizer resume with
 the other (train.py:315-332,503-513).
+
+Opt-in, both free of host synchronisation:
+
+``max_grad_norm=c``     global-norm clipping, ``torch.nn.utils.clip_grad_norm_(model.parameters(), c)`` in front of the step: the
+                        norm of the whole flat gradient is reduced on the device (two launches) and the Adam launch scales the
+                        gradient by ``min(1, c / (norm + 1e-6))`` as it reads it.  Unlike torch's in-place clip the gradient
+                        buffer -- and so every ``p.grad`` -- KEEPS ITS UNCLIPPED VALUES.
+``skip_nonfinite=True`` a step whose gradient holds a NaN or an inf changes nothing (weights, moments, step count) and is
+                        counted in ``steps_skipped()``.
+
+With both at their defaults ``step()`` is the one ``adam`` launch with the host's step count, bit for bit as before.
 """
 import torch
 
@@ -14,7 +25,8 @@ from . import _lib
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
+                 skip_nonfinite=False):
         if not hasattr(model, "engine"):
             raise TypeError("FusedAdam takes the WaveNet model (it updates the model's flat buffer)")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
@@ -24,6 +36,46 @@ class FusedAdam(torch.optim.Optimizer):
         self._step = 0
         self._exp_avg = None
         self._exp_avg_sq = None
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be positive (None = no clipping)")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        self._opt_state = None     # device WnOptState + the norm's scratch: allocated once, on the first guarded use
+        self._norm_scratch = None
+
+    def _guard_buffers(self):
+        eng = self.model.engine
+        if self._opt_state is None or self._opt_state.device != eng.flat_params.device:
+            old = self._opt_state
+            self._opt_state = eng.new_opt_state()
+            self._norm_scratch = eng.grad_norm_scratch()
+            if old is not None:
+                self._opt_state.copy_(old)
+            else:
+                self._opt_state[3] = self._step
+        return self._opt_state, self._norm_scratch
+
+    @property
+    def grad_norm(self):
+        """0-dim device tensor (a view of the state block): the global gradient norm of the last ``step()`` BEFORE clipping --
+        under data parallelism the norm of the reduced, global gradient.  Valid after ``step()``; reading it on the device
+        needs no synchronisation.  None on the unguarded path."""
+        if not self.guarded:
+            return None
+        return self.model.engine.opt_state_views(self._guard_buffers()[0])["total_norm"]
+
+    def steps_applied(self):
+        """Number of applied steps (synchronises on the guarded path: the count lives on the device)."""
+        if not self.guarded:
+            return self._step
+        return int(self._guard_buffers()[0][3])
+
+    def steps_skipped(self):
+        """Number of steps the non-finite guard skipped (synchronises)."""
+        if not self.guarded:
+            return 0
+        return int(self._guard_buffers()[0][4])
 
     def _buffers(self):
         eng = self.model.engine
@@ -59,8 +111,15 @@ class FusedAdam(torch.optim.Optimizer):
             if not (lo <= p.grad.data_ptr() < hi):
                 flat_g[off:off + n].copy_(p.grad.reshape(-1))
         group = self.param_groups[0]
-        self._step += 1
-        eng.adam_step(m, v, self._step, group["lr"], group["betas"], group["eps"], group["weight_decay"])
+        if self.guarded:
+            # the gather above comes first: the norm is the norm of what the Adam launch reads (zeroed slices of live parameters
+            # without a gradient add 0, which is torch leaving them out)
+            state, scratch = self._guard_buffers()
+            eng.grad_norm(state, scratch, self.max_grad_norm, self.skip_nonfinite, group["lr"], group["betas"])
+            eng.adam_step_guarded(m, v, state, group["eps"], group["weight_decay"])
+        else:
+            self._step += 1
+            eng.adam_step(m, v, self._step, group["lr"], group["betas"], group["eps"], group["weight_decay"])
         for sl, p0, m0, v0 in skipped:   # the one launch covers the whole flat buffer: put the skipped slices back
             eng.flat_params[sl].copy_(p0)
             m[sl].copy_(m0)
@@ -71,11 +130,12 @@ class FusedAdam(torch.optim.Optimizer):
     def state_dict(self):
         m, v = self._buffers()
         state = {}
-        if self._step > 0:
+        step = self.steps_applied()
+        if step > 0:
             for idx, (off, n, shape, dead) in enumerate(self.model._param_slices):
                 if dead:
                     continue
-                state[idx] = {"step": torch.tensor(float(self._step)),
+                state[idx] = {"step": torch.tensor(float(step)),
                               "exp_avg": m[off:off + n].view(shape).clone(),
                               "exp_avg_sq": v[off:off + n].view(shape).clone()}
         groups = []
@@ -96,6 +156,8 @@ class FusedAdam(torch.optim.Optimizer):
             v[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
             step = max(step, int(float(st["step"])))
         self._step = step
+        if self.guarded:
+            self._guard_buffers()[0][3] = step
         for g, sg in zip(self.param_groups, sd["param_groups"]):
             for k in ("lr", "betas", "eps", "weight_decay"):
                 if k in sg:
