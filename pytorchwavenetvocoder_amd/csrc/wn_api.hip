@@ -31,29 +31,20 @@ static int fail(int code, const char* fmt, ...) {
 // Every entry point starts from a clean slate: the error text is reset and an error some EARLIER runtime call of
 // the process left behind (hipGetLastError is sticky per thread: e.g. a device probe before the framework
 // initialised the runtime) is discarded, so rt_check only reports launches of this call.
-#ifdef WN_EMU
-static void api_enter() { g_err[0] = 0; }
-#else
 static void api_enter() {
     g_err[0] = 0;
-    (void)hipGetLastError();
+    wn_rt_clear_error();
 }
-#endif
 
-#ifdef WN_EMU
-static int rt_check(const char*) { return 0; }
-static void rt_event_record(void*, wn_stream_t) { wn_prof_mark("bucket_event"); }
-#else
 static int rt_check(const char* where) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(100, "HIP error after %s: %s", where, hipGetErrorString(e));
+    const char* e = wn_rt_last_error();
+    if (e) return fail(100, "HIP error after %s: %s", where, e);
     return 0;
 }
 static void rt_event_record(void* ev, wn_stream_t st) {
     wn_prof_mark("bucket_event");
-    (void)hipEventRecord((hipEvent_t)ev, st);
+    wn_rt_event_record(ev, st);
 }
-#endif
 
 // ------------------------------------------------------------------------------------------
 // Internal side stream of wn_backward.  The data chain of the backward pass (gate', dX: 2 dependent launches per
@@ -70,12 +61,10 @@ static void rt_event_record(void* ev, wn_stream_t st) {
 struct SideRt {
     wn_stream_t st;
 };
-struct SideLock {   // emulator: one in-order "stream", but the overlap launch sequences (chunked skip-sum) still run
+struct SideLock {   // emulator: the side "stream" is the caller's own, but the overlap launch sequences (chunked skip-sum) still run
+    SideRt one;
     SideRt* rt;
-    SideLock(bool want, wn_stream_t) : rt(nullptr) {
-        static SideRt one = {nullptr};
-        if (want) rt = &one;
-    }
+    SideLock(bool want, wn_stream_t caller) : one{caller}, rt(want ? &one : nullptr) {}
 };
 static int side_link(SideRt*, wn_stream_t, wn_stream_t) { return 0; }
 #else
@@ -1055,9 +1044,7 @@ static int forward_impl(const WnConfig* cfg, int B, int T, const float* params, 
     SideLock side((flags & WN_FLAG_FWD_OVERLAP) && c.fused && !wn_prof_is_on(), c.st);
     Ctx cs = c;
     int skip_done = 0;
-#ifndef WN_EMU
     if (side.rt) cs.st = side.rt->st;
-#endif
     const Dims& d = c.d;
     const Lay& y = c.y;
     const Ws& w = c.w;

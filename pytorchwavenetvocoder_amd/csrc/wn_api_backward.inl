@@ -115,9 +115,7 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
     // c = the data chain on the caller's stream; cs = the weight gradients, on the side stream unless serial
     SideLock side((flags & WN_FLAG_BWD_OVERLAP) && !wn_prof_is_on(), c.st);
     Ctx cs = c;
-#ifndef WN_EMU
     if (side.rt) cs.st = side.rt->st;
-#endif
     const Dims& d = c.d;
     const Lay& y = c.y;
     const Ws& w = c.w;

@@ -16,12 +16,8 @@
 #define WN_DH_TPB 256
 
 static __device__ __forceinline__ void dh_ld4(const float* p, float (&v)[4]) {
-#ifdef WN_EMU
-    memcpy(v, p, 16);
-#else
     const wn_f4 q = wn_ld4_unaligned(p);
-    v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
-#endif
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
 }
 
 // row k of the B operand, columns [n, n + 4) (zeros beyond ncol)

@@ -221,15 +221,10 @@ extern "C" void wn_decode_debug_set_buffer(void* p) { g_dec_dbg = (long long*)p;
 // The LDS addresses of the matrix-vector units are loop invariant; hoisted out of the step loop they would pin
 // ~90 registers next to the weight ring.  Passing the lane's role through an empty asm once per layer / per step
 // makes the compiler recompute them (two VALU ops each) where they are used.
-#ifdef WN_EMU
-#define WN_OPAQUE(x) (x)
-#else
 static __device__ __forceinline__ int wn_opaque(int v) {
-    asm volatile("" : "+v"(v));
+    WN_PIN(v);
     return v;
 }
-#define WN_OPAQUE(x) wn_opaque(x)
-#endif
 
 template <int UD, int UR, int US, int UP1, int UP2>
 __global__ __launch_bounds__(WN_DT) void k_decode(WnDecodeArgs a) {
@@ -383,7 +378,7 @@ __global__ __launch_bounds__(WN_DT) void k_decode(WnDecodeArgs a) {
         // ---- residual stack (wavenet.py:538-549) ------------------------------------------------
         for (int l = 0; l < L; ++l) {
             const float* xl = xin + l * XS;
-            const int part_d = WN_OPAQUE(part_d0), part_r = WN_OPAQUE(part_r0), part_s = WN_OPAQUE(part_s0);
+            const int part_d = wn_opaque(part_d0), part_r = wn_opaque(part_r0), part_s = wn_opaque(part_s0);
             const unsigned nxt = (unsigned)(l + 1) * LB;  // after the last layer: post pseudo-layer 0
             f32x2 sg = f32x2{0.f, 0.f};  // (sigmoid row, tanh row) of channel c_d
             WN_UNROLL
@@ -441,7 +436,7 @@ __global__ __launch_bounds__(WN_DT) void k_decode(WnDecodeArgs a) {
         DSTAMP(3);
 
         // ---- post net (wavenet.py:518-523) -------------------------------------------------------
-        const int part_s = WN_OPAQUE(part_s0), part_1 = WN_OPAQUE(part_10), part_2 = WN_OPAQUE(part_20);
+        const int part_s = wn_opaque(part_s0), part_1 = wn_opaque(part_10), part_2 = wn_opaque(part_20);
         {
             const float v = group_sum(acc_sk.x + acc_sk.y, pl.lg_ps);
             acc_sk = f32x2{0.f, 0.f};
@@ -587,12 +582,7 @@ __global__ __launch_bounds__(WN_DT) void k_decode(WnDecodeArgs a) {
 
 template <int UD, int UR, int US, int UP1, int UP2>
 static int launch_cls(const WnDecodeArgs& a, int B, wn_stream_t st) {
-#ifndef WN_EMU
-    if (a.plan.lds_bytes > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode<UD, UR, US, UP1, UP2>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.plan.lds_bytes) != hipSuccess)
-        return 1;
-#endif
+    if (wn_dyn_lds<k_decode<UD, UR, US, UP1, UP2>>(a.plan.lds_bytes)) return 1;
 #ifdef WN_TIMING
     WnDecodeArgs a2 = a;
     a2.dbg = g_dec_dbg;

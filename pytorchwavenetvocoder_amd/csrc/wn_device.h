@@ -1,12 +1,18 @@
 // wn_device.h -- device-side common definitions for the gfx950 (CDNA4 / MI355X) kernels.
 //
 // The product build is hipcc --offload-arch=gfx950.  The same sources also compile with g++
-// and -DWN_EMU against tests/emu/hip_emu.h (TEST INFRASTRUCTURE: index-math checks without a
-// GPU).  Everything architecture specific is funnelled through this header:
+// and the emulator macro against tests/emu/hip_emu.h (TEST INFRASTRUCTURE: index-math checks
+// without a GPU).  Everything architecture specific is funnelled through this header, and so is the seam between the two
+// builds: the ONE #ifdef below holds the emulator's half and the HIP half of every primitive, under one name each.  Kernels and
+// launchers do not name the macro (besides this header only the side-stream runtime of wn_api.hip and the two implementations
+// of wn_prof.hip do; tests/test_abi.py keeps it so).
 //   * f32x16 / mfma32(): v_mfma_f32_32x32x2_f32 -- exact f32 (k-ordered fma chain) at the f32
 //     vector rate; lane l supplies A[i=l&31][k=l>>5] and B[k=l>>5][j=l&31]; the 16 accumulator
 //     registers of lane l hold D[row=(r&3)+8*(r>>2)+4*(l>>5)][col=l&31].
 //   * WN_LAUNCH(): kernel launch on an explicit stream.
+//   * wn_dyn_lds<kernel>(bytes): the only caller of hipFuncSetAttribute -- raises a kernel's dynamic-LDS limit, once per
+//     kernel, device and size; wn_coop_capacity_cached<kernel>(): resident workgroups, cached the same way.
+//   * wn_rt_*(): the host runtime calls of wn_api.hip; wn_setprio / WN_PIN / wn_fmul_rn: instructions the emulator has no use for.
 #pragma once
 
 #include <stddef.h>
@@ -34,8 +40,27 @@ static inline int wn_coop_capacity(Kn, int, size_t) {
     return o >= 0 ? o : 0x7fffffff;
 }
 #define WN_COOP_MAXDEV 64
-template <typename Kn>
-static inline int wn_coop_capacity_cached(int (&)[WN_COOP_MAXDEV], bool&, Kn k, int b, size_t l) { return wn_coop_capacity(k, b, l); }
+template <auto Kern>
+static inline int wn_coop_capacity_cached(int b, size_t l) { return wn_coop_capacity(Kern, b, l); }
+template <auto Kern>
+static inline int wn_dyn_lds(size_t) { return 0; }   // the emulator's LDS is as large as the launch asks for
+// host runtime primitives of wn_api.hip: no sticky error, no events (one in-order "stream")
+static inline void wn_rt_clear_error() {}
+static inline const char* wn_rt_last_error() { return nullptr; }
+static inline void wn_rt_event_record(void*, wn_stream_t) {}
+// wave priority and register pins steer the hardware scheduler and hipcc only
+#define wn_setprio(n) ((void)0)
+#define WN_PIN(x) ((void)(x))
+#define WN_PIN2(x, y) ((void)(x), (void)(y))
+static inline float wn_fmul_rn(float a, float b) { return a * b; }   // (built with -ffp-contract=off)
+// 2^x, 1 / x, log2 x; the sum over each aligned group of 16 lanes
+static inline float wn_exp2(float x) { return exp2f(x); }
+static inline float wn_rcp(float x) { return 1.0f / x; }
+static inline float wn_log2(float x) { return log2f(x); }
+static inline float wn_row16_sum(float v) {
+    for (int m = 1; m <= 8; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
 #define WN_DYN_SMEM(name) char* name = emu::S().dyn_smem
 static inline f32x16 mfma32(float a, float b, f32x16 c) { return emu::mfma_f32_32x32x2f32(a, b, c); }
 typedef emu::f32x4_t f32x4;
@@ -158,7 +183,7 @@ typedef hipStream_t wn_stream_t;
     hipLaunchKernelGGL(kernel, (grid), (block), (smem), (stream), __VA_ARGS__)
 // Workgroups of `kernel` (block threads, `lds` bytes of dynamic LDS) the current device keeps resident at once = occupancy per
 // CU x CUs: the bound a WN_LAUNCH_COOP grid is checked against BEFORE it is launched (a partitioned GPU -- CPX / DPX --, a part
-// with fewer CUs).  0 when the query fails.  The caller caches the value per kernel (the devices of a node are alike).
+// with fewer CUs).  0 when the query fails.
 // WN_COOP_CAPACITY=<n> in the environment overrides the query (test knob: the error / fall-back paths on a full chip).
 #include <stdlib.h>
 static inline int wn_coop_capacity_override() {
@@ -177,23 +202,54 @@ static inline int wn_coop_capacity(Kn kernel, int block, size_t lds) {
     }
     return per * cus;
 }
-// The same, cached PER DEVICE (one process may decode on several devices, and a node's devices need not be alike:
-// partitioned GPUs).  `cache` = a static array of WN_COOP_MAXDEV ints initialised to -1 by the caller's first use.
+// The same, cached PER KERNEL AND PER DEVICE (one process may decode on several devices, and a node's devices need
+// not be alike: partitioned GPUs).  The cache holds capacity + 1; 0 = not asked yet.
 #define WN_COOP_MAXDEV 64
-template <typename Kn>
-static inline int wn_coop_capacity_cached(int (&cache)[WN_COOP_MAXDEV], bool& init, Kn kernel, int block, size_t lds) {
+template <auto Kern>
+static inline int wn_coop_capacity_cached(int block, size_t lds) {
     const int o = wn_coop_capacity_override();
     if (o >= 0) return o;
-    if (!init) {
-        for (int i = 0; i < WN_COOP_MAXDEV; ++i) cache[i] = -1;
-        init = true;
-    }
+    static int cache[WN_COOP_MAXDEV];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if (dev < 0 || dev >= WN_COOP_MAXDEV) return wn_coop_capacity(kernel, block, lds);
-    if (cache[dev] < 0) cache[dev] = wn_coop_capacity(kernel, block, lds);
-    return cache[dev];
+    if (dev < 0 || dev >= WN_COOP_MAXDEV) return wn_coop_capacity(Kern, block, lds);
+    if (cache[dev] == 0) cache[dev] = wn_coop_capacity(Kern, block, lds) + 1;
+    return cache[dev] - 1;
 }
+// Dynamic LDS beyond the default limit of 64 KB has to be allowed per kernel and per device before the launch (or the occupancy
+// query) that needs it: the ONE place that does so.  Called at every launch site with the bytes of that launch; asks the
+// runtime only when they exceed what this kernel was last given on the current device (a device index outside the table: every
+// time).  Non-zero when the runtime refuses.  The table is relaxed-atomic: two threads that race both make the same idempotent
+// call, and the larger value of a mixed race is simply set again by the next launch that needs it.
+#include <atomic>
+template <auto Kern>
+static inline int wn_dyn_lds(size_t bytes) {
+    if (bytes <= 64 * 1024) return 0;
+    static std::atomic<int> given[WN_COOP_MAXDEV];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 1;
+    const bool tab = dev >= 0 && dev < WN_COOP_MAXDEV;
+    if (tab && (size_t)given[dev].load(std::memory_order_relaxed) >= bytes) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+        return 1;
+    if (tab) given[dev].store((int)bytes, std::memory_order_relaxed);
+    return 0;
+}
+// host runtime primitives of wn_api.hip: drop the thread's sticky error; the last error as text (NULL: none); record an event
+static inline void wn_rt_clear_error() { (void)hipGetLastError(); }
+static inline const char* wn_rt_last_error() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+static inline void wn_rt_event_record(void* ev, wn_stream_t st) { (void)hipEventRecord((hipEvent_t)ev, st); }
+// s_setprio: issue priority of the wave (an immediate: a macro)
+#define wn_setprio(n) __builtin_amdgcn_s_setprio(n)
+// register pin: the value exists, in a VGPR, from here on -- the compiler neither sinks its computation below this point nor
+// treats what it computes from it afterwards as known before
+#define WN_PIN(x) asm volatile("" : "+v"(x))
+#define WN_PIN2(x, y) asm volatile("" : "+v"(x), "+v"(y))   // (one statement: two would be two scheduling points)
+// a product that is never contracted into a neighbouring fma
+static __device__ __forceinline__ float wn_fmul_rn(float a, float b) { return __fmul_rn(a, b); }
 #define WN_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) char name[]
 static __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -355,6 +411,22 @@ static __device__ __forceinline__ unsigned wn_f32_bits(float f) { return __built
 // two-lane fp32 vector: fma on it is one v_pk_fma_f32
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 static __device__ __forceinline__ f32x2 wn_pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+// the hardware transcendental units (v_exp_f32 = 2^x, v_rcp_f32, v_log_f32 = log2 x: 1 ulp): see wn_sigmoid / wn_tanh below
+static __device__ __forceinline__ float wn_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+static __device__ __forceinline__ float wn_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+static __device__ __forceinline__ float wn_log2(float x) { return __builtin_amdgcn_logf(x); }
+// Sum over each aligned group of 16 lanes (a DPP "row"); every lane of the group ends with the same bits.
+template <int CTRL>
+static __device__ __forceinline__ float wn_dpp_f32(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+static __device__ __forceinline__ float wn_row16_sum(float v) {
+    v += wn_dpp_f32<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += wn_dpp_f32<0x4E>(v);   // quad_perm [2,3,0,1]
+    v += wn_dpp_f32<0x141>(v);  // row_half_mirror: the other quad of the 8
+    v += wn_dpp_f32<0x140>(v);  // row_mirror: the other 8 of the 16
+    return v;
+}
 #define WN_UNROLL _Pragma("unroll")
 #define WN_NOUNROLL _Pragma("unroll 1")
 #define WN_PRAGMA(x) _Pragma(#x)
@@ -390,15 +462,6 @@ static __device__ __forceinline__ f32x16 f32x16_zero() {
 // e = 2^(-2|x| log2 e) carry an ABSOLUTE error of a few 1e-7 -- far inside the 1e-4 parity gate --
 // at ~1/4 of the instruction count of ocml expf/tanhf + IEEE division (the gate math is the
 // VALU-heavy part of the fused residual-block kernels).
-#ifdef WN_EMU
-static inline float wn_exp2(float x) { return exp2f(x); }
-static inline float wn_rcp(float x) { return 1.0f / x; }
-static inline float wn_log2(float x) { return log2f(x); }
-#else
-static __device__ __forceinline__ float wn_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-static __device__ __forceinline__ float wn_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-static __device__ __forceinline__ float wn_log2(float x) { return __builtin_amdgcn_logf(x); }
-#endif
 static __device__ __forceinline__ float wn_sigmoid(float x) {
     const float xc = fminf(fmaxf(x, -80.0f), 80.0f);  // keeps 2^(...) finite; sigmoid(+-80) is 1/0 in fp32
     return wn_rcp(1.0f + wn_exp2(-1.4426950408889634f * xc));
@@ -415,25 +478,6 @@ static __device__ __forceinline__ float wave_reduce_sum(float v) {
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
     return v;
 }
-// Sum over each aligned group of 16 lanes (a DPP "row"); every lane of the group ends with the same bits.
-#ifdef WN_EMU
-static inline float wn_row16_sum(float v) {
-    for (int m = 1; m <= 8; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-#else
-template <int CTRL>
-static __device__ __forceinline__ float wn_dpp_f32(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-static __device__ __forceinline__ float wn_row16_sum(float v) {
-    v += wn_dpp_f32<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += wn_dpp_f32<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += wn_dpp_f32<0x141>(v);  // row_half_mirror: the other quad of the 8
-    v += wn_dpp_f32<0x140>(v);  // row_mirror: the other 8 of the 16
-    return v;
-}
-#endif
 static __device__ __forceinline__ float wave_reduce_max(float v) {
     WN_UNROLL
     for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));

@@ -613,22 +613,11 @@ __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlp(WnDlpArgs a) {
     if (tid == 0 && s_flag[0]) wn_store_coherent_int(a.err, 1);
 }
 
-// LDS attribute (once) and the number of workgroups of this class the device keeps resident (cached; 0: the query failed)
+// LDS limit (wn_dyn_lds) and the number of workgroups of this class the device keeps resident (cached; 0: the query failed)
 template <int RS, int NSP, int NSX>
 static int capacity_cls(long lds_bytes) {
-    static int cap[WN_COOP_MAXDEV];
-    static bool cap_init = false;
-#ifndef WN_EMU
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_dlp<RS, NSP, NSX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes) != hipSuccess)
-            return 0;
-        attr_set = true;
-    }
-#endif
-    if (wn_coop_capacity_override() >= 0) return wn_coop_capacity_override();
-    return wn_coop_capacity_cached(cap, cap_init, k_dlp<RS, NSP, NSX>, WN_DLP_T, (size_t)lds_bytes);
+    if (wn_dyn_lds<k_dlp<RS, NSP, NSX>>((size_t)lds_bytes)) return 0;
+    return wn_coop_capacity_cached<k_dlp<RS, NSP, NSX>>(WN_DLP_T, (size_t)lds_bytes);
 }
 
 template <int RS, int NSP, int NSX>

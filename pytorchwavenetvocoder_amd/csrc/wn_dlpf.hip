@@ -476,20 +476,9 @@ static constexpr size_t lds_flags() {
 
 template <int NSP, int NSX>
 static int capacity_flags() {   // as capacity_cls of wn_dlp.hip
-    static int cap[WN_COOP_MAXDEV];
-    static bool cap_init = false;
     constexpr size_t lds = lds_flags<NSP, NSX>();
-#ifndef WN_EMU
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_dlpf<NSP, NSX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess)
-            return 0;
-        attr_set = true;
-    }
-#endif
-    if (wn_coop_capacity_override() >= 0) return wn_coop_capacity_override();
-    return wn_coop_capacity_cached(cap, cap_init, k_dlpf<NSP, NSX>, WN_DLP_T, lds);
+    if (wn_dyn_lds<k_dlpf<NSP, NSX>>(lds)) return 0;
+    return wn_coop_capacity_cached<k_dlpf<NSP, NSX>>(WN_DLP_T, lds);
 }
 
 template <int NSP, int NSX>

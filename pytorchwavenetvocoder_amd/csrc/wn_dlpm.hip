@@ -452,19 +452,8 @@ __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlpm(WnDlpArgs a) {
 
 template <int NSP, int NSX>
 static int capacity_wide(long lds_bytes) {   // as capacity_cls of wn_dlp.hip
-    static int cap[WN_COOP_MAXDEV];
-    static bool cap_init = false;
-#ifndef WN_EMU
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_dlpm<NSP, NSX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes) != hipSuccess)
-            return 0;
-        attr_set = true;
-    }
-#endif
-    if (wn_coop_capacity_override() >= 0) return wn_coop_capacity_override();
-    return wn_coop_capacity_cached(cap, cap_init, k_dlpm<NSP, NSX>, WN_DLP_T, (size_t)lds_bytes);
+    if (wn_dyn_lds<k_dlpm<NSP, NSX>>((size_t)lds_bytes)) return 0;
+    return wn_coop_capacity_cached<k_dlpm<NSP, NSX>>(WN_DLP_T, (size_t)lds_bytes);
 }
 
 template <int NSP, int NSX>

@@ -150,12 +150,7 @@ int wn_front_gather(const int64_t* x, const float* wc_f, const float* bias, floa
         int ch = (T + nc - 1) / nc;
         ch = (ch + 63) / 64 * 64;
         nc = (T + ch - 1) / ch;
-#ifndef WN_EMU
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_front_gather_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return 2;
-#endif
+        if (wn_dyn_lds<k_front_gather_lds>(lds)) return 2;
         WN_LAUNCH(k_front_gather_lds, dim3((unsigned)nc, (unsigned)B, (unsigned)(R / RG)), dim3(FG_T), lds, st, x, wc_f, bias, x0, T, Q, R, K, ch, RG);
         return 0;
     }
@@ -578,11 +573,7 @@ __global__ __launch_bounds__(WN_TPB) void k_adam_guarded(float* __restrict__ p, 
     for (long i = (long)blockIdx.x * WN_TPB + threadIdx.x; i < n; i += stride) {
         if (i >= skip_lo && i < skip_hi) continue;
         const float pv = p[i];
-#ifdef WN_EMU
-        float gv = coef * g[i];
-#else
-        float gv = __fmul_rn(coef, g[i]);   // never contracted into the decay term's fma: coef == 1 leaves k_adam's arithmetic
-#endif
+        float gv = wn_fmul_rn(coef, g[i]);   // never contracted into the decay term's fma: coef == 1 leaves k_adam's arithmetic
         if (wd != 0.0f) gv += wd * pv;
         const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
         const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
@@ -1274,17 +1265,13 @@ int wn_front_dw(const float* dX0, const int64_t* x, float* partial, float* dW, f
     const int RG = front_dw_row_groups(R, K, Q);
     front_dw_grid(B, T, RG, &nc, &ch);
     const size_t lds = ((size_t)R * K * Q + R) * 4;
-#ifndef WN_EMU
-    if (!front_dw_mfma_ok(R, K, Q) && lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_front_dw_scatter), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return 2;
-#endif
     if (front_dw_mfma_ok(R, K, Q)) {
         const size_t lds_m = 2 * 2 * 3 * 2048 + (size_t)(ch + K) * 4;
         WN_LAUNCH(k_front_dw_mfma, dim3((unsigned)nc, (unsigned)B, (unsigned)RG), dim3(FM_T), lds_m, st, dX0, x, partial, T, R, K, Q, ch);
-    } else
-    WN_LAUNCH(k_front_dw_scatter, dim3((unsigned)nc, (unsigned)B), dim3(FD_T), lds, st, dX0, x, partial, T, R, K, Q, ch);
+    } else {
+        if (wn_dyn_lds<k_front_dw_scatter>(lds)) return 2;
+        WN_LAUNCH(k_front_dw_scatter, dim3((unsigned)nc, (unsigned)B), dim3(FD_T), lds, st, dX0, x, partial, T, R, K, Q, ch);
+    }
     const long per = (long)R * K * Q + R;
     WN_LAUNCH(k_front_dw_reduce, dim3((unsigned)((per + 63) / 64)), dim3(256), 0, st, partial, nc * B, dW, db, R, K, Q);
     return 0;

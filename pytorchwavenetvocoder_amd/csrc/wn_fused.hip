@@ -72,11 +72,11 @@ static long chain_blocks() {
 // for its gate phase: the MFMAs go out when their operands are ready, the neighbour's gate math fills the gaps.  Same box:
 // forward blocks 1.89 -> 1.82 ms per step, backward chain 2.94 -> 2.91 (profiles/r02/ab_probe_prio_phases.txt); the opposite
 // assignment is slower than none (1.94).
-#if !defined(WN_NO_PRIO_PHASES) && !defined(WN_EMU)
+#ifndef WN_NO_PRIO_PHASES
 #ifdef WN_PRIO_GATE_BY_WAVE   // experiment: the second wave of a SIMD keeps priority 1 in its gate phase
-#define WN_PRIO(n) do { if ((n) == WN_PRIO_GATE && (threadIdx.x >> 8)) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(n); } while (0)
+#define WN_PRIO(n) do { if ((n) == WN_PRIO_GATE && (threadIdx.x >> 8)) wn_setprio(1); else wn_setprio(n); } while (0)
 #else
-#define WN_PRIO(n) __builtin_amdgcn_s_setprio(n)
+#define WN_PRIO(n) wn_setprio(n)
 #endif
 #else
 #define WN_PRIO(n)
@@ -122,17 +122,6 @@ int wn_fused_supported(int R, int K, int S) {
     const long lim = 160 * 1024;
     return fwd <= lim && gate <= lim && dx <= lim;
 }
-
-#ifndef WN_EMU
-template <class Kern>
-static int set_lds(Kern kern, size_t bytes) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e == hipSuccess ? 0 : 1;
-}
-#else
-template <class Kern>
-static int set_lds(Kern, size_t) { return 0; }
-#endif
 
 // XCD-aware tile mapping.  Workgroup b is dispatched to XCD b % 8 (each XCD has its own 4 MB L2): the tile
 // space is cut into 8 contiguous time ranges, one per XCD, and the 256 waves of an XCD walk their range
@@ -806,10 +795,8 @@ __global__ __launch_bounds__(WN_LB) void k_resblock_fwd_s(FwdArgs a) {
                 for (int r = 0; r < 16; ++r)
                     xb2[q][r] = (inb ? xc[16 * q + r] : 0.0f) + rbl[32 * q + mfma32_row(r, 0)];
             }
-#ifndef WN_EMU
             // pin: the sums exist from here on (machine sinking would otherwise move them below the branch and keep xc alive)
-            asm volatile("" : "+v"(xb2[0]), "+v"(xb2[1]));
-#endif
+            WN_PIN2(xb2[0], xb2[1]);
         }
         // next tile of this wave: its history taps are requested NOW, before the stores of the gate phase.  (A variant that
         // kept the history tap of a d >= 32 layer in registers across "tile chains" measured slower -- 60 B/lane of scratch and
@@ -1309,9 +1296,7 @@ __global__ __launch_bounds__(WN_LB) void k_resblock_fwd_h(FwdArgs a) {
                 for (int r = 0; r < 16; ++r)
                     xb2[q][r] = (inb ? xc[16 * q + r] : 0.0f) + rbl[32 * q + mfma32_row(r, 0)];
             }
-#ifndef WN_EMU
-            asm volatile("" : "+v"(xb2[0]), "+v"(xb2[1]));
-#endif
+            WN_PIN2(xb2[0], xb2[1]);
         }
         const int next_v = tile_v + step;
         if (K > 1 && next_v < tile_end) issue_hist(next_v);
@@ -1414,19 +1399,19 @@ static int launch_fwd(const FwdArgs& a, int split, wn_stream_t st) {
     if (split == 2) {   // fp16 pair split (needs the two-piece image of wn_fused_pack_images16)
         if (a.wimg == nullptr) return 1;
         const size_t lds_h = (size_t)fwd16_image_bytes(K) + 192 * sizeof(float);
-        if (set_lds(k_resblock_fwd_h<K>, lds_h)) return 1;
+        if (wn_dyn_lds<k_resblock_fwd_h<K>>(lds_h)) return 1;
         WN_LAUNCH((k_resblock_fwd_h<K>), dim3((unsigned)nblk), dim3(WN_FT), lds_h, st, a);
         return 0;
     }
     // split arithmetic: taps (+ res 1x1 for K <= 2; K = 3 reads those fragments from the global image) + cvec / bias
     const size_t lds_s = (size_t)K * 4 * (3 * 128 * 32) + (K >= 3 ? 0 : 4 * (3 * 64 * 32)) + 192 * sizeof(float);
     if (split && lds_s <= 160 * 1024 && (K < 3 || a.wimg != nullptr)) {  // (K = 3 without a weight image: the f32 MFMA kernel)
-        if (set_lds(k_resblock_fwd_s<K>, lds_s)) return 1;
+        if (wn_dyn_lds<k_resblock_fwd_s<K>>(lds_s)) return 1;
         WN_LAUNCH((k_resblock_fwd_s<K>), dim3((unsigned)nblk), dim3(WN_FT), lds_s, st, a);
         return 0;
     }
     const size_t lds = ((size_t)K * 64 * 128 + 64 * 64 + 192) * sizeof(float);
-    if (set_lds(k_resblock_fwd<K>, lds)) return 1;
+    if (wn_dyn_lds<k_resblock_fwd<K>>(lds)) return 1;
     WN_LAUNCH((k_resblock_fwd<K>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
     return 0;
 }
@@ -1907,13 +1892,13 @@ static int launch_conv64(const ConvArgs& a, int split, wn_stream_t st) {
     const long nblk = balanced_blocks(ntiles);
     if (split) {
         const size_t lds = (size_t)a.nchunks * 2 * 6144;
-        if (lds > 160 * 1024 || set_lds(k_conv64s<MODE>, lds)) return 1;
+        if (lds > 160 * 1024 || wn_dyn_lds<k_conv64s<MODE>>(lds)) return 1;
         WN_LAUNCH((k_conv64s<MODE>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
         return 0;
     }
     if constexpr (MODE != 2) {  // the aux-partial epilogue exists in the split kernel only
         const size_t lds = (size_t)a.wfloats * sizeof(float);
-        if (set_lds(k_conv64<MODE>, lds)) return 1;
+        if (wn_dyn_lds<k_conv64<MODE>>(lds)) return 1;
         WN_LAUNCH((k_conv64<MODE>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
         return 0;
     }
@@ -2481,7 +2466,7 @@ int wn_fused_bwd_chain(const float* wd_b, const float* dP, const float* dXn, flo
         const size_t lds16 = (size_t)(K * 8 + 4) * 4096;
 #define WN_CHAIN_LAUNCH16(AUXV, KV)                                                                               \
     do {                                                                                                          \
-        if (set_lds(k_chain64s<AUXV, KV, false, true>, lds16)) return 1;                                          \
+        if (wn_dyn_lds<k_chain64s<AUXV, KV, false, true>>(lds16)) return 1;                                       \
         WN_LAUNCH((k_chain64s<AUXV, KV, false, true>), dim3((unsigned)nblk), dim3(WN_FT), lds16, st, a);          \
     } while (0)
         if (aux) {
@@ -2499,7 +2484,7 @@ int wn_fused_bwd_chain(const float* wd_b, const float* dP, const float* dXn, flo
     const size_t lds = (size_t)(K * 8 + (K >= 3 ? 0 : 4)) * 6144;
 #define WN_CHAIN_LAUNCH(AUXV, KV)                                                                       \
     do {                                                                                                \
-        if (set_lds(k_chain64s<AUXV, KV>, lds)) return 1;                                               \
+        if (wn_dyn_lds<k_chain64s<AUXV, KV>>(lds)) return 1;                                            \
         WN_LAUNCH((k_chain64s<AUXV, KV>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);               \
     } while (0)
     if (aux) {

@@ -1003,21 +1003,6 @@ int wn_gemm6_launch(const WnGemm6Args* gp, wn_stream_t st) {
     constexpr int lds = 2 * (3 * WN_G6_BM * 32 + 3 * WN_G6_BN * 32);
     constexpr int lds16 = 2 * (2 * WN_G6_BM * 32 + 2 * WN_G6_BN * 32);
     if (g.f16 && (!g.ovf || g.b_mul == 0.0f)) return 5;
-#ifndef WN_EMU
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm6<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-                hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm6<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-                hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm6<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds16) !=
-                hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm6<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds16) !=
-                hipSuccess)
-            return 3;
-        attr_set = true;
-    }
-#endif
     const bool redo = !g.f16 && g.ovf != nullptr;   // the conditional redo: no work unless an fp16 launch overflowed
     WN_PROF(redo ? "mm_redo_if_overflow" : (g.tag ? g.tag : "gemm6"), redo ? 0.0 : 2.0 * g.M * g.N * (double)g.K * g.nbatch,
             redo ? 0.0 : ((double)g.M * g.K * (g.f16 ? 4.0 : 6.0) + (double)g.K * g.N * 4.0 + (double)g.M * g.N * (g.E ? 8.0 : 4.0)) * g.nbatch, st);
@@ -1026,15 +1011,19 @@ int wn_gemm6_launch(const WnGemm6Args* gp, wn_stream_t st) {
         constexpr int ldsn = 2 * (2 * WN_G6N_BM * 32 + 2 * WN_G6_BN * 32);
         dim3 gridn((unsigned)((g.N + WN_G6_BN - 1) / WN_G6_BN), (unsigned)(g.M / WN_G6N_BM), (unsigned)g.nbatch);
         WN_LAUNCH(k_gemm6n, gridn, dim3(G6_T), ldsn, st, g, xcd_block_order() ? 2 : 0);
-    } else if (g.f16) {
-        if (g.ce_target)
-            WN_LAUNCH((k_gemm6<true, true>), grid, dim3(G6_T), lds16, st, g, xcd_block_order() ? 2 : 0 G6_DBG_ARG(g.tag));
-        else
-            WN_LAUNCH((k_gemm6<false, true>), grid, dim3(G6_T), lds16, st, g, xcd_block_order() ? 2 : 0 G6_DBG_ARG(g.tag));
-    } else if (g.ce_target)
-        WN_LAUNCH(k_gemm6<true>, grid, dim3(G6_T), lds, st, g, xcd_block_order() ? 2 : 0 G6_DBG_ARG(g.tag));
-    else
+    } else if (!g.f16 && !g.ce_target) {
+        if (wn_dyn_lds<k_gemm6<false>>(lds)) return 3;
         WN_LAUNCH(k_gemm6<false>, grid, dim3(G6_T), lds, st, g, xcd_block_order() ? 2 : 0 G6_DBG_ARG(g.tag));
+    } else if (!g.f16) {
+        if (wn_dyn_lds<k_gemm6<true>>(lds)) return 3;
+        WN_LAUNCH(k_gemm6<true>, grid, dim3(G6_T), lds, st, g, xcd_block_order() ? 2 : 0 G6_DBG_ARG(g.tag));
+    } else if (!g.ce_target) {
+        if (wn_dyn_lds<k_gemm6<false, true>>(lds16)) return 3;
+        WN_LAUNCH((k_gemm6<false, true>), grid, dim3(G6_T), lds16, st, g, xcd_block_order() ? 2 : 0 G6_DBG_ARG(g.tag));
+    } else {
+        if (wn_dyn_lds<k_gemm6<true, true>>(lds16)) return 3;
+        WN_LAUNCH((k_gemm6<true, true>), grid, dim3(G6_T), lds16, st, g, xcd_block_order() ? 2 : 0 G6_DBG_ARG(g.tag));
+    }
     return 0;
 }
 
@@ -1810,13 +1799,7 @@ int wn_dw_skipres_launch(const WnDwSkipRes* ap, float f16_mul, int* ovf, wn_stre
             ((double)a.S * a.K + 2.0 * cols * a.K) * 4.0 * a.nbatch, st);
     dim3 grid((unsigned)((a.nl + 1) / 2), (unsigned)(a.S / 256), (unsigned)(a.nbatch * a.ksplit));
     constexpr int lds = 3 * (2 * 256 * 32 + 2 * 2 * 128 * 32);   // three stages of dS, z, dX pieces: 96 KB
-#ifndef WN_EMU
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_dw_skipres8), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return 3;
-        attr_set = true;
-    }
-#endif
+    if (wn_dyn_lds<k_dw_skipres8>(lds)) return 3;
     WN_LAUNCH(k_dw_skipres8, grid, dim3(WN_SR8_T), lds, st, a, xcd_block_order(), f16_mul, ovf);
     return 0;
 }
@@ -1860,33 +1843,15 @@ static int launch_dw(const WnGemmArgs& g, int products, float f16_mul, int* ovf,
               (unsigned)(g.nlayer * g.nbatch * g.ksplit));
     if (f16_mul != 0.0f) {
         constexpr int lds = 2 * (2 * 64 * TM * 32 + 2 * 64 * TN * 32);
-#ifndef WN_EMU
-        static bool attr_set = false;
-        if (lds > 65536 && !attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm6_dw<TM, TN, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return 3;
-            attr_set = true;
-        }
-#endif
+        if (wn_dyn_lds<k_gemm6_dw<TM, TN, 2, true>>(lds)) return 3;
         WN_LAUNCH((k_gemm6_dw<TM, TN, 2, true>), grid, dim3(G6_T), lds, st, g, xcd_block_order(), f16_mul, ovf G6_DBG_ARG(g.tag));
     } else if (products == 3) {
         constexpr int lds = 2 * (2 * 64 * TM * 32 + 2 * 64 * TN * 32);
-#ifndef WN_EMU
-        static bool attr_set = false;
-        if (lds > 65536 && !attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm6_dw<TM, TN, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return 3;
-            attr_set = true;
-        }
-#endif
+        if (wn_dyn_lds<k_gemm6_dw<TM, TN, 2>>(lds)) return 3;
         WN_LAUNCH((k_gemm6_dw<TM, TN, 2>), grid, dim3(G6_T), lds, st, g, xcd_block_order(), 1.0f, static_cast<int*>(nullptr) G6_DBG_ARG(g.tag));
     } else {
         constexpr int lds = 2 * (3 * 64 * TM * 32 + 3 * 64 * TN * 32);
-#ifndef WN_EMU
-        static bool attr_set = false;
-        if (lds > 65536 && !attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm6_dw<TM, TN, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return 3;
-            attr_set = true;
-        }
-#endif
+        if (wn_dyn_lds<k_gemm6_dw<TM, TN, 3>>(lds)) return 3;
         WN_LAUNCH((k_gemm6_dw<TM, TN, 3>), grid, dim3(G6_T), lds, st, g, xcd_block_order(), 1.0f, ovf G6_DBG_ARG(g.tag));
     }
     return 0;

@@ -61,3 +61,24 @@ def test_cfg2_workspace_is_sane():
     nbytes = lib.wn_workspace_bytes(ctypes.byref(cfg), 8, 23040)
     assert 4e9 < nbytes < 40e9  # a few GB of the 288 GB HBM3E
     assert lib.wn_workspace_bytes(ctypes.byref(cfg), 8, 23041) == 0  # T must be a multiple of U
+
+
+def test_emulator_seam_stays_in_its_three_blocks():
+    """The host-emulator build switch is named by one #ifdef / #ifndef line in wn_device.h (the two halves), wn_api.hip (the
+    side-stream runtime) and wn_prof.hip (two implementations of one interface) and nowhere else in the product sources, and
+    the dynamic-LDS limit is raised in one place (wn_dyn_lds of wn_device.h)."""
+    csrc = os.path.join(ROOT, "pytorchwavenetvocoder_amd", "csrc")
+    seam, attr = {}, set()
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h", ".inl")):
+            continue
+        lines = open(os.path.join(csrc, name)).read().splitlines()
+        hits = [ln for ln in lines if re.search(r"WN_EMU(?![A-Za-z0-9_])", ln)]   # (WN_EMU_EXTRA_FLAGS etc. are other names)
+        if hits:
+            seam[name] = hits
+        if any("hipFuncSetAttribute" in ln for ln in lines):
+            attr.add(name)
+    assert sorted(seam) == ["wn_api.hip", "wn_device.h", "wn_prof.hip"], sorted(seam)
+    for name, hits in seam.items():
+        assert len(hits) == 1 and re.match(r"\s*#\s*ifn?def\s+WN_EMU\s*$", hits[0]), (name, hits)
+    assert attr == {"wn_device.h"}, attr
