@@ -386,6 +386,25 @@ static DwPlan dw_plan(int M, int N, int Kdim, int nbatch) {
 // ------------------------------------------------------------------------------------------
 // workspace
 // ------------------------------------------------------------------------------------------
+// What the MODEL can take, whatever the flags and the launch plan of a call.  make_ws carves the workspace from it; make_ctx
+// combines it with the flags of a call into the Route every launch site reads.
+struct Caps {
+    bool fused;      // the fused residual-block kernels (n_resch == 64)
+    bool images;     // ... with their weights as pre-split LDS images (split kernels)
+    bool aux_fused;  // ... leaving the aux-gradient partials behind (upsampling layer with U % 16 == 0)
+    bool chain;      // the one-launch-per-layer backward chain (needs a layer below the head)
+    bool wide;       // any-size path, n_resch % 128 == 0: the five per-layer weight sets of a training step, split once per step
+};
+static Caps model_caps(const Dims& d, bool training) {
+    Caps m;
+    m.fused = wn_fused_supported(d.R, d.K, d.S);
+    m.images = m.fused && wn_fused_image_floats(d.K, d.L, 0) > 0;
+    m.aux_fused = m.fused && d.U >= 16 && d.U % 16 == 0;
+    m.chain = wn_fused_chain_supported(d.R, d.K, d.S) && d.L > 1;
+    m.wide = training && d.R % 128 == 0 && !m.fused;
+    return m;
+}
+
 struct Ws {
     // packed weights
     long wc_f, wd_f, waux_f, cvec, rowsum_aux, wres_f, wskip_f, bskip, w1_f, w2_f, wd_b, one, apk;
@@ -397,12 +416,11 @@ struct Ws {
     long amax_partial, amax_partial_floats;
     long dw_ovf;   // one word (of 64): raised by an fp16-pair weight-gradient launch whose result was not finite (WN_FLAG_DW_F16PAIR)
     long dGp, qp;  // aux-gradient partials of the gate kernel (WN_FLAG_AUX_FUSED); 0 floats when the mode cannot apply
-    long img_fwd16, img16_floats;  // two-piece fp16 images of the fused forward block (WN_FLAG_FUSED_F16PAIR)
-    long img_taps16, img_res16, img_taps16_floats, img_res16_floats;   // ... of the backward chain (WN_FLAG_CHAIN_F16PAIR)
+    // LDS weight images of the fused split kernels, [which]: 0 forward block, 1 chain taps, 2 chain Wres^T (wn_fused.h); img16: the
+    // two-piece fp16 ones (WN_FLAG_FUSED_F16PAIR / WN_FLAG_CHAIN_F16PAIR); *_l: floats per layer (0: not applicable)
+    long img[3], img_l[3], img16[3], img16_l[3];
     long amaxP, amaxP_lfloats;     // max |dP_l| per 32-sample tile, [L][B * ceil(T / 32)]
-    long img_fwd, img_taps, img_res, img_floats;  // pre-split LDS weight images of the fused split kernels (0 floats: not applicable)
     long wskipT_f, dZs;  // chain mode (wn_fused_chain_supported): skip weights as [s][l*R + i], dZs = Wskip^T dSkip (B, L*R, T)
-    long dZs_floats;
     long red_scratch_floats;
     long apk_floats;
     long apk_pre[6];   // the six weight sets of a training step, split ONCE per step (pack_weights): offsets, -1 = none
@@ -412,6 +430,8 @@ struct Ws {
     long front_partial, front_partial_floats;
     long total;
     int F;  // frames (T/U, or T without upsampling)
+    long BRT, BST;  // one (B, n_resch, T) / (B, n_skipch, T) tensor: the layer stride of the saved activations
+    Caps caps;      // what make_ws carved for (model_caps)
 };
 
 static inline long al64(long n) { return (n + 63) / 64 * 64; }
@@ -422,7 +442,8 @@ static int make_ws(const Dims& d, int B, int T, Ws* w, bool training = true) {
     if (T % Ue != 0) return fail(1, "T=%d is not a multiple of upsampling_factor=%d", T, d.U);
     const int F = T / Ue;
     w->F = F;
-    const long BRT = (long)B * d.R * T, BST = (long)B * d.S * T;
+    const long BRT = w->BRT = (long)B * d.R * T, BST = w->BST = (long)B * d.S * T;
+    const Caps m = w->caps = model_caps(d, training);
     long o = 0;
 #define CARVE(field, n) \
     w->field = o;       \
@@ -453,32 +474,20 @@ static int make_ws(const Dims& d, int B, int T, Ws* w, bool training = true) {
     CARVE(dXall, (long)d.L * BRT);  // dL/dx_l of every layer
     CARVE(dG, (long)d.L * B * 2 * d.R * F);
     CARVE(dw_partial, (long)d.L * B * 2 * d.R * Ue);
-    {
-        const bool auxf = wn_fused_supported(d.R, d.K, d.S) && d.U >= 16 && d.U % 16 == 0;
-        CARVE(dGp, auxf ? (long)d.L * B * 2 * d.R * (T / 16) : 0);
-        CARVE(qp, auxf ? (long)d.L * B * T : 0);
+    CARVE(dGp, m.aux_fused ? (long)d.L * B * 2 * d.R * (T / 16) : 0);
+    CARVE(qp, m.aux_fused ? (long)d.L * B * T : 0);
+    for (int i = 0; i < 3; ++i) {
+        w->img_l[i] = m.images ? wn_fused_image_floats(d.K, d.L, i) / d.L : 0;
+        CARVE(img[i], m.images ? wn_fused_image_floats(d.K, d.L, i) : 0);
     }
-    {
-        const bool img = wn_fused_supported(d.R, d.K, d.S) && wn_fused_image_floats(d.K, d.L, 0) > 0;
-        w->img_floats = img ? wn_fused_image_floats(d.K, d.L, 0) : 0;
-        CARVE(img_fwd, w->img_floats);
-        CARVE(img_taps, img ? wn_fused_image_floats(d.K, d.L, 1) : 0);
-        CARVE(img_res, img ? wn_fused_image_floats(d.K, d.L, 2) : 0);
-        w->img16_floats = img ? wn_fused_image16_floats(d.K, d.L, 0) : 0;
-        CARVE(img_fwd16, w->img16_floats);
-        w->img_taps16_floats = img ? wn_fused_image16_floats(d.K, d.L, 1) : 0;
-        CARVE(img_taps16, w->img_taps16_floats);
-        w->img_res16_floats = img ? wn_fused_image16_floats(d.K, d.L, 2) : 0;
-        CARVE(img_res16, w->img_res16_floats);
-        w->amaxP_lfloats = img ? al64((long)B * ((T + 31) / 32)) : 0;
-        CARVE(amaxP, w->amaxP_lfloats * d.L);
+    for (int i = 0; i < 3; ++i) {
+        w->img16_l[i] = m.images ? wn_fused_image16_floats(d.K, d.L, i) / d.L : 0;
+        CARVE(img16[i], m.images ? wn_fused_image16_floats(d.K, d.L, i) : 0);
     }
-    {
-        const bool chain = wn_fused_chain_supported(d.R, d.K, d.S) && d.L > 1;
-        w->dZs_floats = chain ? (long)B * d.L * d.R * T : 0;
-        CARVE(wskipT_f, chain ? (long)d.S * d.L * d.R : 0);
-        CARVE(dZs, w->dZs_floats);
-    }
+    w->amaxP_lfloats = m.images ? al64((long)B * ((T + 31) / 32)) : 0;
+    CARVE(amaxP, w->amaxP_lfloats * d.L);
+    CARVE(wskipT_f, m.chain ? (long)d.S * d.L * d.R : 0);
+    CARVE(dZs, m.chain ? (long)B * d.L * d.R * T : 0);
     CARVE(dc, (long)d.L * 2 * d.R);
     CARVE(tmpS, d.S > d.Qo ? d.S : d.Qo);
     // partial buffers: max over the dW GEMMs issued by wn_backward
@@ -534,7 +543,7 @@ static int make_ws(const Dims& d, int B, int T, Ws* w, bool training = true) {
         const int pre[6][2] = {{d.S, d.L * d.R}, {d.S, d.S}, {d.Qo, d.S}, {d.S, d.Qo}, {d.S, d.S}, {d.L * d.R, d.S}};
         for (int i = 0; i < 6; ++i) {
             w->apk_pre[i] = -1;
-            if (pre[i][0] < 128 || (i == 5 && w->dZs_floats <= 0)) continue;   // (the split contraction wants M >= 128)
+            if (pre[i][0] < 128 || (i == 5 && !m.chain)) continue;   // (the split contraction wants M >= 128)
             w->apk_pre[i] = o;
             o += al64((wn_gemm6_apk_elems(pre[i][0], pre[i][1]) + 1) / 2);
         }
@@ -545,23 +554,22 @@ static int make_ws(const Dims& d, int B, int T, Ws* w, bool training = true) {
             o += al64((wn_gemm6_apk_elems(pre[i][0], pre[i][1]) + 1) / 2);
         }
     }
-        {   // (same order as wide_jobs())
-            const bool wide = training && d.R % 128 == 0 && !wn_fused_supported(d.R, d.K, d.S);
-            const int mk[5][2] = {{2 * d.R, d.K * d.R}, {d.R, d.R}, {d.R, d.S}, {d.R, d.R}, {d.R, d.K * 2 * d.R}};
-            for (int i = 0; i < 5; ++i) {
-                w->apk_wide[i] = -1;
-                w->apk_wide_l[i] = al64((wn_gemm6_apk_elems(mk[i][0], mk[i][1]) + 1) / 2);
-                if (!wide) continue;
-                w->apk_wide[i] = o;
-                o += w->apk_wide_l[i] * d.L;
-            }
-            for (int i = 0; i < 5; ++i) {
-                w->apk_wide16[i] = -1;
-                if (!wide) continue;
-                w->apk_wide16[i] = o;
-                o += w->apk_wide_l[i] * d.L;
-            }
+    {   // (same order as wide_jobs())
+        const int mk[5][2] = {{2 * d.R, d.K * d.R}, {d.R, d.R}, {d.R, d.S}, {d.R, d.R}, {d.R, d.K * 2 * d.R}};
+        for (int i = 0; i < 5; ++i) {
+            w->apk_wide[i] = -1;
+            w->apk_wide_l[i] = al64((wn_gemm6_apk_elems(mk[i][0], mk[i][1]) + 1) / 2);
+            if (!m.wide) continue;
+            w->apk_wide[i] = o;
+            o += w->apk_wide_l[i] * d.L;
         }
+        for (int i = 0; i < 5; ++i) {
+            w->apk_wide16[i] = -1;
+            if (!m.wide) continue;
+            w->apk_wide16[i] = o;
+            o += w->apk_wide_l[i] * d.L;
+        }
+    }
 #undef CARVE
     w->total = o;
     return 0;
@@ -584,24 +592,41 @@ extern "C" int wn_workspace_region(const WnConfig* cfg, int B, int T, int kind, 
     Ws w;
     WN_TRY(make_ws(d, B, T, &w));
     if (!offset_floats || !n_floats) return fail(1, "NULL argument");
-    const long BRT = (long)B * d.R * T, BST = (long)B * d.S * T;
     long off, n;
     switch (kind) {
-        case WN_WS_X: off = w.X; n = (long)d.L * BRT; break;
-        case WN_WS_SIGMOID: off = w.Sg; n = (long)d.L * BRT; break;
-        case WN_WS_TANH: off = w.Gt; n = (long)d.L * BRT; break;
-        case WN_WS_Z: off = w.Z; n = (long)d.L * BRT; break;
-        case WN_WS_RELU_SKIP: off = w.O1; n = BST; break;
-        case WN_WS_RELU_POST1: off = w.O2; n = BST; break;
-        case WN_WS_DSKIP: off = w.dSk; n = BST; break;
-        case WN_WS_DP: off = w.P; n = (long)d.L * 2 * BRT; break;
-        case WN_WS_DX: off = w.dXall; n = (long)d.L * BRT; break;
+        case WN_WS_X: off = w.X; n = d.L * w.BRT; break;
+        case WN_WS_SIGMOID: off = w.Sg; n = d.L * w.BRT; break;
+        case WN_WS_TANH: off = w.Gt; n = d.L * w.BRT; break;
+        case WN_WS_Z: off = w.Z; n = d.L * w.BRT; break;
+        case WN_WS_RELU_SKIP: off = w.O1; n = w.BST; break;
+        case WN_WS_RELU_POST1: off = w.O2; n = w.BST; break;
+        case WN_WS_DSKIP: off = w.dSk; n = w.BST; break;
+        case WN_WS_DP: off = w.P; n = d.L * 2 * w.BRT; break;
+        case WN_WS_DX: off = w.dXall; n = d.L * w.BRT; break;
         default: return fail(1, "unknown workspace region %d", kind);
     }
     *offset_floats = off;
     *n_floats = n;
     return 0;
 }
+
+// The kernels a call takes: what the model can take (Caps) AND the flags of the call, decided ONCE in make_ctx.  The call-level
+// decisions that also depend on the launch plan (skipres / fuse / fmax of backward_impl) read these fields.
+struct Route {
+    bool fused;       // the fused 64-channel residual-block kernels (no WN_FLAG_NO_FUSED)
+    bool split_bf16;  // forward-type contractions on the bf16 matrix cores (3-way split, fp32-equivalent; no WN_FLAG_EXACT_MFMA)
+    bool images;      // the fused split kernels take their weights from the LDS images pack_weights builds
+    bool fused_f16;   // WN_FLAG_FUSED_F16PAIR: the fused forward block on the fp16 pair split (block-scaled, k_resblock_fwd_h)
+    bool chain_f16;   // WN_FLAG_CHAIN_F16PAIR: the backward chain kernel on the block-scaled fp16 pair split (k_chain64s<.., H16>)
+    bool mm_f16;      // WN_FLAG_MM_F16PAIR: the forward / data-gradient split contractions (k_gemm6) take the fp16 pair split as well,
+                      // each followed by its conditional six-product redo
+    bool chain;       // backward: one launch per layer computes dX_l AND dP_{l-1} (default for the fused split kernels).
+                      // WN_FLAG_NO_CHAIN: the former gate' / dX pair, where its gate' kernel holds the layer's skip weights
+                      // (n_skipch <= 352); ignored beyond
+    bool aux_fused;   // WN_FLAG_AUX_FUSED: the gate' kernel leaves the partial sums of the aux-path gradients behind, dP is not
+                      // re-read for them
+    bool wide;        // the per-layer weight sets of a wide model are split once per step (wide_jobs)
+};
 
 struct Ctx {
     const WnConfig* cfg;
@@ -611,20 +636,50 @@ struct Ctx {
     int B, T;
     float* ws;
     wn_stream_t st;
-    bool fused;
-    bool split_bf16;  // forward-type contractions on the bf16 matrix cores (3-way split, fp32-equivalent)
+    Route r;
     int dw_products;  // products per multiply of the weight-gradient contractions: 6, or 3 with WN_FLAG_DW_3PRODUCT
-    bool chain_f16;   // WN_FLAG_CHAIN_F16PAIR: the backward chain kernel on the block-scaled fp16 pair split (k_chain64s<.., H16>)
-    bool fused_f16;   // WN_FLAG_FUSED_F16PAIR: the fused 64-channel forward block on the fp16 pair split (block-scaled, k_resblock_fwd_h)
-    bool mm_f16;      // WN_FLAG_MM_F16PAIR: the forward / data-gradient split contractions (k_gemm6) take the fp16 pair split as well, each
-                      // followed by its conditional six-product redo
     int dw_f16_mode;  // WN_FLAG_DW_F16PAIR / WN_FLAG_MM_F16PAIR: 0 off; 1 the caller's exponent (| WN_FLAG_DW_F16_EXP_VALID); 2 max |dlogits| as the loss call of
                       // this workspace measured it (| WN_FLAG_DW_F16_AMAX_WS); 3 measured by a scan of the dlogits given to wn_backward
     float dw_f16_mul; // != 0 (WN_FLAG_DW_F16PAIR): weight gradients by the fp16 pair split; -1: the gradient operand times the power of two
                       // wn_dw_prepare leaves in the workspace (every mode: one code path);
     int* dw_ovf;      // their overflow word (workspace): a raised word makes the six-product launch behind each of them do the work
     const float* params;   // set by the training entry points: lets fw_gemm recognise the pre-split weight sets
-    bool have_pre;         // apk_pre[] of this workspace is valid (regular layout, not the decode state)
+
+    // ---- per-layer tensors: every layer stride of the workspace and of the flat parameters is written here, once ----
+    float* at(long off, int l, long lstride) const { return ws + off + l * lstride; }
+    float* X(int l) const { return at(w.X, l, w.BRT); }
+    float* Sg(int l) const { return at(w.Sg, l, w.BRT); }
+    float* Gt(int l) const { return at(w.Gt, l, w.BRT); }
+    float* Z(int l) const { return at(w.Z, l, w.BRT); }
+    float* dX(int l) const { return at(w.dXall, l, w.BRT); }
+    long P_L() const { return 2 * w.BRT; }
+    float* P(int l) const { return at(w.P, l, P_L()); }
+    long G_B() const { return (long)d.L * 2 * d.R * w.F; }   // G (B, L*2R, F): batch stride; layer l = rows [l*2R, (l+1)*2R)
+    float* G(int l) const { return at(w.G, l, (long)2 * d.R * w.F); }
+    long dG_L() const { return (long)B * 2 * d.R * w.F; }
+    float* dG(int l) const { return at(w.dG, l, dG_L()); }
+    float* dw_partial(int l) const { return at(w.dw_partial, l, (long)B * 2 * d.R * (d.U > 0 ? d.U : 1)); }
+    long dGp_L() const { return (long)B * 2 * d.R * (T / 16); }
+    float* dGp(int l) const { return at(w.dGp, l, dGp_L()); }
+    long qp_L() const { return (long)B * T; }
+    float* qp(int l) const { return at(w.qp, l, qp_L()); }
+    float* cvec(int l) const { return at(w.cvec, l, 2 * d.R); }
+    float* dc(int l) const { return at(w.dc, l, 2 * d.R); }
+    float* amaxP(int l) const { return at(w.amaxP, l, w.amaxP_lfloats); }
+    // LDS weight image `which` (Ws::img) of layer l, two-piece fp16 or split bf16; NULL: the kernels build their own
+    const float* img(int which, int l, bool f16) const {
+        if (!r.images) return nullptr;
+        return f16 ? at(w.img16[which], l, w.img16_l[which]) : at(w.img[which], l, w.img_l[which]);
+    }
+    long wd_L() const { return (long)d.K * 2 * d.R * d.R; }   // wd_f [l][(tap*R + i)*2R + o'] and wd_b [l][(tap*2R + o')*R + i]
+    float* wd_f(int l) const { return at(w.wd_f, l, wd_L()); }
+    float* wd_b(int l) const { return at(w.wd_b, l, wd_L()); }
+    float* wres_f(int l) const { return at(w.wres_f, l, (long)d.R * d.R); }
+    float* wskip_f(int l) const { return at(w.wskip_f, l, (long)d.R * d.S); }
+    long dZs_B() const { return (long)d.L * d.R * T; }   // dZs (B, L*R, T): batch stride; layer l = rows [l*R, (l+1)*R)
+    float* dZs(int l) const { return at(w.dZs, l, (long)d.R * T); }
+    long p_layer(int l) const { return layer_base(y, d, l); }   // flat parameters: block of layer l (+ Lay::o_*), its skip_1x1
+    long p_skip(int l) const { return y.skip0 + l * y.ls_skip; }
 };
 
 static int make_ctx(Ctx* c, const WnConfig* cfg, int B, int T, void* ws, size_t ws_bytes, int flags, void* stream) {
@@ -639,17 +694,22 @@ static int make_ctx(Ctx* c, const WnConfig* cfg, int B, int T, void* ws, size_t 
     c->T = T;
     c->ws = (float*)ws;
     c->st = (wn_stream_t)stream;
-    c->fused = wn_fused_supported(c->d.R, c->d.K, c->d.S) && !(flags & WN_FLAG_NO_FUSED);
-    c->split_bf16 = !(flags & WN_FLAG_EXACT_MFMA);
+    const Caps& m = c->w.caps;
+    Route& r = c->r;
+    r.fused = m.fused && !(flags & WN_FLAG_NO_FUSED);
+    r.split_bf16 = !(flags & WN_FLAG_EXACT_MFMA);
+    r.images = r.fused && r.split_bf16 && m.images;
+    r.fused_f16 = r.images && (flags & WN_FLAG_FUSED_F16PAIR);
+    r.chain_f16 = r.images && (flags & WN_FLAG_CHAIN_F16PAIR);
+    r.mm_f16 = r.split_bf16 && (flags & WN_FLAG_MM_F16PAIR);
+    r.chain = r.fused && r.split_bf16 && m.chain && !((flags & WN_FLAG_NO_CHAIN) && wn_fused_gate_split_supported(c->d.S));
+    r.aux_fused = r.fused && r.split_bf16 && m.aux_fused && (flags & WN_FLAG_AUX_FUSED);
+    r.wide = r.split_bf16 && m.wide;
     c->dw_products = (flags & WN_FLAG_DW_3PRODUCT) ? 3 : 6;
-    c->mm_f16 = c->split_bf16 && (flags & WN_FLAG_MM_F16PAIR);
-    c->fused_f16 = c->fused && c->split_bf16 && (flags & WN_FLAG_FUSED_F16PAIR) && c->w.img16_floats > 0;
-    c->chain_f16 = c->fused && c->split_bf16 && (flags & WN_FLAG_CHAIN_F16PAIR) && c->w.img_taps16_floats > 0;
-    c->dw_f16_mode = !((flags & WN_FLAG_DW_F16PAIR) || c->mm_f16) ? 0 : (flags & WN_FLAG_DW_F16_EXP_VALID) ? 1 : (flags & WN_FLAG_DW_F16_AMAX_WS) ? 2 : 3;
+    c->dw_f16_mode = !((flags & WN_FLAG_DW_F16PAIR) || r.mm_f16) ? 0 : (flags & WN_FLAG_DW_F16_EXP_VALID) ? 1 : (flags & WN_FLAG_DW_F16_AMAX_WS) ? 2 : 3;
     c->dw_f16_mul = (flags & WN_FLAG_DW_F16PAIR) ? -1.0f : 0.0f;
     c->dw_ovf = reinterpret_cast<int*>(c->ws + c->w.dw_ovf);
     c->params = nullptr;
-    c->have_pre = true;
     return 0;
 }
 
@@ -668,7 +728,6 @@ struct GateEpi {   // optional gate epilogue of a split contraction (wn_gemm6.h)
     const float *bw_S = nullptr, *bw_Gt = nullptr;
     float* bw_dP = nullptr;
 };
-static int dzs_layers(const Dims& d) { return d.L; }   // layers bwd_dz_skip_all contracts (all: the head of the chain takes its rows)
 
 // The weight sets of the split contractions every training step launches: (A, lda, M, K) and where their split form lives.
 // They are split ONCE per step by one launch at the end of pack_weights (six dependent little launches in front of the
@@ -684,9 +743,9 @@ static int pre_jobs(const Ctx& c, const float* params, PreJob (&j)[6]) {
                            {ws + w.w2_f, d.Qo, d.Qo, d.S, w.apk_pre[2], w.apk_pre16[2]},
                            {params ? params + y.post2_w : nullptr, d.S, d.S, d.Qo, w.apk_pre[3], w.apk_pre16[3]},
                            {params ? params + y.post1_w : nullptr, d.S, d.S, d.S, w.apk_pre[4], w.apk_pre16[4]},
-                           {ws + w.wskipT_f, (long)d.L * d.R, dzs_layers(d) * d.R, d.S, w.apk_pre[5], w.apk_pre16[5]}};
+                           {ws + w.wskipT_f, (long)d.L * d.R, d.L * d.R, d.S, w.apk_pre[5], w.apk_pre16[5]}};
     int n = 0;
-    if (!c.have_pre || !c.split_bf16) return 0;
+    if (!c.r.split_bf16) return 0;
     for (int i = 0; i < 6; ++i)
         if (all[i].A && all[i].off >= 0) j[n++] = all[i];
     return n;
@@ -699,7 +758,7 @@ static int wide_jobs(const Ctx& c, const float* params, WideJob (&j)[5]) {
     const Dims& d = c.d;
     const Lay& y = c.y;
     const Ws& w = c.w;
-    if (!c.have_pre || !c.split_bf16 || c.fused || w.apk_wide[0] < 0 || !params) return 0;
+    if (!c.r.wide || !params) return 0;
     const long lb0 = layer_base(y, d, 0);
     const WideJob all[5] = {
         {c.ws + w.wd_f, (long)d.K * d.R * 2 * d.R, 2 * d.R, 2 * d.R, d.K * d.R, d.R, d.L, w.apk_wide[0], w.apk_wide_l[0], w.apk_wide16[0]},   // fwd_dilated_gate
@@ -736,12 +795,14 @@ static long prepacked_offset(const Ctx& c, const WnGemmArgs& g, int gate_R = 0, 
     return -1;
 }
 
-static bool fw_gemm_split_ok(const Ctx& c, const WnGemmArgs& g) {
-    return c.split_bf16 && g.M >= 128 && !g.a_kmajor && !g.b_kmajor &&
+// "This contraction takes the split kernel": `split` = Route::split_bf16, `apk_floats` = the workspace's buffer for the split weights
+static bool split_ok(bool split, long apk_floats, const WnGemmArgs& g) {
+    return split && g.M >= 128 && !g.a_kmajor && !g.b_kmajor &&
            (g.b_seg_len >= g.K || g.b_seg_len % 16 == 0) && g.ksplit == 1 && g.nlayer == 1 && !g.b_relu &&
            !g.b_index && g.a_zstride == 0 && !g.a_rowsum &&
-           wn_gemm6_apk_elems(g.M, g.K) <= 2 * c.w.apk_floats && (long)g.M * g.ldc * 4 < 0x7ffffff0L;
+           wn_gemm6_apk_elems(g.M, g.K) <= 2 * apk_floats && (long)g.M * g.ldc * 4 < 0x7ffffff0L;
 }
+static bool split_ok(const Ctx& c, const WnGemmArgs& g) { return split_ok(c.r.split_bf16, c.w.apk_floats, g); }
 struct CeEpi {   // softmax cross-entropy as the epilogue of the contraction that produces the logits (wn_gemm6.h)
     const int64_t* target;
     int t_start;
@@ -757,11 +818,7 @@ struct CeEpi {   // softmax cross-entropy as the epilogue of the contraction tha
 // grad_b: the B operand is a back-propagated gradient (fp16 pair mode: scaled by the measured 2^8 / max |dlogits|, wn_dw_prepare)
 static int fw_gemm(const Ctx& c, const WnGemmArgs& g, const GateEpi* ge = nullptr, const CeEpi* ce = nullptr, int n_origin = 0,
                    bool grad_b = false) {
-    const bool ok = c.split_bf16 && g.M >= 128 && !g.a_kmajor && !g.b_kmajor &&
-                    (g.b_seg_len >= g.K || g.b_seg_len % 16 == 0) && g.ksplit == 1 && g.nlayer == 1 && !g.b_relu &&
-                    !g.b_index && g.a_zstride == 0 && !g.a_rowsum &&
-                    wn_gemm6_apk_elems(g.M, g.K) <= 2 * c.w.apk_floats && (long)g.M * g.ldc * 4 < 0x7ffffff0L;
-    if (!ok) return (ge || ce) ? fail(3, "gate / loss epilogue needs the split contraction") : wn_gemm_launch(&g, c.st);
+    if (!split_ok(c, g)) return (ge || ce) ? fail(3, "gate / loss epilogue needs the split contraction") : wn_gemm_launch(&g, c.st);
     unsigned short* apk = reinterpret_cast<unsigned short*>(c.ws + c.w.apk);
     long pre16 = -1;
     const long pre = prepacked_offset(c, g, ge ? ge->gate_R : 0, &pre16);   // (gate' epilogues use the plain packing: gate_R = 0)
@@ -793,7 +850,7 @@ static int fw_gemm(const Ctx& c, const WnGemmArgs& g, const GateEpi* ge = nullpt
     // WN_FLAG_MM_F16PAIR: the fp16 pair split with the conditional six-product redo behind it -- for the weight sets pack_weights
     // split both ways, and only where a redo may simply run again (no C += result, no in-place residual)
     const bool writes_acc = g.accumulate && !(ge && ge->bw_dP);
-    if (c.mm_f16 && c.dw_ovf && pre >= 0 && pre16 >= 0 && !writes_acc && !(g.D && g.D == g.C)) {
+    if (c.r.mm_f16 && c.dw_ovf && pre >= 0 && pre16 >= 0 && !writes_acc && !(g.D && g.D == g.C)) {
         WnGemm6Args h = a;
         h.f16 = 1; h.Apk = reinterpret_cast<unsigned short*>(c.ws + pre16); h.b_mul = grad_b ? -1.0f : 16.0f; h.ovf = c.dw_ovf;   // activations times 2^4: second pieces normal down to 2^-7
         WN_TRY(wn_gemm6_launch(&h, c.st));
@@ -843,7 +900,7 @@ static int pack_weights(const Ctx& c, const float* params) {
     cp.s0 = 0; cp.s1 = 1; cp.s2 = d.R; cp.sl = y.ls_skip;
     cp.d0 = 0; cp.d1 = d.S; cp.d2 = 1; cp.dl = (long)d.R * d.S;
     WN_TRY(wn_copy4_batch_add(&jobs, ws + w.wskip_f, params + y.skip0, &cp));
-    if (w.dZs_floats > 0) {  // wskipT_f[s*(L*R) + l*R + i] = Wskip_l[s][i]: the A operand of dZs = Wskip^T dSkip (all layers)
+    if (w.caps.chain) {  // (whatever the flags: wn_backward takes its own)  wskipT_f[s*(L*R) + l*R + i] = Wskip_l[s][i]: the A operand of dZs = Wskip^T dSkip (all layers)
         cp.n0 = 1; cp.n1 = d.S; cp.n2 = d.R; cp.nl = d.L;
         cp.s0 = 0; cp.s1 = d.R; cp.s2 = 1; cp.sl = y.ls_skip;
         cp.d0 = 0; cp.d1 = (long)d.L * d.R; cp.d2 = 1; cp.dl = d.R;
@@ -857,13 +914,13 @@ static int pack_weights(const Ctx& c, const float* params) {
     cp.n1 = d.S; cp.n2 = d.Qo; cp.s1 = 1; cp.s2 = d.S; cp.d1 = d.Qo; cp.d2 = 1;
     WN_TRY(wn_copy4_batch_add(&jobs, ws + w.w2_f, params + y.post2_w, &cp));
     WN_TRY(wn_copy4_batch(&jobs, c.st));
-    if (c.fused && c.split_bf16 && w.img_floats > 0)   // LDS images of the split kernels: one launch for all layers
-        WN_TRY(wn_fused_pack_images(ws + w.wd_f, ws + w.wres_f, ws + w.wd_b, params, lb0 + y.o_res_w, lstep, ws + w.img_fwd,
-                                    ws + w.img_taps, ws + w.img_res, d.K, d.L, c.st));
-    if (c.fused_f16 || c.chain_f16)
+    if (c.r.images)   // LDS images of the split kernels: one launch for all layers
+        WN_TRY(wn_fused_pack_images(ws + w.wd_f, ws + w.wres_f, ws + w.wd_b, params, lb0 + y.o_res_w, lstep, ws + w.img[0],
+                                    ws + w.img[1], ws + w.img[2], d.K, d.L, c.st));
+    if (c.r.fused_f16 || c.r.chain_f16)
         WN_TRY(wn_fused_pack_images16(ws + w.wd_f, ws + w.wres_f, ws + w.wd_b, params, lb0 + y.o_res_w, lstep,
-                                      c.fused_f16 ? ws + w.img_fwd16 : nullptr, c.chain_f16 ? ws + w.img_taps16 : nullptr,
-                                      ws + w.img_res16, d.K, d.L, c.st));
+                                      c.r.fused_f16 ? ws + w.img16[0] : nullptr, c.r.chain_f16 ? ws + w.img16[1] : nullptr,
+                                      ws + w.img16[2], d.K, d.L, c.st));
     // cvec / rowsum_aux / bskip / one
     WnCvecArgs ca;
     ca.params = params;
@@ -882,36 +939,26 @@ static int pack_weights(const Ctx& c, const float* params) {
         const int n = pre_jobs(c, params, pj);
         WideJob wj[5];
         const int nw = wide_jobs(c, c.params, wj);   // (only the training entry points declare their params: the look-up side needs them)
-        if (n + nw > 0) {
-            WnGemm6PackJobs jobs;
-            jobs.njobs = n + nw;
-            for (int i = 0; i < n; ++i) {
-                jobs.src[i] = pj[i].A; jobs.lda[i] = pj[i].lda; jobs.M[i] = pj[i].M; jobs.K[i] = pj[i].K;
-                jobs.dst[i] = reinterpret_cast<unsigned short*>(ws + pj[i].off);
-                wn_gemm6_pack_job_single(&jobs, i);
-            }
-            int nj = n + nw;
-            for (int i = 0; i < nw; ++i) {   // every layer of a wide model's five per-layer sets: one launch instead of 5 L - 1
-                const int q = n + i;
-                jobs.src[q] = wj[i].A; jobs.lda[q] = wj[i].lda; jobs.M[q] = wj[i].M; jobs.K[q] = wj[i].K;
-                jobs.dst[q] = reinterpret_cast<unsigned short*>(ws + wj[i].off);
-                jobs.nl[q] = wj[i].nl; jobs.src_lstride[q] = wj[i].lstride; jobs.dst_lstride[q] = 2 * wj[i].off_l;
-                jobs.gate_R[q] = wj[i].gate_R; jobs.f16[q] = 0;
-            }
-            if (c.mm_f16) {   // ... and as two-piece fp16 images (the bf16 ones stay: the redo launches contract with them)
-                for (int q = 0; q < n + nw; ++q) {
-                    const long o16 = q < n ? pj[q].off16 : wj[q - n].off16;
-                    if (o16 < 0 || nj >= WN_G6_PACK_MAXJOBS) continue;
-                    jobs.src[nj] = jobs.src[q]; jobs.lda[nj] = jobs.lda[q]; jobs.M[nj] = jobs.M[q]; jobs.K[nj] = jobs.K[q];
-                    jobs.nl[nj] = jobs.nl[q]; jobs.src_lstride[nj] = jobs.src_lstride[q]; jobs.dst_lstride[nj] = jobs.dst_lstride[q];
-                    jobs.gate_R[nj] = jobs.gate_R[q]; jobs.f16[nj] = 1;
-                    jobs.dst[nj] = reinterpret_cast<unsigned short*>(ws + o16);
-                    ++nj;
-                }
-            }
-            jobs.njobs = nj;
-            WN_TRY(wn_gemm6_pack_batch(&jobs, c.st));
+        WnGemm6PackJobs jobs;
+        jobs.njobs = 0;
+        auto add = [&](const float* A, long lda, int M, int K, int nl, long src_lstride, long dst_lstride, int gate_R, long dst, int f16) {
+            const int q = jobs.njobs;
+            if (dst < 0 || q >= WN_G6_PACK_MAXJOBS) return;
+            jobs.src[q] = A; jobs.lda[q] = lda; jobs.M[q] = M; jobs.K[q] = K;
+            jobs.nl[q] = nl; jobs.src_lstride[q] = src_lstride; jobs.dst_lstride[q] = dst_lstride;
+            jobs.gate_R[q] = gate_R; jobs.f16[q] = f16;
+            jobs.dst[q] = reinterpret_cast<unsigned short*>(ws + dst);
+            jobs.njobs = q + 1;
+        };
+        // bf16 pieces of every set first, then (WN_FLAG_MM_F16PAIR) the two-piece fp16 images of the sets that have one -- the bf16
+        // ones stay: the redo launches contract with them.  A wide model's per-layer sets: all layers by one job each.
+        for (int f16 = 0; f16 <= (c.r.mm_f16 ? 1 : 0); ++f16) {
+            for (int i = 0; i < n; ++i) add(pj[i].A, pj[i].lda, pj[i].M, pj[i].K, 1, 0, 0, 0, f16 ? pj[i].off16 : pj[i].off, f16);
+            for (int i = 0; i < nw; ++i)
+                add(wj[i].A, wj[i].lda, wj[i].M, wj[i].K, wj[i].nl, wj[i].lstride, 2 * wj[i].off_l, wj[i].gate_R,
+                    f16 ? wj[i].off16 : wj[i].off, f16);
         }
+        if (jobs.njobs > 0) WN_TRY(wn_gemm6_pack_batch(&jobs, c.st));
     }
     return rt_check("pack_weights");
 }
@@ -927,12 +974,11 @@ static int skip_sum(const Ctx& c, int lo, int hi, bool last, int t0 = 0) {   // 
     const Dims& d = c.d;
     const Ws& w = c.w;
     float* ws = c.ws;
-    const long BRT = (long)c.B * d.R * c.T;
     WnGemmArgs g = wn_gemm_default();
     g.M = d.S; g.N = c.T - t0; g.K = (hi - lo) * d.R;
-    g.A = ws + w.wskip_f + (long)lo * d.R * d.S; g.lda = d.S;
-    g.B = ws + w.Z + (long)lo * BRT + t0; g.ldb = c.T; g.b_zstride = (long)d.R * c.T; g.b_clen = c.T - t0;
-    g.b_seg_len = d.R; g.b_seg_stride = BRT;
+    g.A = c.wskip_f(lo); g.lda = d.S;
+    g.B = c.Z(lo) + t0; g.ldb = c.T; g.b_zstride = (long)d.R * c.T; g.b_clen = c.T - t0;
+    g.b_seg_len = d.R; g.b_seg_stride = w.BRT;
     g.C = ws + w.O1 + t0; g.ldc = c.T; g.c_zstride = (long)d.S * c.T;
     if (lo == 0) g.bias = ws + w.bskip;
     else { g.D = ws + w.O1 + t0; g.ldd = c.T; g.d_zstride = (long)d.S * c.T; }  // in place: an element is read by the lane that writes it
@@ -950,7 +996,6 @@ static int forward_stack(const Ctx& c, const float* params, const int64_t* x, co
     const Ws& w = c.w;
     float* ws = c.ws;
     const int F = w.F, Ue = d.U > 0 ? d.U : 1;
-    const long BRT = (long)B * d.R * T;
 
     WN_TRY(pack_weights(c, params));
     // [0] the overflow word of the fp16 pair launches of this pass; [1] a_mul; [2] max |dlogits| of the last loss call: a new forward
@@ -965,29 +1010,23 @@ static int forward_stack(const Ctx& c, const float* params, const int64_t* x, co
         g.M = d.L * 2 * d.R; g.N = F; g.K = d.A;
         g.A = ws + w.waux_f; g.lda = (long)d.L * 2 * d.R;
         g.B = h; g.ldb = F; g.b_zstride = (long)d.A * F; g.b_clen = F;
-        g.C = ws + w.G; g.ldc = F; g.c_zstride = (long)d.L * 2 * d.R * F;
+        g.C = ws + w.G; g.ldc = F; g.c_zstride = c.G_B();
         g.nbatch = B; g.tag = "fwd_aux_frames";
         WN_TRY(wn_gemm_launch(&g, c.st));
     }
     const float* upw = d.U > 0 ? params + y.up_w : ws + w.one;
-    const long g_bstride = (long)d.L * 2 * d.R * F;
     for (int l = 0; l < d.L; ++l) {
         const int dil = dilation_of(cfg, l);
-        const float* Xl = ws + w.X + (long)l * BRT;
-        float* Xn = (l + 1 < d.L) ? ws + w.X + (long)(l + 1) * BRT : nullptr;
-        const float* Gl = ws + w.G + (long)l * 2 * d.R * F;
-        float* Sl = ws + w.Sg + (long)l * BRT;
-        float* Gtl = ws + w.Gt + (long)l * BRT;
-        float* Zl = ws + w.Z + (long)l * BRT;
-        const long lb = layer_base(y, d, l);
-        if (c.fused) {
-            WN_TRY(wn_fused_resblock_fwd(ws + w.wd_f + (long)l * d.K * d.R * 2 * d.R, ws + w.wres_f + (long)l * d.R * d.R,
-                                         ws + w.cvec + (long)l * 2 * d.R, params + lb + y.o_res_b, Xl, Gl, g_bstride, upw, Xn,
+        const float* Xl = c.X(l);
+        float* Xn = (l + 1 < d.L) ? c.X(l + 1) : nullptr;
+        const float* Gl = c.G(l);
+        float *Sl = c.Sg(l), *Gtl = c.Gt(l), *Zl = c.Z(l);
+        const float* res_b = params + c.p_layer(l) + y.o_res_b;
+        if (c.r.fused) {
+            WN_TRY(wn_fused_resblock_fwd(c.wd_f(l), c.wres_f(l), c.cvec(l), res_b, Xl, Gl, c.G_B(), upw, Xn,
                                          Sl, /*tanh half: not saved, backward rebuilds it as z / s*/ nullptr, Zl, B, T,
-                                         d.K, dil, Ue, F,
-                                         c.fused_f16 ? 2 : (c.split_bf16 ? 1 : 0),
-                                         c.fused_f16 ? ws + w.img_fwd16 + (long)l * (w.img16_floats / d.L)
-                                                     : ((w.img_floats > 0) ? ws + w.img_fwd + (long)l * (w.img_floats / d.L) : nullptr), c.st));
+                                         d.K, dil, Ue, F, c.r.fused_f16 ? 2 : (c.r.split_bf16 ? 1 : 0), c.img(0, l, c.r.fused_f16),
+                                         c.st));
             if (side && (l + 1) % chunk == 0 && l + 1 < d.L) {
                 WN_TRY(side_link(side, c.st, cs->st));  // z of layers [*skip_done, l] is enqueued
                 WN_TRY(skip_sum(*cs, *skip_done, l + 1, false));
@@ -997,33 +1036,32 @@ static int forward_stack(const Ctx& c, const float* params, const int64_t* x, co
             // P = sum_tap W_tap . x[t-(K-1-tap)d]            (wavenet.py:527-528)
             WnGemmArgs g = wn_gemm_default();
             g.M = 2 * d.R; g.N = T; g.K = d.K * d.R;
-            g.A = ws + w.wd_f + (long)l * d.K * d.R * 2 * d.R; g.lda = 2 * d.R;
+            g.A = c.wd_f(l); g.lda = 2 * d.R;
             g.B = Xl; g.ldb = T; g.b_zstride = (long)d.R * T; g.b_clen = T;
             g.b_seg_len = d.R; g.b_seg_stride = 0; g.b_shift0 = (d.K - 1) * dil; g.b_shift_step = -dil;
             g.C = ws + w.P; g.ldc = T; g.c_zstride = (long)2 * d.R * T;
             g.nbatch = B; g.tag = "fwd_dilated_layered";
-            if (d.R % 128 == 0 && fw_gemm_split_ok(c, g)) {
+            if (d.R % 128 == 0 && split_ok(c, g)) {
                 // wide models: the gate is the epilogue of the contraction (sigmoid / tanh rows paired by the weight
                 // packing), the 2R pre-activations never go to memory                  (wavenet.py:527-532)
                 GateEpi ge;
-                ge.gate_R = d.R; ge.S = Sl; ge.Gt = Gtl; ge.Z = Zl; ge.G = Gl; ge.g_bstride = g_bstride; ge.F = F; ge.U = Ue;
-                ge.upw = upw; ge.cvec = ws + w.cvec + (long)l * 2 * d.R;
+                ge.gate_R = d.R; ge.S = Sl; ge.Gt = Gtl; ge.Z = Zl; ge.G = Gl; ge.g_bstride = c.G_B(); ge.F = F; ge.U = Ue;
+                ge.upw = upw; ge.cvec = c.cvec(l);
                 g.tag = "fwd_dilated_gate";
                 WN_TRY(fw_gemm(c, g, &ge));
             } else {
                 WN_TRY(fw_gemm(c, g));
                 // z = sigmoid(.)*tanh(.)                           (wavenet.py:529-532)
-                WN_TRY(wn_gate_fwd(ws + w.P, Gl, g_bstride, upw, ws + w.cvec + (long)l * 2 * d.R, Sl, Gtl, Zl, B, T, d.R, Ue, F,
-                                   c.st));
+                WN_TRY(wn_gate_fwd(ws + w.P, Gl, c.G_B(), upw, c.cvec(l), Sl, Gtl, Zl, B, T, d.R, Ue, F, c.st));
             }
             // x_{l+1} = res_1x1(z) + x_l                       (wavenet.py:534-535); dead for the last layer
             if (Xn) {
                 WnGemmArgs r = wn_gemm_default();
                 r.M = d.R; r.N = T; r.K = d.R;
-                r.A = ws + w.wres_f + (long)l * d.R * d.R; r.lda = d.R;
+                r.A = c.wres_f(l); r.lda = d.R;
                 r.B = Zl; r.ldb = T; r.b_zstride = (long)d.R * T; r.b_clen = T;
                 r.C = Xn; r.ldc = T; r.c_zstride = (long)d.R * T;
-                r.bias = params + lb + y.o_res_b;
+                r.bias = res_b;
                 r.D = Xl; r.ldd = T; r.d_zstride = (long)d.R * T;
                 r.nbatch = B; r.tag = "fwd_res_layered";
                 WN_TRY(fw_gemm(c, r));
@@ -1031,6 +1069,17 @@ static int forward_stack(const Ctx& c, const float* params, const int64_t* x, co
         }
     }
     return 0;
+}
+
+// conv_post_2 (wavenet.py:522) over the columns [t0, T): everything but its operands' addresses
+static WnGemmArgs post2_shape(const Dims& d, int B, int T, int t0) {
+    WnGemmArgs g = wn_gemm_default();
+    g.M = d.Qo; g.N = T - t0; g.K = d.S;
+    g.lda = d.Qo;
+    g.ldb = T; g.b_zstride = (long)d.S * T; g.b_clen = T - t0;
+    g.ldc = T; g.c_zstride = (long)d.Qo * T;
+    g.nbatch = B;
+    return g;
 }
 
 // wn_forward, optionally with the softmax cross-entropy as the epilogue of conv_post_2 (`ce`: the logits are not written)
@@ -1041,7 +1090,7 @@ static int forward_impl(const WnConfig* cfg, int B, int T, const float* params, 
     if (!params || !x || !h || (!logits && !ce_in)) return fail(1, "NULL argument");
     c.params = params;
     // overlap mode (opt-in, fused kernels): partial skip-sums run on the internal side stream beside the stack
-    SideLock side((flags & WN_FLAG_FWD_OVERLAP) && c.fused && !wn_prof_is_on(), c.st);
+    SideLock side((flags & WN_FLAG_FWD_OVERLAP) && c.r.fused && !wn_prof_is_on(), c.st);
     Ctx cs = c;
     int skip_done = 0;
     if (side.rt) cs.st = side.rt->st;
@@ -1078,12 +1127,9 @@ static int forward_impl(const WnConfig* cfg, int B, int T, const float* params, 
         WN_TRY(fw_gemm(c, g, nullptr, nullptr, t0));
     }
     {   // conv_post_2  (wavenet.py:522)
-        WnGemmArgs g = wn_gemm_default();
-        g.M = d.Qo; g.N = Tw; g.K = d.S;
-        g.A = ws + w.w2_f; g.lda = d.Qo;
-        g.B = ws + w.O2 + t0; g.ldb = T; g.b_zstride = (long)d.S * T; g.b_clen = Tw;
-        g.C = logits ? logits + t0 : nullptr; g.ldc = T; g.c_zstride = (long)d.Qo * T;
-        g.bias = params + y.post2_b; g.nbatch = B; g.tag = "fwd_post2";
+        WnGemmArgs g = post2_shape(d, B, T, t0);
+        g.A = ws + w.w2_f; g.B = ws + w.O2 + t0; g.C = logits ? logits + t0 : nullptr;
+        g.bias = params + y.post2_b; g.tag = "fwd_post2";
         if (ce_in) {
             CeEpi ce = *ce_in;
             ce.target = ce_in->target + t0;     // column j of the window is position t0 + j (row stride T)
@@ -1114,10 +1160,9 @@ extern "C" int wn_forward_loss_fused(const WnConfig* cfg, int B, int T, int flag
     Dims d;
     Ws w;
     if (check_cfg(cfg, &d) || B < 1 || T < 1 || make_ws(d, B, T, &w)) return 0;
-    const bool split = !(flags & WN_FLAG_EXACT_MFMA);
-    // the conditions under which fw_gemm takes the split contraction for conv_post_2, plus: every class in one 256-row block
-    return (split && d.Qo == d.Q && d.Qo >= 128 && d.Qo <= WN_G6_BM &&
-            wn_gemm6_apk_elems(d.Qo, d.S) <= 2 * w.apk_floats && (long)d.Qo * T * 4 < 0x7ffffff0L) ? 1 : 0;
+    // fw_gemm takes the split contraction for conv_post_2 (no term of the predicate reads the window start), plus: every class in one
+    // 256-row block
+    return (split_ok(!(flags & WN_FLAG_EXACT_MFMA), w.apk_floats, post2_shape(d, B, T, 0)) && d.Qo == d.Q && d.Qo <= WN_G6_BM) ? 1 : 0;
 }
 
 // Divisor of the mean and the argument checks shared by the three ragged loss entry points.  Dense (t_end == NULL): the

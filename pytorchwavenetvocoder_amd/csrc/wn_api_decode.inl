@@ -161,6 +161,10 @@ struct DlLay {
     long dlp_w, dlp_post, dlp_cfold, dlp_fold, dlp_gz, dlp_gx, dlp_gs, dlp_go, dlp_gl, dlp_flags, dlp_pq, dlp_err;
     int dlp_flags_on;        // 1: wn_dlpf.hip (plain vectors + flags) runs this model / batch
     int dlp_grid, dlp_capacity;   // workgroups of the persistent launch the plan asks for / the device keeps resident at once
+    // per-layer vectors of the layer-wise path, RB = n_resch * utterances floats per row block
+    float* xin_l(float* st, int l, int K, long RB) const { return st + xin + l * K * RB; }   // [l][tap][R][nb]
+    float* z_l(float* st, int l, long RB) const { return st + Zcat + l * RB; }
+    float* gstep_l(float* st, int l, long RB) const { return st + gstep + l * 2 * RB; }
 };
 
 // granules (mode bit WN_DECODE_GRANULES): the persistent launches hand their vectors over as 8-byte granules everywhere
@@ -246,19 +250,14 @@ static void dl_ctx(Ctx* c, const WnConfig* cfg, const Dims& d, const DlLay& y, i
     c->T = nb;
     c->ws = state;
     c->st = (wn_stream_t)stream;
-    c->fused = false;
     // exact f32 MFMA here: with a handful of utterance columns the contractions are weight-streaming bound and
     // the split path would re-split (or stream 1.5x the bytes of) the weights on every step
-    c->split_bf16 = false;
+    c->r = Route();   // (nothing of the training routes either: no pre-split weight sets in this state)
     c->dw_products = 6;
     c->dw_f16_mul = 0.0f;
     c->dw_f16_mode = 0;
-    c->mm_f16 = false;
-    c->fused_f16 = false;
-    c->chain_f16 = false;
     c->dw_ovf = nullptr;
     c->params = nullptr;
-    c->have_pre = false;
 }
 
 extern "C" int64_t wn_decode_layered_state_floats(const WnConfig* cfg, int B, int mode) {
@@ -317,8 +316,8 @@ extern "C" int wn_decode_layered_prepare(const WnConfig* cfg, int B, int F, cons
             if (s >= 1 && s < d.L) {   // fold[o'][i] = sum_j Wd_new(s)[o'][j] Wres(s-1)[j][i]
                 WnGemmArgs f = wn_gemm_default();
                 f.M = 2 * d.R; f.N = d.R; f.K = d.R;
-                f.A = state + y.w.wd_f + (long)s * d.K * d.R * 2 * d.R + (long)(d.K - 1) * d.R * 2 * d.R; f.lda = 2 * d.R;
-                f.B = params + layer_base(lay, d, s - 1) + lay.o_res_w; f.ldb = d.R; f.b_clen = d.R;
+                f.A = c.wd_f(s) + (long)(d.K - 1) * d.R * 2 * d.R; f.lda = 2 * d.R;
+                f.B = params + c.p_layer(s - 1) + lay.o_res_w; f.ldb = d.R; f.b_clen = d.R;
                 f.C = state + y.dlp_fold; f.ldc = d.R;
                 f.nbatch = 1; f.tag = "dlp_fold";
                 WN_TRY(wn_gemm_launch(&f, c.st));
@@ -326,10 +325,10 @@ extern "C" int wn_decode_layered_prepare(const WnConfig* cfg, int B, int F, cons
             WnDlpPackArgs pa;
             pa.R = d.R; pa.S = d.S; pa.Qo = d.Qo; pa.L = d.L; pa.K = d.K; pa.plan = y.dlp; pa.stage = s;
             pa.params = params;
-            pa.lb_s = s < d.L ? layer_base(lay, d, s) : 0;
-            pa.lb_prev = s >= 1 ? layer_base(lay, d, s - 1) : 0;
+            pa.lb_s = s < d.L ? c.p_layer(s) : 0;
+            pa.lb_prev = s >= 1 ? c.p_layer(s - 1) : 0;
             pa.o_dsig_w = lay.o_dsig_w; pa.o_dtanh_w = lay.o_dtanh_w; pa.o_res_w = lay.o_res_w;
-            pa.skip_prev = s >= 1 ? lay.skip0 + (long)(s - 1) * lay.ls_skip : 0;
+            pa.skip_prev = s >= 1 ? c.p_skip(s - 1) : 0;
             pa.fold = state + y.dlp_fold;
             pa.dst = state + y.dlp_w + (long)s * y.dlp.NU * y.dlp.stage_floats;
             WN_TRY(wn_dlp_pack_stage(&pa, c.st));
@@ -414,33 +413,32 @@ extern "C" int wn_decode_layered_steps(const WnConfig* cfg, int B, const float* 
         a.p = p;
         WN_TRY(wn_dl_inputs(&a, c.st));
         for (int l = 0; l < d.L; ++l) {
-            const long lb = layer_base(lay, d, l);
-            float* xin_l = ws + y.xin + (long)l * d.K * RB;
-            float* z_l = ws + y.Zcat + (long)l * RB;
+            float* xin_l = y.xin_l(ws, l, d.K, RB);
+            float* z_l = y.z_l(ws, l, RB);
             {   // both rows of the gate: taps [history | newest] x packed dilated weights  (wavenet.py:540-541)
                 WnDlMmArgs g;
                 g.M = 2 * d.R; g.K = d.K * d.R; g.nb = nb;
-                g.A = ws + w.wd_f + (long)l * d.K * d.R * 2 * d.R; g.lda = 2 * d.R; g.a_zstride = 0;
+                g.A = c.wd_f(l); g.lda = 2 * d.R; g.a_zstride = 0;
                 g.B = xin_l; g.ldb = nb; g.b_zstride = 0;
                 g.C = ws + y.P; g.ldc = nb; g.c_zstride = 0;
                 g.bias = nullptr; g.D = nullptr; g.ldd = 0; g.relu = 0; g.nz = 1; g.tag = "dl_dilated";
                 g.gate_R = 0; g.gate_g = nullptr; g.gate_c = nullptr;
                 if (gate_fused) {  // z = sigmoid(.)*tanh(.) in the epilogue (wavenet.py:542-544): one launch less per layer
-                    g.gate_R = d.R; g.gate_g = ws + y.gstep + (long)l * 2 * RB; g.gate_c = ws + w.cvec + (long)l * 2 * d.R;
+                    g.gate_R = d.R; g.gate_g = y.gstep_l(ws, l, RB); g.gate_c = c.cvec(l);
                     g.C = z_l;
                 }
                 WN_TRY(wn_dl_mm(&g, c.st));
             }
             if (!gate_fused)
-                WN_TRY(wn_gate_fwd(ws + y.P, ws + y.gstep + (long)l * 2 * RB, 0, ws + w.one, ws + w.cvec + (long)l * 2 * d.R,
-                                   ws + y.Sg, ws + y.Gt, z_l, 1, nb, d.R, 1, nb, c.st));
+                WN_TRY(wn_gate_fwd(ws + y.P, y.gstep_l(ws, l, RB), 0, ws + w.one, c.cvec(l), ws + y.Sg,
+                                   ws + y.Gt, z_l, 1, nb, d.R, 1, nb, c.st));
             if (l + 1 < d.L) {  // next layer input = res_1x1(z) + x  (wavenet.py:546-548)
                 WnDlMmArgs r;
                 r.M = d.R; r.K = d.R; r.nb = nb;
-                r.A = ws + w.wres_f + (long)l * d.R * d.R; r.lda = d.R; r.a_zstride = 0;
+                r.A = c.wres_f(l); r.lda = d.R; r.a_zstride = 0;
                 r.B = z_l; r.ldb = nb; r.b_zstride = 0;
                 r.C = xin_l + (long)d.K * RB + (long)(d.K - 1) * RB; r.ldc = nb; r.c_zstride = 0;
-                r.bias = params + lb + lay.o_res_b;
+                r.bias = params + c.p_layer(l) + lay.o_res_b;
                 r.D = xin_l + (long)(d.K - 1) * RB; r.ldd = nb;
                 r.relu = 0; r.nz = 1; r.tag = "dl_res";
                 r.gate_R = 0; r.gate_g = nullptr; r.gate_c = nullptr;
@@ -556,7 +554,7 @@ extern "C" int wn_decode_prefill(const WnConfig* cfg, int B, int Tctx, int pos0,
     }
     WN_TRY(forward_stack(c, params, x_ctx, h_ctx));
     // decoding resumes at the last context position pos0 + Tctx-1 (its logits choose the first new sample)
-    WN_TRY(wn_decode_fill_queues(c.ws + c.w.X, qdst, d.L, B, d.R, Tctx, d.K, cfg->dilation_depth, Tctx - 1, pos0, elem_stride,
+    WN_TRY(wn_decode_fill_queues(c.X(0), qdst, d.L, B, d.R, Tctx, d.K, cfg->dilation_depth, Tctx - 1, pos0, elem_stride,
                                  utt_stride, c.st));
     return rt_check("wn_decode_prefill");
 }

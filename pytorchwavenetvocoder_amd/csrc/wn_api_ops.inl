@@ -95,21 +95,12 @@ extern "C" int wn_op_causal_conv_backward(const float* weight, const float* x, c
         g.tag = "op_causal_conv_dw";
         WN_TRY(wn_gemm_launch(&g, st));
         if (dw) {   // dW[o][i][tap] = sum_z partial[z][o][tap*Cin + i]
-            WnReduceArgs r;
-            r.partial = partial; r.nz = nz; r.M = Cout; r.N = N;
-            r.out = dw; r.m_seg = 0x7fffffff; r.n_seg = Cin;
-            r.m_seg_stride = 0; r.m_stride = (long)Cin * K; r.n_seg_stride = 1; r.n_stride = K;
-            r.scale = 1.0f; r.accumulate = 0; r.addend_m = nullptr; r.addend_scale_ptr = nullptr;
-            r.scratch = nullptr; r.scratch_floats = 0; r.nl = 1; r.out_lstride = 0; r.addend_lstride = 0;
+            WnReduceArgs r = reduce_plain(partial, nz, Cout, N, dw, (long)Cin * K, K);
+            r.n_seg = Cin; r.n_seg_stride = 1;
             WN_TRY(wn_reduce(&r, st));
         }
         if (db) {
-            WnReduceArgs q;
-            q.partial = rs_partial; q.nz = nz; q.M = Cout; q.N = 1;
-            q.out = db; q.m_seg = 0x7fffffff; q.n_seg = 0x7fffffff;
-            q.m_seg_stride = 0; q.m_stride = 1; q.n_seg_stride = 0; q.n_stride = 0;
-            q.scale = 1.0f; q.accumulate = 0; q.addend_m = nullptr; q.addend_scale_ptr = nullptr;
-            q.scratch = nullptr; q.scratch_floats = 0; q.nl = 1; q.out_lstride = 0; q.addend_lstride = 0;
+            const WnReduceArgs q = reduce_plain(rs_partial, nz, Cout, 1, db, 1, 0);
             WN_TRY(wn_reduce(&q, st));
         }
     }
