@@ -20,6 +20,10 @@
 // the layer-stacked skip operand (segment = layer).
 //   a_kmajor = 0 : A(m,k) = Az[k*lda + m]     (packed / transposed weights)
 //   a_kmajor = 1 : A(m,k) = Az[m*lda + k]     (k = time; dW type)
+// Epilogue, in this fixed order, acc = the sum over this z's k range:
+//      v = acc + bias[m] + D[m][n];   if (relu) v = max(v, 0);   v = (E[m][n] > 0) ? v : 0;   if (accumulate) v += C_old[m][n]
+// so the mask does not clear what `accumulate` adds.  D and E follow the batch index b; C and a_rowsum follow
+// z = (layer*nbatch + b)*ksplit + ks.  D may be C itself (in place) when accumulate = 0 and z == b.
 typedef struct WnGemmArgs {
     int M, N, K;
     const float* A;

@@ -17,6 +17,14 @@ OUT = os.path.join(HERE, "_build")
 SOURCES = ["wn_gemm.hip", "wn_gemm6.hip", "wn_elem.hip", "wn_fused.hip", "wn_decode.hip", "wn_dlp.hip", "wn_dlpm.hip", "wn_dlpf.hip", "wn_prof.hip", "wn_api.hip"]
 LIB = os.path.join(OUT, "libwavenet_emu.so")
 FLAGS = ["-O2", "-std=c++17", "-fPIC", "-DWN_EMU", "-Wno-psabi", "-mfma", "-ffp-contract=off", "-I", HERE, "-I", CSRC, "-x", "c++"]
+# wn_gemm.hip keeps the 16-byte alignment of its float4 accesses checked (hip_emu.h: WN_EMU_ALIGNED_VEC): a trap, no sanitizer
+# runtime.  A misaligned access ends the process with SIGILL, with no assertion and no test name, in every emulator test that
+# runs this kernel (pytest's fault handler prints the Python traceback of the test; pytest-xdist names the test whose worker
+# crashed).  The tests stay in the pytest process: a forked child deadlocks in the thread pools the parent already started, and
+# a fresh interpreter per case would cost more than the matrix itself.
+# float4 is alignas(16) in that one translation unit only: size and calling convention are the same as elsewhere and no
+# float4 crosses a translation unit here, but it is a one-definition-rule difference to keep in mind.
+SOURCE_FLAGS = {"wn_gemm.hip": ["-DWN_EMU_ALIGNED_VEC", "-fsanitize=alignment", "-fsanitize-undefined-trap-on-error"]}
 # A/B build macros of the kernel sources (e.g. WN_EMU_EXTRA_FLAGS="-DWN_G6_FINE") get their own build directory
 _EXTRA = os.environ.get("WN_EMU_EXTRA_FLAGS", "").split()
 if _EXTRA:
@@ -52,7 +60,7 @@ def _build_locked(force):
     objs, procs = [], []
     for s in SOURCES:
         o = os.path.join(OUT, s.replace(".hip", ".o"))
-        procs.append((s, subprocess.Popen(["g++"] + FLAGS + ["-c", os.path.join(CSRC, s), "-o", o])))
+        procs.append((s, subprocess.Popen(["g++"] + FLAGS[:4] + SOURCE_FLAGS.get(s, []) + FLAGS[4:] + ["-c", os.path.join(CSRC, s), "-o", o])))
         objs.append(o)
     for s, p in procs:
         if p.wait() != 0:

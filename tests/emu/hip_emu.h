@@ -467,7 +467,15 @@ inline unsigned atomicAdd(unsigned* p, unsigned v) {
     return o;
 }
 inline float __frcp_rn(float x) { return 1.0f / x; }
+// HIP's float4 is 16-byte aligned and a 16-byte access through it needs that alignment.  A source built with
+// -DWN_EMU_ALIGNED_VEC (build_emu.py, together with -fsanitize=alignment in trap mode: no runtime library) keeps the
+// requirement on the host: a 16-byte access at an address that is only 4-byte aligned stops the process there instead
+// of returning the right values (x86 does not care; the kernel's eligibility tests for its 16-byte paths would be untested).
+#ifdef WN_EMU_ALIGNED_VEC
+struct alignas(16) float4 {
+#else
 struct float4 {
+#endif
     float x, y, z, w;
 };
 inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
