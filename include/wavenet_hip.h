@@ -166,7 +166,7 @@ enum {
                                * 1x1) on the fp16 pair split as well (three products per multiply instead of six), BLOCK-SCALED: every
                                * weight image and every 64 x 32 operand tile is multiplied by the power of two that puts its maximum
                                * at 2^12 / 2^14, so no magnitude can leave fp16's range and no redo is needed (csrc/wn_fused.hip
-                               * k_resblock_fwd_h).  Forward only: the backward chain keeps six bf16 products. */
+                               * k_resblock_fwd<K, FwdF16x2>).  Forward only: the backward chain keeps six bf16 products. */
 #define WN_FLAG_CHAIN_F16PAIR (1 << 30) /* since ABI v9, opt-in: wn_forward(_loss) packs and wn_backward(_window) uses -- the fused backward data chain
                                * (dX_l from dP_l, gate' of layer l-1) on the block-scaled fp16 pair split (k_chain64s<.., H16>): weight
                                * images by the power of two of their maximum, the dP operand of a tile by the maximum of the producer

@@ -616,7 +616,7 @@ struct Route {
     bool fused;       // the fused 64-channel residual-block kernels (no WN_FLAG_NO_FUSED)
     bool split_bf16;  // forward-type contractions on the bf16 matrix cores (3-way split, fp32-equivalent; no WN_FLAG_EXACT_MFMA)
     bool images;      // the fused split kernels take their weights from the LDS images pack_weights builds
-    bool fused_f16;   // WN_FLAG_FUSED_F16PAIR: the fused forward block on the fp16 pair split (block-scaled, k_resblock_fwd_h)
+    bool fused_f16;   // WN_FLAG_FUSED_F16PAIR: the fused forward block on the fp16 pair split (block-scaled, k_resblock_fwd<K, FwdF16x2>)
     bool chain_f16;   // WN_FLAG_CHAIN_F16PAIR: the backward chain kernel on the block-scaled fp16 pair split (k_chain64s<.., H16>)
     bool mm_f16;      // WN_FLAG_MM_F16PAIR: the forward / data-gradient split contractions (k_gemm6) take the fp16 pair split as well,
                       // each followed by its conditional six-product redo
@@ -1024,9 +1024,8 @@ static int forward_stack(const Ctx& c, const float* params, const int64_t* x, co
         const float* res_b = params + c.p_layer(l) + y.o_res_b;
         if (c.r.fused) {
             WN_TRY(wn_fused_resblock_fwd(c.wd_f(l), c.wres_f(l), c.cvec(l), res_b, Xl, Gl, c.G_B(), upw, Xn,
-                                         Sl, /*tanh half: not saved, backward rebuilds it as z / s*/ nullptr, Zl, B, T,
-                                         d.K, dil, Ue, F, c.r.fused_f16 ? 2 : (c.r.split_bf16 ? 1 : 0), c.img(0, l, c.r.fused_f16),
-                                         c.st));
+                                         Sl, Zl, B, T, d.K, dil, Ue, F, c.r.fused_f16 ? 2 : (c.r.split_bf16 ? 1 : 0),
+                                         c.img(0, l, c.r.fused_f16), c.st));
             if (side && (l + 1) % chunk == 0 && l + 1 < d.L) {
                 WN_TRY(side_link(side, c.st, cs->st));  // z of layers [*skip_done, l] is enqueued
                 WN_TRY(skip_sum(*cs, *skip_done, l + 1, false));

@@ -13,14 +13,14 @@ int wn_fused_supported(int R, int K, int S);
 // wres_f: [i*R + o]               packed (transposed) res_1x1 weight
 int wn_fused_resblock_fwd(const float* wd_f, const float* wres_f, const float* cvec, const float* res_bias,
                           const float* X, const float* G, long g_bstride, const float* upw, float* Xnext, float* S,
-                          float* Gt, float* Z, int B, int T, int K, int dilation, int U, int F, int split, const float* wimg,
+                          float* Z, int B, int T, int K, int dilation, int U, int F, int split, const float* wimg,
                           wn_stream_t st);
 // wimg (split kernels, K <= 2; nullable): this layer's pre-built LDS weight image, see wn_fused_pack_images
 
 // dZ = Wskip^T dSkip (+ Wres^T dXn) ; dP = [dZ*g*s*(1-s) ; dZ*s*(1-g^2)]
 // wskip : natural skip_1x1 weight [S][R] ; wres : natural res_1x1 weight [R][R] ; dXn may be NULL.
 // gt_is_z != 0 (all three gate' launchers): `Gt` holds the saved product z = s * tanh instead of the tanh half, which the
-// fused forward then does not store at all (Gt == NULL there); the kernels rebuild g = z / s (s = sigmoid > 0).
+// fused forward does not store at all; the kernels rebuild g = z / s (s = sigmoid > 0).
 int wn_fused_bwd_gate(const float* wskip, const float* wres, const float* dSk, const float* dXn, const float* S,
                       const float* Gt, int gt_is_z, float* dP, int B, int T, int Sch, int split, wn_stream_t st);
 // 1: the split form of the two launchers (the skip and res weights of a layer resident in LDS as bf16 pieces) holds Sch skip channels
@@ -68,7 +68,7 @@ int wn_fused_bwd_chain_head(const float* dZs, long zs_bstride, const float* S, c
 // wn_fused_image_floats: floats of region `which` for L layers (0 when K is outside the split kernels' range).
 // (img_taps of layer l and img_res of layer l-1 belong to the chain launch of layer l.)
 long wn_fused_image_floats(int K, int L, int which);
-// Two-piece fp16 images of the forward block (k_resblock_fwd_h: `split` = 2 in wn_fused_resblock_fwd, `wimg` = layer l's image):
+// Two-piece fp16 images of the forward block (k_resblock_fwd<K, FwdF16x2>: `split` = 2 in wn_fused_resblock_fwd, `wimg` = layer l's image):
 // [K*4 blocks][2 pieces][128 rows][16 k] taps, [4][2][64][16] res 1x1, block-scaled by powers of two, inverse scales in the tail
 // which = 0 forward block, 1 chain taps, 2 chain Wres^T (k_chain64s<.., H16>); img_taps16 == NULL: the forward image only
 long wn_fused_image16_floats(int K, int L, int which);

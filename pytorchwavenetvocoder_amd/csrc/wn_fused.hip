@@ -23,7 +23,6 @@
 //     waits vmcnt(0) on each, and both waves of a SIMD stall in lock step).
 // The f32-input MFMA is an exact fp32 fma chain, so parity with the fp32 reference is kept.
 #include "wn_fused.h"
-#include <type_traits>
 
 
 #include "wn_prof.h"
@@ -114,9 +113,14 @@ static __device__ __forceinline__ int kappa64(int s, int hi) {
     return 32 * (s >> 4) + ((s & 15) & 3) + 8 * ((s & 15) >> 2) + 4 * hi;
 }
 
+// the per-channel vectors every forward-block kernel keeps behind its weights in the LDS: cvec [128], then the res-1x1 bias [64]
+#define WN_FWD_VEC_FLOATS 192
+// dynamic LDS of k_resblock_fwd_f32, the forward kernel every configuration can fall back to
+static __host__ __device__ constexpr int fwd_f32_lds_bytes(int K) { return (K * 64 * 128 + 64 * 64 + WN_FWD_VEC_FLOATS) * 4; }
+
 int wn_fused_supported(int R, int K, int S) {
     if (R != 64 || K < 1 || K > 3 || S % 32 != 0) return 0;
-    const long fwd = ((long)K * 64 * 128 + 64 * 64 + 192) * 4;
+    const long fwd = fwd_f32_lds_bytes(K);
     const long gate = ((long)S * 64 + 64 * 64) * 4;
     const long dx = ((long)K * 128 * 64) * 4;
     const long lim = 160 * 1024;
@@ -159,6 +163,10 @@ static __device__ __forceinline__ void stage_copy(float* dst, const float* __res
 }
 
 // ---------------------------------------------------------------------------------------------
+// The forward residual block.  Two kernels: k_resblock_fwd<K, Arith> (further down: the split arithmetics on the bf16 / fp16
+// matrix cores) and k_resblock_fwd_f32<K> (the exact f32-input MFMA).  What follows first are the pieces of the software
+// pipeline that know nothing about the arithmetic; both kernels are built from them.
+// ---------------------------------------------------------------------------------------------
 struct FwdArgs {
     const float* wimg;   // split kernels: pre-built LDS weight image of this layer (wn_fused_pack_images) or NULL
     const float* wd_f;
@@ -171,7 +179,6 @@ struct FwdArgs {
     const float* upw;
     float* Xnext;
     float* S;
-    float* Gt;
     float* Z;
     int B, T, dil, U, F;
 #ifdef WN_TIMING
@@ -179,13 +186,8 @@ struct FwdArgs {
 #endif
 };
 
-template <int K>
-__global__ __launch_bounds__(WN_LB) void k_resblock_fwd(FwdArgs a) {
-    WN_DYN_SMEM(smem_raw);
-    float* Wd = reinterpret_cast<float*>(smem_raw);  // [K*64][128]
-    float* Wr = Wd + K * 64 * 128;                   // [64][64]
-    float* cv = Wr + 64 * 64;                        // [128]
-    float* rb = cv + 128;                            // [64]
+// WN_TIMING builds: stamps of the kernel's start, of the end of its staging prologue and of its end
+static __device__ __forceinline__ void fwd_timing_begin(const FwdArgs& a) {
 #ifdef WN_TIMING
     if (a.dbg && blockIdx.x == 0 && (threadIdx.x & 63) == 0) {
         a.dbg[((threadIdx.x >> 6) * 4) * 16 + 5] = (long long)__builtin_readcyclecounter();
@@ -193,219 +195,259 @@ __global__ __launch_bounds__(WN_LB) void k_resblock_fwd(FwdArgs a) {
     }
     if (a.dbg && threadIdx.x == 0) a.dbg[512 + blockIdx.x * 4 + 0] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
-    stage_copy(Wd, a.wd_f, K * 64 * 128);
-    stage_copy(Wr, a.wres_f, 64 * 64);
-    if (threadIdx.x < 128) cv[threadIdx.x] = a.cvec[threadIdx.x];
-    if (threadIdx.x < 64) rb[threadIdx.x] = a.res_bias[threadIdx.x];
-    __syncthreads();
+}
+static __device__ __forceinline__ void fwd_timing_staged(const FwdArgs& a) {
 #ifdef WN_TIMING
     if (a.dbg && blockIdx.x == 0 && (threadIdx.x & 63) == 0)
         a.dbg[((threadIdx.x >> 6) * 4) * 16 + 6] = (long long)__builtin_readcyclecounter();
 #endif
-    // De-phase the two waves that share a SIMD (waves w and w+4): started together they would run
-    // their MFMA phases and their gate/store phases in lock step and leave the matrix pipe idle
-    // during the latter; half a tile of head start makes one wave's VALU/VMEM phase coincide with
-    // the other's MFMA phase.
+}
+static __device__ __forceinline__ void fwd_timing_end(const FwdArgs& a, int tcount) {
+#ifdef WN_TIMING
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (a.dbg && blockIdx.x == 0 && lane == 0) {
+        __builtin_amdgcn_s_waitcnt(0);
+        a.dbg[(wave * 4) * 16 + 8] = (long long)__builtin_amdgcn_s_memrealtime();
+        a.dbg[(wave * 4) * 16 + 9] = (long long)__builtin_readcyclecounter();
+    }
+    if (a.dbg && lane == 0) {
+        __builtin_amdgcn_s_waitcnt(0);
+        if (wave == 0) a.dbg[512 + blockIdx.x * 4 + 1] = (long long)__builtin_amdgcn_s_memrealtime();
+        if (wave == 7) a.dbg[512 + blockIdx.x * 4 + 2] = (long long)__builtin_amdgcn_s_memrealtime();
+        if (wave == 0) a.dbg[512 + blockIdx.x * 4 + 3] = tcount;
+    }
+#endif
+}
+
+// the WN_FWD_VEC_FLOATS per-channel values behind the weights
+static __device__ __forceinline__ void fwd_stage_vectors(float* cv, const FwdArgs& a) {
+    if (threadIdx.x < 128) cv[threadIdx.x] = a.cvec[threadIdx.x];
+    if (threadIdx.x < 64) cv[128 + threadIdx.x] = a.res_bias[threadIdx.x];
+}
+
+// what a lane keeps for the whole launch
+struct FwdLane {
+    int li, hi;              // column of the 32-sample tile; lane half (channels + 4 hi)
+    int T, T4, F4;           // T4, F4: bytes per channel row of an activation / of the frame-rate aux projection
+    int tiles_per_b, ntiles;
+    unsigned slab;           // bytes of one sequence's 64 activation rows
+};
+static __device__ __forceinline__ FwdLane fwd_lane(const FwdArgs& a) {
+    FwdLane g;
+    g.li = threadIdx.x & 31;
+    g.hi = (threadIdx.x & 63) >> 5;
+    g.T = a.T;
+    g.T4 = a.T * 4;
+    g.F4 = a.F * 4;
+    g.tiles_per_b = (a.T + 31) >> 5;
+    g.ntiles = a.B * g.tiles_per_b;
+    g.slab = (unsigned)(64 * g.T4);
+    return g;
+}
+// coordinates of a (wave-uniform) tile
+struct FwdTile {
+    int b, t;    // sequence; this lane's sample
+    bool inb;    // t < T
+    int vcur;    // per-lane byte offset of (channel 4 hi, sample t) for loads: dead lanes read a valid dummy address
+    int vst;     // ... for stores: dead lanes carry an out-of-range offset
+};
+static __device__ __forceinline__ FwdTile fwd_tile(const FwdLane& g, int tile) {
+    FwdTile c;
+    c.b = tile / g.tiles_per_b;
+    c.t = (tile - c.b * g.tiles_per_b) * 32 + g.li;
+    c.inb = c.t < g.T;
+    c.vcur = c.inb ? (4 * g.hi * g.T + c.t) * 4 : 0;
+    c.vst = c.inb ? c.vcur : WN_VOFF_DEAD;
+    return c;
+}
+
+// Operand issue.  Operands are raw loads, consumed in place (zero history / dead lanes selected at use); k-step s of lane half
+// hi is channel kappa64(s, hi).  History taps [TAP0, TAP1) of a (wave-uniform) tile: tap `tap` lies (K - 1 - tap) * dil samples back.
+template <int K, int TAP0, int TAP1, int KH>
+static __device__ __forceinline__ void fwd_issue_hist(const FwdArgs& a, const FwdLane& g, int tile, float (&xh)[KH][32], bool (&okh)[KH]) {
+    const int b = tile / g.tiles_per_b;
+    const int t = (tile - b * g.tiles_per_b) * 32 + g.li;
+    const wn_rsrc_t Xr = wn_make_buf(a.X + (long)b * 64 * g.T, g.slab);
+    WN_UNROLL
+    for (int tap = TAP0; tap < TAP1; ++tap) {
+        const int ts = t - (K - 1 - tap) * a.dil;
+        const bool ok = (t < g.T) && ts >= 0;
+        okh[tap] = ok;
+        const int vt = ok ? (4 * g.hi * g.T + ts) * 4 : 0;  // dead lanes read a valid dummy address
+        WN_UNROLL
+        for (int s = 0; s < 32; ++s) xh[tap][s] = wn_buf_load(Xr, vt, kappa64(s, 0) * g.T4);
+    }
+}
+// current tap (shift 0); it is also the residual input, already in D layout
+static __device__ __forceinline__ void fwd_issue_cur(const FwdArgs& a, const FwdLane& g, const FwdTile& c, float (&xc)[32]) {
+    const wn_rsrc_t Xr = wn_make_buf(a.X + (long)c.b * 64 * g.T, g.slab);
+    WN_UNROLL
+    for (int s = 0; s < 32; ++s) xc[s] = wn_buf_load(Xr, c.vcur, kappa64(s, 0) * g.T4);
+}
+// residual input + res-1x1 bias in D layout (rb: the bias vector in the LDS)
+static __device__ __forceinline__ void fwd_resid_bias(const FwdLane& g, const FwdTile& c, const float (&xc)[32], const float* rb, f32x16 (&xb)[2]) {
+    const float* rbl = rb + 4 * g.hi;
+    WN_UNROLL
+    for (int q = 0; q < 2; ++q) {
+        WN_UNROLL
+        for (int r = 0; r < 16; ++r) xb[q][r] = (c.inb ? xc[16 * q + r] : 0.0f) + rbl[32 * q + mfma32_row(r, 0)];
+    }
+}
+
+// aux / gate inputs (frame rate, L2 resident).  One register set for both 32-channel halves: an element of the second half is
+// requested right after the element of the first half in the same register has been consumed (64 registers less across the
+// gate phase).  fwd_aux_issue requests the first half.
+struct FwdAux {
+    wn_rsrc_t Gr;
+    int vg;
+    float upw_j;
+    float ga[16], gg[16];
+};
+static __device__ __forceinline__ void fwd_aux_issue(const FwdArgs& a, const FwdLane& g, const FwdTile& c, FwdAux& x) {
+    const int tc = c.inb ? c.t : g.T - 1;
+    const int fr = tc / a.U;
+    x.upw_j = a.upw[tc - fr * a.U];
+    x.Gr = wn_make_buf(a.G + (long)c.b * a.g_bstride, (unsigned)(128 * g.F4));
+    x.vg = (4 * g.hi * a.F + fr) * 4;
+    WN_UNROLL
+    for (int r = 0; r < 16; ++r) {
+        x.ga[r] = wn_buf_load(x.Gr, x.vg, mfma32_row(r, 0) * g.F4);
+        x.gg[r] = wn_buf_load(x.Gr, x.vg, (mfma32_row(r, 0) + 64) * g.F4);
+    }
+}
+// gate (reference wavenet.py:529-532): P = conv + w[j]*G[row][f] + c[row]; s = sigmoid(P[:64]) and z = s * tanh(P[64:]) are saved
+// for backward (the tanh half is not: backward rebuilds it as z / s).  pre(acc, add): the pre-activation from an accumulator
+// element and the aux + bias term that is added to it.
+template <class Pre>
+static __device__ __forceinline__ void fwd_gate_phase(const FwdArgs& a, const FwdLane& g, const FwdTile& c, const f32x16 (&acc)[4],
+                                                      FwdAux& x, const float* cv, f32x16 (&z)[2], Pre pre) {
+    const wn_rsrc_t Sr = wn_make_buf(a.S + (long)c.b * 64 * g.T, g.slab);
+    const wn_rsrc_t Zr = wn_make_buf(a.Z + (long)c.b * 64 * g.T, g.slab);
+    const float* cvl = cv + 4 * g.hi;
+    WN_UNROLL
+    for (int q = 0; q < 2; ++q) {
+        WN_UNROLL
+        for (int r = 0; r < 16; ++r) {
+            const int row0 = 32 * q + mfma32_row(r, 0);  // + 4*hi is in the per-lane offsets
+            const float pa = pre(acc[q][r], x.upw_j * x.ga[r] + cvl[row0]);
+            const float pg = pre(acc[q + 2][r], x.upw_j * x.gg[r] + cvl[row0 + 64]);
+            if (q == 0) {
+                x.ga[r] = wn_buf_load(x.Gr, x.vg, (32 + mfma32_row(r, 0)) * g.F4);
+                x.gg[r] = wn_buf_load(x.Gr, x.vg, (96 + mfma32_row(r, 0)) * g.F4);
+            }
+            const float s = wn_sigmoid(pa);
+            const float zz = s * wn_tanh(pg);
+            z[q][r] = zz;
+            // unconditional stores: lanes past T carry an out-of-range offset (dropped by the buffer range check) -- a lane-
+            // conditional store here would cut the gate phase into one basic block per element (no overlap of the exp / rcp
+            // chains of different elements: measured 11000 cycles for ~4500 cycles of arithmetic)
+            wn_buf_store(Sr, s, c.vst, row0 * g.T4);
+            wn_buf_store(Zr, zz, c.vst, row0 * g.T4);
+        }
+    }
+}
+static __device__ __forceinline__ void fwd_store_xnext(const FwdArgs& a, const FwdLane& g, const FwdTile& c, const f32x16 (&v)[2]) {
+    const wn_rsrc_t Xn = wn_make_buf(a.Xnext + (long)c.b * 64 * g.T, g.slab);
+    WN_UNROLL
+    for (int q = 0; q < 2; ++q) {
+        WN_UNROLL
+        for (int r = 0; r < 16; ++r) wn_buf_store(Xn, v[q][r], c.vst, (32 * q + mfma32_row(r, 0)) * g.T4);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_resblock_fwd_f32 -- the block on the f32-input MFMA (an exact fp32 fma chain).  The pipeline is k_resblock_fwd's, except
+// that ALL history taps are requested a tile ahead, the walk is not forced into scalar registers, there are no priority phases,
+// and residual + bias are the initial value of the res accumulators (formed after the gate phase).
+// LDS (fwd_f32_lds_bytes): weights as staged by stage_copy, [K*64][128] taps and [64][64] res 1x1, then the vectors.
+// ---------------------------------------------------------------------------------------------
+// one tap: 32 k-steps of Wt's 128 rows against x.  Ping-pong LDS operand sets: the reads of k-step s+1 are in flight during the
+// MFMAs of step s
+static __device__ __forceinline__ void fwd_f32_tap(const float* Wt, const float (&x)[32], bool ok, f32x16 (&acc)[4]) {
+    float a0[4], a1[4];
+    WN_UNROLL
+    for (int q = 0; q < 4; ++q) a0[q] = Wt[kappa64(0, 0) * 128 + 32 * q];
+    WN_SGB_DS(2);  // prologue group: from here on every [DS][MFMA] pair = (next operands, current MFMAs)
+    WN_UNROLL
+    for (int s = 0; s < 32; s += 2) {
+        WN_UNROLL
+        for (int q = 0; q < 4; ++q) a1[q] = Wt[kappa64(s + 1, 0) * 128 + 32 * q];
+        {
+            const float xv = ok ? x[s] : 0.0f;
+            WN_UNROLL
+            for (int q = 0; q < 4; ++q) acc[q] = mfma32(a0[q], xv, acc[q]);
+        }
+        WN_SGB_DS(2);
+        WN_SGB_MFMA(4);
+        if (s + 2 < 32) {
+            WN_UNROLL
+            for (int q = 0; q < 4; ++q) a0[q] = Wt[kappa64(s + 2, 0) * 128 + 32 * q];
+        }
+        {
+            const float xv = ok ? x[s + 1] : 0.0f;
+            WN_UNROLL
+            for (int q = 0; q < 4; ++q) acc[q] = mfma32(a1[q], xv, acc[q]);
+        }
+        WN_SGB_DS(2);
+        WN_SGB_MFMA(4);
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(WN_LB) void k_resblock_fwd_f32(FwdArgs a) {
+    WN_DYN_SMEM(smem_raw);
+    float* Wd = reinterpret_cast<float*>(smem_raw);  // [K*64][128]
+    float* Wr = Wd + K * 64 * 128;                   // [64][64]
+    float* cv = Wr + 64 * 64;                        // [128], then the res bias [64]
+    fwd_timing_begin(a);
+    stage_copy(Wd, a.wd_f, K * 64 * 128);
+    stage_copy(Wr, a.wres_f, 64 * 64);
+    fwd_stage_vectors(cv, a);
+    __syncthreads();
+    fwd_timing_staged(a);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 31, hi = lane >> 5;
-    const int T = a.T;
-    const int T4 = T * 4;  // bytes per channel row
-    const int F4 = a.F * 4;
-    const int tiles_per_b = (T + 31) >> 5;
-    const int ntiles = a.B * tiles_per_b;
-    const unsigned slab = (unsigned)(64 * T4);
-    const TileWalk walk = tile_walk(ntiles, threadIdx.x >> 6);
+    (void)lane; (void)wave;
+    const FwdLane g = fwd_lane(a);
+    const TileWalk walk = tile_walk(g.ntiles, threadIdx.x >> 6);
     const int step = walk.step, tile_end = walk.end;
     constexpr int KH = (K > 1) ? (K - 1) : 1;  // history taps (shift > 0)
 
-    // Software pipeline (per wave, per 32-sample tile):
-    //   history-tap operands xh : issued before the res MFMAs of the PREVIOUS tile (cross-tile prefetch)
-    //   current-tap operands xc : issued at tile start, land under the history-tap MFMAs
-    //   aux/gate inputs         : first half issued before the current-tap MFMAs, second half
-    //                             before the gate math of the first half
-    // Operands are consumed in place (zero history / dead lanes selected at use).
     float xh[KH][32];
     bool okh[KH];
-    auto issue_hist = [&](int tl_v) {
-        const int tl = WN_UNIFORM(tl_v);
-        const int b = tl / tiles_per_b;
-        const int t = (tl - b * tiles_per_b) * 32 + li;
-        const wn_rsrc_t Xr = wn_make_buf(a.X + (long)b * 64 * T, slab);
-        WN_UNROLL
-        for (int tap = 0; tap + 1 < K; ++tap) {
-            const int ts = t - (K - 1 - tap) * a.dil;
-            const bool ok = (t < T) && ts >= 0;
-            okh[tap] = ok;
-            const int vt = ok ? (4 * hi * T + ts) * 4 : 0;  // dead lanes read a valid dummy address
-            WN_UNROLL
-            for (int s = 0; s < 32; ++s) xh[tap][s] = wn_buf_load(Xr, vt, kappa64(s, 0) * T4);
-        }
-    };
-
     int tile_v = walk.first;
     int tcount = 0;
     (void)tcount;
-    if (K > 1 && tile_v < tile_end) issue_hist(tile_v);
+    if (K > 1 && tile_v < tile_end) fwd_issue_hist<K, 0, K - 1>(a, g, WN_UNIFORM(tile_v), xh, okh);
     while (tile_v < tile_end) {
         WN_STAMP(0);
-        const int tile = WN_UNIFORM(tile_v);
-        const int b = tile / tiles_per_b;
-        const int t = (tile - b * tiles_per_b) * 32 + li;
-        const bool inb = t < T;
-        const int tc = inb ? t : T - 1;
-        const int vcur = inb ? (4 * hi * T + t) * 4 : 0;
-
-        // current tap (shift 0): raw loads now, consumed after the history taps
+        const FwdTile c = fwd_tile(g, WN_UNIFORM(tile_v));
         float xc[32];
-        {
-            const wn_rsrc_t Xr = wn_make_buf(a.X + (long)b * 64 * T, slab);
-            WN_UNROLL
-            for (int s = 0; s < 32; ++s) xc[s] = wn_buf_load(Xr, vcur, kappa64(s, 0) * T4);
-        }
+        fwd_issue_cur(a, g, c, xc);
         WN_SCHED_BARRIER();
         f32x16 acc[4];
         WN_UNROLL
         for (int q = 0; q < 4; ++q) acc[q] = f32x16_zero();
-        // dilated taps with history (shift > 0)
         WN_UNROLL
-        for (int tap = 0; tap + 1 < K; ++tap) {
-            const float* Wt = Wd + tap * 64 * 128 + 4 * hi * 128 + li;
-            // ping-pong LDS operand sets: the reads of k-step s+1 are in flight during the MFMAs of step s
-            float a0[4], a1[4];
-            WN_UNROLL
-            for (int q = 0; q < 4; ++q) a0[q] = Wt[kappa64(0, 0) * 128 + 32 * q];
-            WN_SGB_DS(2);  // prologue group: from here on every [DS][MFMA] pair = (next operands, current MFMAs)
-            WN_UNROLL
-            for (int s = 0; s < 32; s += 2) {
-                WN_UNROLL
-                for (int q = 0; q < 4; ++q) a1[q] = Wt[kappa64(s + 1, 0) * 128 + 32 * q];
-                {
-                    const float xv = okh[tap] ? xh[tap][s] : 0.0f;
-                    WN_UNROLL
-                    for (int q = 0; q < 4; ++q) acc[q] = mfma32(a0[q], xv, acc[q]);
-                }
-                WN_SGB_DS(2);
-                WN_SGB_MFMA(4);
-                if (s + 2 < 32) {
-                    WN_UNROLL
-                    for (int q = 0; q < 4; ++q) a0[q] = Wt[kappa64(s + 2, 0) * 128 + 32 * q];
-                }
-                {
-                    const float xv = okh[tap] ? xh[tap][s + 1] : 0.0f;
-                    WN_UNROLL
-                    for (int q = 0; q < 4; ++q) acc[q] = mfma32(a1[q], xv, acc[q]);
-                }
-                WN_SGB_DS(2);
-                WN_SGB_MFMA(4);
-            }
-        }
+        for (int tap = 0; tap + 1 < K; ++tap) fwd_f32_tap(Wd + tap * 64 * 128 + 4 * g.hi * 128 + g.li, xh[tap], okh[tap], acc);
         WN_STAMP(1);  // after history-tap MFMAs
-        // aux / gate inputs (frame rate, L2 resident), first 32 gate channels
-        const int fr = tc / a.U;
-        const float upw_j = a.upw[tc - fr * a.U];
-        const wn_rsrc_t Gr = wn_make_buf(a.G + (long)b * a.g_bstride, (unsigned)(128 * F4));
-        const int vg = (4 * hi * a.F + fr) * 4;
-        // one register set for both 32-channel halves: an element of the second half is requested right after the
-        // element of the first half in the same register has been consumed (64 registers less across the gate phase)
-        float ga[16], gg[16];
-        WN_UNROLL
-        for (int r = 0; r < 16; ++r) {
-            ga[r] = wn_buf_load(Gr, vg, mfma32_row(r, 0) * F4);
-            gg[r] = wn_buf_load(Gr, vg, (mfma32_row(r, 0) + 64) * F4);
-        }
+        FwdAux aux;
+        fwd_aux_issue(a, g, c, aux);
         WN_SCHED_BARRIER();
-        // current tap; xc is also the residual input, already in D layout
-        {
-            const float* Wt = Wd + (K - 1) * 64 * 128 + 4 * hi * 128 + li;
-            // ping-pong LDS operand sets: the reads of k-step s+1 are in flight during the MFMAs of step s
-            float a0[4], a1[4];
-            WN_UNROLL
-            for (int q = 0; q < 4; ++q) a0[q] = Wt[kappa64(0, 0) * 128 + 32 * q];
-            WN_SGB_DS(2);  // prologue group: from here on every [DS][MFMA] pair = (next operands, current MFMAs)
-            WN_UNROLL
-            for (int s = 0; s < 32; s += 2) {
-                WN_UNROLL
-                for (int q = 0; q < 4; ++q) a1[q] = Wt[kappa64(s + 1, 0) * 128 + 32 * q];
-                {
-                    const float xv = inb ? xc[s] : 0.0f;
-                    WN_UNROLL
-                    for (int q = 0; q < 4; ++q) acc[q] = mfma32(a0[q], xv, acc[q]);
-                }
-                WN_SGB_DS(2);
-                WN_SGB_MFMA(4);
-                if (s + 2 < 32) {
-                    WN_UNROLL
-                    for (int q = 0; q < 4; ++q) a0[q] = Wt[kappa64(s + 2, 0) * 128 + 32 * q];
-                }
-                {
-                    const float xv = inb ? xc[s + 1] : 0.0f;
-                    WN_UNROLL
-                    for (int q = 0; q < 4; ++q) acc[q] = mfma32(a1[q], xv, acc[q]);
-                }
-                WN_SGB_DS(2);
-                WN_SGB_MFMA(4);
-            }
-        }
+        fwd_f32_tap(Wd + (K - 1) * 64 * 128 + 4 * g.hi * 128 + g.li, xc, c.inb, acc);
         WN_SCHED_BARRIER();
         WN_STAMP(2);  // after current-tap MFMAs
-        // Prefetch the history-tap operands of this wave's next tile NOW, i.e. before the stores of the
-        // gate phase: vmcnt is one in-order counter for loads AND stores, so loads issued behind the
-        // 96 S/Gt/Z stores could only be waited for together with those stores' acknowledgements.
         const int next_v = tile_v + step;
-        if (K > 1 && next_v < tile_end) issue_hist(next_v);
-        // gate (reference wavenet.py:529-532): P = conv + w[j]*G[row][f] + c[row]; saved for backward
-        const wn_rsrc_t Sr = wn_make_buf(a.S + (long)b * 64 * T, slab);
-        const bool keep_g = a.Gt != nullptr;   // NULL: the tanh half is not saved (backward rebuilds it as z / s)
-        const wn_rsrc_t Gtr = wn_make_buf((keep_g ? a.Gt : a.S) + (long)b * 64 * T, slab);
-        const wn_rsrc_t Zr = wn_make_buf(a.Z + (long)b * 64 * T, slab);
-        const float* cvl = cv + 4 * hi;
+        if (K > 1 && next_v < tile_end) fwd_issue_hist<K, 0, K - 1>(a, g, WN_UNIFORM(next_v), xh, okh);
         f32x16 z[2];
-        const int vst = inb ? vcur : WN_VOFF_DEAD;
-        auto gate_phase = [&](auto keep_tag) {
-        constexpr bool KEEP_G = decltype(keep_tag)::value;
-        WN_UNROLL
-        for (int q = 0; q < 2; ++q) {
-            WN_UNROLL
-            for (int r = 0; r < 16; ++r) {
-                const int row0 = 32 * q + mfma32_row(r, 0);  // + 4*hi is in the per-lane offsets
-                const float pa = acc[q][r] + (upw_j * ga[r] + cvl[row0]);
-                const float pg = acc[q + 2][r] + (upw_j * gg[r] + cvl[row0 + 64]);
-                if (q == 0) {
-                    ga[r] = wn_buf_load(Gr, vg, (32 + mfma32_row(r, 0)) * F4);
-                    gg[r] = wn_buf_load(Gr, vg, (96 + mfma32_row(r, 0)) * F4);
-                }
-                const float s = wn_sigmoid(pa);
-                const float g = wn_tanh(pg);
-                const float zz = s * g;
-                z[q][r] = zz;
-                // unconditional stores: lanes past T carry an out-of-range offset (dropped by the buffer range check), and
-                // the tanh half goes through the same instruction stream only when it is kept -- a lane- or kernel-
-                // conditional store here would cut the gate phase into one basic block per element (no overlap of the
-                // exp / rcp chains of different elements: measured 11000 cycles for ~4500 cycles of arithmetic)
-                wn_buf_store(Sr, s, vst, row0 * T4);
-                if (KEEP_G) wn_buf_store(Gtr, g, vst, row0 * T4);
-                wn_buf_store(Zr, zz, vst, row0 * T4);
-            }
-        }
-        };
-        if (keep_g) gate_phase(std::true_type{});
-        else gate_phase(std::false_type{});
-        WN_STAMP(3);  // after gate math + S/Gt/Z stores issued
+        fwd_gate_phase(a, g, c, acc, aux, cv, z, [](float v, float add) { return v + add; });
+        WN_STAMP(3);  // after gate math + S/Z stores issued
         f32x16 racc[2];
-        if (a.Xnext != nullptr) {
-            const float* rbl = rb + 4 * hi;
-            WN_UNROLL
-            for (int q = 0; q < 2; ++q) {
-                WN_UNROLL
-                for (int r = 0; r < 16; ++r)
-                    racc[q][r] = (inb ? xc[16 * q + r] : 0.0f) + rbl[32 * q + mfma32_row(r, 0)];
-            }
-        }
+        if (a.Xnext != nullptr) fwd_resid_bias(g, c, xc, cv + 128, racc);
         WN_SCHED_BARRIER();
         // res 1x1 + residual; z is consumed straight from the accumulator registers
         if (a.Xnext != nullptr) {
-            const float* Wrl = Wr + 4 * hi * 64 + li;
+            const float* Wrl = Wr + 4 * g.hi * 64 + g.li;
             // stage = two k-steps (4 LDS operands, 4 MFMAs); ping-pong operand sets as above
             float a0[4], a1[4];
             WN_UNROLL
@@ -432,40 +474,16 @@ __global__ __launch_bounds__(WN_LB) void k_resblock_fwd(FwdArgs a) {
                 WN_SGB_DS(2);
                 WN_SGB_MFMA(4);
             }
-            {
-                const wn_rsrc_t Xn = wn_make_buf(a.Xnext + (long)b * 64 * T, slab);
-                WN_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    WN_UNROLL
-                    for (int r = 0; r < 16; ++r) wn_buf_store(Xn, racc[q][r], vst, (32 * q + mfma32_row(r, 0)) * T4);
-                }
-            }
+            fwd_store_xnext(a, g, c, racc);
         }
         WN_STAMP(4);  // tile done
         ++tcount;
         tile_v = next_v;
     }
-#ifdef WN_TIMING
-    if (a.dbg && blockIdx.x == 0 && lane == 0) {
-        __builtin_amdgcn_s_waitcnt(0);
-        a.dbg[(wave * 4) * 16 + 8] = (long long)__builtin_amdgcn_s_memrealtime();
-        a.dbg[(wave * 4) * 16 + 9] = (long long)__builtin_readcyclecounter();
-    }
-    if (a.dbg && lane == 0) {
-        __builtin_amdgcn_s_waitcnt(0);
-        if (wave == 0) a.dbg[512 + blockIdx.x * 4 + 1] = (long long)__builtin_amdgcn_s_memrealtime();
-        if (wave == 7) a.dbg[512 + blockIdx.x * 4 + 2] = (long long)__builtin_amdgcn_s_memrealtime();
-        if (wave == 0) a.dbg[512 + blockIdx.x * 4 + 3] = tcount;
-    }
-#endif
+    fwd_timing_end(a, tcount);
 }
 
-// The same residual block on the bf16 matrix cores (3-way operand split, six products, fp32
-// accumulate: fp32-equivalent, see wn_gemm6.hip).  The register layouts of the activation operands
-// (xh, xc, z: k-step s of lane half hi = channel kappa64(s, hi)) are unchanged; 8 consecutive steps
-// form the lane's share of one 16-k block, i.e. block kb holds channels 16 kb .. 16 kb + 15 and
-// position (hi, e) of the block is channel 16 kb + (e&3) + 8 (e>>2) + 4 hi.  The weights are split
-// once per launch into LDS with exactly that k order: [block][piece][row][hi*8 + e].
+// 3-way bf16 split of 8 values: the lane's share of one 16-k block (k order: see the arithmetics of k_resblock_fwd)
 static __device__ __forceinline__ void split8(const float (&x)[8], wn_f4 (&bf)[3]) {
     unsigned hq[4], mq[4], lq[4];
     WN_UNROLL
@@ -592,344 +610,9 @@ int wn_fused_pack_images(const float* wd_f, const float* wres_f, const float* wd
     return 0;
 }
 
-template <int K>
-__global__ __launch_bounds__(WN_LB) void k_resblock_fwd_s(FwdArgs a) {
-    WN_DYN_SMEM(smem_raw);
-    constexpr int WD_BLK = 3 * 128 * 32, WR_BLK = 3 * 64 * 32;  // bytes of one 16-k block
-    char* Wd = smem_raw;                                         // [K*4 blocks][piece][128 rows][16 k] bf16
-    // K = 3: the three taps alone fill the LDS (144 KB), so the res-1x1 fragments (24 KB per layer, L2 resident) are read
-    // from the layer's pre-split image in global memory, one 16-k block ahead of their MFMAs (RG = "res from global")
-    constexpr bool RG = (K >= 3);
-    char* Wr = Wd + K * 4 * WD_BLK;                              // [4 blocks][piece][64 rows][16 k] bf16   (not with RG)
-    float* cv = reinterpret_cast<float*>(Wr + (RG ? 0 : 4 * WR_BLK));   // [128]
-    float* rb = cv + 128;                                        // [64]
-#ifdef WN_TIMING
-    if (a.dbg && blockIdx.x == 0 && (threadIdx.x & 63) == 0) {
-        a.dbg[((threadIdx.x >> 6) * 4) * 16 + 5] = (long long)__builtin_readcyclecounter();
-        a.dbg[((threadIdx.x >> 6) * 4) * 16 + 7] = (long long)__builtin_amdgcn_s_memrealtime();
-    }
-    if (a.dbg && threadIdx.x == 0) a.dbg[512 + blockIdx.x * 4 + 0] = (long long)__builtin_amdgcn_s_memrealtime();
-#endif
-    if (RG) {   // (the launcher only takes this kernel with an image)
-        copy_image_to_lds(smem_raw, a.wimg, K * 4 * WD_BLK);
-        WN_WAIT_VMCNT(0);
-    } else if (a.wimg != nullptr) {
-        copy_image_to_lds(smem_raw, a.wimg, fwd_image_bytes(K));   // pre-split once per step (wn_fused_pack_images)
-        WN_WAIT_VMCNT(0);
-    } else {
-        fill_fwd_image<K>(Wd, Wr, a.wd_f, a.wres_f, threadIdx.x, WN_FT);
-    }
-    if (threadIdx.x < 128) cv[threadIdx.x] = a.cvec[threadIdx.x];
-    if (threadIdx.x < 64) rb[threadIdx.x] = a.res_bias[threadIdx.x];
-    __syncthreads();
-#ifdef WN_TIMING
-    if (a.dbg && blockIdx.x == 0 && (threadIdx.x & 63) == 0)
-        a.dbg[((threadIdx.x >> 6) * 4) * 16 + 6] = (long long)__builtin_readcyclecounter();
-#endif
-    // De-phase the two waves that share a SIMD (waves w and w+4): started together they would run
-    // their MFMA phases and their gate/store phases in lock step and leave the matrix pipe idle
-    // during the latter; half a tile of head start makes one wave's VALU/VMEM phase coincide with
-    // the other's MFMA phase.
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 31, hi = lane >> 5;
-    const int T = a.T;
-    const int T4 = T * 4;  // bytes per channel row
-    const int F4 = a.F * 4;
-    const int tiles_per_b = (T + 31) >> 5;
-    const int ntiles = a.B * tiles_per_b;
-    const unsigned slab = (unsigned)(64 * T4);
-    const TileWalk walk = tile_walk(ntiles, threadIdx.x >> 6);
-    const int step = WN_UNIFORM(walk.step), tile_end = WN_UNIFORM(walk.end);
-    constexpr int KH = (K > 1) ? (K - 1) : 1;  // history taps (shift > 0)
-    // history taps requested one tile ahead (across the gate phase of the previous tile).  K = 3 keeps only the oldest tap
-    // that way and requests the middle one at tile start with the current tap: 32 registers less across the gate phase.
-    constexpr int KP = (K >= 3) ? 1 : K - 1;
-
-    // Software pipeline (per wave, per 32-sample tile):
-    //   history-tap operands xh : issued before the res MFMAs of the PREVIOUS tile (cross-tile prefetch)
-    //   current-tap operands xc : issued at tile start, land under the history-tap MFMAs
-    //   aux/gate inputs         : first half issued before the current-tap MFMAs, second half
-    //                             before the gate math of the first half
-    // Operands are consumed in place (zero history / dead lanes selected at use).
-    float xh[KH][32];
-    bool okh[KH];
-    auto issue_hist = [&](int tl_v) {
-        const int tl = WN_UNIFORM(tl_v);
-        const int b = tl / tiles_per_b;
-        const int t = (tl - b * tiles_per_b) * 32 + li;
-        const wn_rsrc_t Xr = wn_make_buf(a.X + (long)b * 64 * T, slab);
-        WN_UNROLL
-        for (int tap = 0; tap < KP; ++tap) {
-            const int ts = t - (K - 1 - tap) * a.dil;
-            const bool ok = (t < T) && ts >= 0;
-            okh[tap] = ok;
-            const int vt = ok ? (4 * hi * T + ts) * 4 : 0;  // dead lanes read a valid dummy address
-            WN_UNROLL
-            for (int s = 0; s < 32; ++s) xh[tap][s] = wn_buf_load(Xr, vt, kappa64(s, 0) * T4);
-        }
-    };
-
-    int tile_v = WN_UNIFORM(walk.first);
-    int tcount = 0;
-    (void)tcount;
-    if (K > 1 && tile_v < tile_end) issue_hist(tile_v);
-    while (tile_v < tile_end) {
-        WN_STAMP(0);
-        const int tile = WN_UNIFORM(tile_v);
-        const int b = tile / tiles_per_b;
-        const int t = (tile - b * tiles_per_b) * 32 + li;
-        const bool inb = t < T;
-        const int tc = inb ? t : T - 1;
-        const int vcur = inb ? (4 * hi * T + t) * 4 : 0;
-
-        // current tap (shift 0): raw loads now, consumed after the history taps
-        float xc[32];
-        {
-            const wn_rsrc_t Xr = wn_make_buf(a.X + (long)b * 64 * T, slab);
-            WN_UNROLL
-            for (int tap = KP; tap + 1 < K; ++tap) {   // (K = 3) the history taps that are not requested a tile ahead
-                const int ts = t - (K - 1 - tap) * a.dil;
-                const bool ok = inb && ts >= 0;
-                okh[tap] = ok;
-                const int vt = ok ? (4 * hi * T + ts) * 4 : 0;
-                WN_UNROLL
-                for (int s = 0; s < 32; ++s) xh[tap][s] = wn_buf_load(Xr, vt, kappa64(s, 0) * T4);
-            }
-            WN_UNROLL
-            for (int s = 0; s < 32; ++s) xc[s] = wn_buf_load(Xr, vcur, kappa64(s, 0) * T4);
-        }
-        WN_SCHED_BARRIER();
-        WN_PRIO(WN_PRIO_MFMA);
-        f32x16 acc[4];
-        WN_UNROLL
-        for (int q = 0; q < 4; ++q) acc[q] = f32x16_zero();
-        // dilated taps with history (shift > 0)
-        WN_UNROLL
-        for (int tap = 0; tap + 1 < K; ++tap) {
-            WN_UNROLL
-            for (int kb = 0; kb < 4; ++kb) {
-                float x8[8];
-                WN_UNROLL
-                for (int e = 0; e < 8; ++e) x8[e] = okh[tap] ? xh[tap][8 * kb + e] : 0.0f;
-                wn_f4 bf[3];
-                split8(x8, bf);
-                const char* Wl = Wd + (tap * 4 + kb) * WD_BLK + wn_frag_off(li, hi);
-                constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};  // small terms first
-                WN_UNROLL
-                for (int qh = 0; qh < 4; qh += 2) {  // two row tiles at a time (register budget)
-                    wn_f4 af[2][3];
-                    WN_UNROLL
-                    for (int q = 0; q < 2; ++q) {
-                        WN_UNROLL
-                        for (int p = 0; p < 3; ++p)
-                            af[q][p] = *reinterpret_cast<const wn_f4*>(Wl + p * (128 * 32) + (qh + q) * 1024);
-                    }
-                    WN_UNROLL
-                    for (int t6 = 0; t6 < WN_EXP_NPROD; ++t6) {
-                        acc[qh] = mfma_bf16(af[0][PA[t6]], bf[PB[t6]], acc[qh]);
-                        acc[qh + 1] = mfma_bf16(af[1][PA[t6]], bf[PB[t6]], acc[qh + 1]);
-                    }
-                }
-            }
-        }
-        WN_STAMP(1);  // after history-tap MFMAs
-        // aux / gate inputs (frame rate, L2 resident), first 32 gate channels
-        const int fr = tc / a.U;
-        const float upw_j = a.upw[tc - fr * a.U];
-        const wn_rsrc_t Gr = wn_make_buf(a.G + (long)b * a.g_bstride, (unsigned)(128 * F4));
-        const int vg = (4 * hi * a.F + fr) * 4;
-        // one register set for both 32-channel halves: an element of the second half is requested right after the
-        // element of the first half in the same register has been consumed (64 registers less across the gate phase)
-        float ga[16], gg[16];
-        WN_UNROLL
-        for (int r = 0; r < 16; ++r) {
-            ga[r] = wn_buf_load(Gr, vg, mfma32_row(r, 0) * F4);
-            gg[r] = wn_buf_load(Gr, vg, (mfma32_row(r, 0) + 64) * F4);
-        }
-        WN_SCHED_BARRIER();
-        // current tap; xc is also the residual input, already in D layout
-        {
-            WN_UNROLL
-            for (int kb = 0; kb < 4; ++kb) {
-                float x8[8];
-                WN_UNROLL
-                for (int e = 0; e < 8; ++e) x8[e] = inb ? xc[8 * kb + e] : 0.0f;
-                wn_f4 bf[3];
-                split8(x8, bf);
-                const char* Wl = Wd + ((K - 1) * 4 + kb) * WD_BLK + wn_frag_off(li, hi);
-                constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-                WN_UNROLL
-                for (int qh = 0; qh < 4; qh += 2) {  // two row tiles at a time (register budget)
-                    wn_f4 af[2][3];
-                    WN_UNROLL
-                    for (int q = 0; q < 2; ++q) {
-                        WN_UNROLL
-                        for (int p = 0; p < 3; ++p)
-                            af[q][p] = *reinterpret_cast<const wn_f4*>(Wl + p * (128 * 32) + (qh + q) * 1024);
-                    }
-                    WN_UNROLL
-                    for (int t6 = 0; t6 < WN_EXP_NPROD; ++t6) {
-                        acc[qh] = mfma_bf16(af[0][PA[t6]], bf[PB[t6]], acc[qh]);
-                        acc[qh + 1] = mfma_bf16(af[1][PA[t6]], bf[PB[t6]], acc[qh + 1]);
-                    }
-                }
-            }
-        }
-        WN_SCHED_BARRIER();
-        WN_PRIO(WN_PRIO_GATE);
-        WN_STAMP(2);  // after current-tap MFMAs
-        // Prefetch the history-tap operands of this wave's next tile NOW, i.e. before the stores of the
-        // gate phase: vmcnt is one in-order counter for loads AND stores, so loads issued behind the
-        // 96 S/Gt/Z stores could only be waited for together with those stores' acknowledgements.
-        // residual input + bias = the initial value of the res-1x1 accumulators, formed NOW: xc dies here, so that in a
-        // chain its registers simply become the next tile's history operands (no second copy of the tile is ever live)
-        // (Round 3: the sums are ADDED to the res products after the last MFMA instead of being the accumulators' initial
-        // value -- products aligned against a large initial value lose their low bits with a consistent sign, see k_chain64s.)
-        f32x16 xb2[2];
-        if (a.Xnext != nullptr) {
-            const float* rbl = rb + 4 * hi;
-            WN_UNROLL
-            for (int q = 0; q < 2; ++q) {
-                WN_UNROLL
-                for (int r = 0; r < 16; ++r)
-                    xb2[q][r] = (inb ? xc[16 * q + r] : 0.0f) + rbl[32 * q + mfma32_row(r, 0)];
-            }
-            // pin: the sums exist from here on (machine sinking would otherwise move them below the branch and keep xc alive)
-            WN_PIN2(xb2[0], xb2[1]);
-        }
-        // next tile of this wave: its history taps are requested NOW, before the stores of the gate phase.  (A variant that
-        // kept the history tap of a d >= 32 layer in registers across "tile chains" measured slower -- 60 B/lane of scratch and
-        // 16-tile runs instead of one contiguous span: profiles/r02/ab_probe_fwd_chain.txt -- and was removed in round 3.)
-        const int next_v = tile_v + step;
-        if (K > 1 && next_v < tile_end) issue_hist(next_v);
-        // gate (reference wavenet.py:529-532): P = conv + w[j]*G[row][f] + c[row]; saved for backward
-        const wn_rsrc_t Sr = wn_make_buf(a.S + (long)b * 64 * T, slab);
-        const bool keep_g = a.Gt != nullptr;   // NULL: the tanh half is not saved (backward rebuilds it as z / s)
-        const wn_rsrc_t Gtr = wn_make_buf((keep_g ? a.Gt : a.S) + (long)b * 64 * T, slab);
-        const wn_rsrc_t Zr = wn_make_buf(a.Z + (long)b * 64 * T, slab);
-        const float* cvl = cv + 4 * hi;
-        f32x16 z[2];
-        const int vst = inb ? vcur : WN_VOFF_DEAD;
-        auto gate_phase = [&](auto keep_tag) {
-        constexpr bool KEEP_G = decltype(keep_tag)::value;
-        WN_UNROLL
-        for (int q = 0; q < 2; ++q) {
-            WN_UNROLL
-            for (int r = 0; r < 16; ++r) {
-                const int row0 = 32 * q + mfma32_row(r, 0);  // + 4*hi is in the per-lane offsets
-                const float pa = acc[q][r] + (upw_j * ga[r] + cvl[row0]);
-                const float pg = acc[q + 2][r] + (upw_j * gg[r] + cvl[row0 + 64]);
-                if (q == 0) {
-                    ga[r] = wn_buf_load(Gr, vg, (32 + mfma32_row(r, 0)) * F4);
-                    gg[r] = wn_buf_load(Gr, vg, (96 + mfma32_row(r, 0)) * F4);
-                }
-                const float s = wn_sigmoid(pa);
-                const float g = wn_tanh(pg);
-                const float zz = s * g;
-                z[q][r] = zz;
-                // unconditional stores: lanes past T carry an out-of-range offset (dropped by the buffer range check), and
-                // the tanh half goes through the same instruction stream only when it is kept -- a lane- or kernel-
-                // conditional store here would cut the gate phase into one basic block per element (no overlap of the
-                // exp / rcp chains of different elements: measured 11000 cycles for ~4500 cycles of arithmetic)
-                wn_buf_store(Sr, s, vst, row0 * T4);
-                if (KEEP_G) wn_buf_store(Gtr, g, vst, row0 * T4);
-                wn_buf_store(Zr, zz, vst, row0 * T4);
-            }
-        }
-        };
-        if (keep_g) gate_phase(std::true_type{});
-        else gate_phase(std::false_type{});
-        WN_STAMP(3);  // after gate math + S/Gt/Z stores issued
-        WN_SCHED_BARRIER();
-        WN_PRIO(WN_PRIO_MFMA);
-        // res 1x1 + residual; z is consumed straight from the accumulator registers
-        if (a.Xnext != nullptr) {
-            f32x16 racc[2];
-            racc[0] = f32x16_zero();
-            racc[1] = f32x16_zero();
-            const wn_rsrc_t Ir = wn_make_buf(a.wimg, (unsigned)(RG ? fwd_image_bytes(K) : 16));
-            const int vfrag = wn_frag_off(li, hi);
-            auto res_frags = [&](int kb, wn_f4 (&af)[2][3]) {
-                WN_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    WN_UNROLL
-                    for (int p = 0; p < 3; ++p) {
-                        if (RG) {
-                            const float4 f = wn_buf_load4(Ir, vfrag, (unsigned)(K * 4 * WD_BLK + kb * WR_BLK + p * (64 * 32) + q * 1024));
-                            af[q][p] = wn_f4{f.x, f.y, f.z, f.w};
-                        } else {
-                            af[q][p] = *reinterpret_cast<const wn_f4*>(Wr + kb * WR_BLK + vfrag + p * (64 * 32) + q * 1024);
-                        }
-                    }
-                }
-            };
-            wn_f4 afr[2][2][3];   // two sets: with RG the fragments of block kb + 1 are in flight under the MFMAs of block kb
-            res_frags(0, afr[0]);
-            WN_UNROLL
-            for (int kb = 0; kb < 4; ++kb) {
-                float x8[8];
-                WN_UNROLL
-                for (int e = 0; e < 8; ++e) x8[e] = z[(8 * kb + e) >> 4][(8 * kb + e) & 15];
-                wn_f4 bf[3];
-                split8(x8, bf);
-                if (kb + 1 < 4) res_frags(kb + 1, afr[(kb + 1) & 1]);
-                constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-                WN_UNROLL
-                for (int t6 = 0; t6 < WN_EXP_NPROD; ++t6) {
-                    racc[0] = mfma_bf16(afr[kb & 1][0][PA[t6]], bf[PB[t6]], racc[0]);
-                    racc[1] = mfma_bf16(afr[kb & 1][1][PA[t6]], bf[PB[t6]], racc[1]);
-                }
-            }
-            WN_UNROLL
-            for (int q = 0; q < 2; ++q) {
-                WN_UNROLL
-                for (int r = 0; r < 16; ++r) racc[q][r] += xb2[q][r];
-            }
-            {
-                const wn_rsrc_t Xn = wn_make_buf(a.Xnext + (long)b * 64 * T, slab);
-                WN_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    WN_UNROLL
-                    for (int r = 0; r < 16; ++r) wn_buf_store(Xn, racc[q][r], vst, (32 * q + mfma32_row(r, 0)) * T4);
-                }
-            }
-        }
-        WN_PRIO(WN_PRIO_GATE);
-        WN_STAMP(4);  // tile done
-        ++tcount;
-        tile_v = next_v;
-    }
-#ifdef WN_TIMING
-    if (a.dbg && blockIdx.x == 0 && lane == 0) {
-        __builtin_amdgcn_s_waitcnt(0);
-        a.dbg[(wave * 4) * 16 + 8] = (long long)__builtin_amdgcn_s_memrealtime();
-        a.dbg[(wave * 4) * 16 + 9] = (long long)__builtin_readcyclecounter();
-    }
-    if (a.dbg && lane == 0) {
-        __builtin_amdgcn_s_waitcnt(0);
-        if (wave == 0) a.dbg[512 + blockIdx.x * 4 + 1] = (long long)__builtin_amdgcn_s_memrealtime();
-        if (wave == 7) a.dbg[512 + blockIdx.x * 4 + 2] = (long long)__builtin_amdgcn_s_memrealtime();
-        if (wave == 0) a.dbg[512 + blockIdx.x * 4 + 3] = tcount;
-    }
-#endif
-}
-
 // ---------------------------------------------------------------------------------------------
-// k_resblock_fwd_h -- the same residual block on the FP16 matrix cores with a two-piece operand split (round 6,
-// WN_FLAG_FUSED_F16PAIR): x ~ h + l with two fp16 pieces (11 + 11 significand bits), the three products h h + h l + l h on
-// v_mfma_f32_32x32x16_f16, fp32 accumulate -- ~2^-22 |w x| per product (the rounding of an fp32 running sum over the 128 - 192
-// terms of a tap contraction) at HALF the matrix work of the six bf16 products, a weight image of 80 KB instead of 120 KB
-// (K = 3: 112 KB, so the res-1x1 fragments are back in the LDS), and 6 instead of 11 VALU instructions per operand pair.
-// fp16 has 5 exponent bits, so everything is BLOCK-SCALED by powers of two (exact):
-//   * each weight image by 2^ew with max |w| 2^ew in [2^11, 2^12) (wn_fused_pack_images measures the maximum per layer);
-//   * each 64-channel x 32-sample operand tile by 2^e with max |x| 2^e in [2^13, 2^14) -- the wave reduces the maximum of the tile
-//     it holds in registers; the taps of a tile share ONE scale (the smallest so far: the accumulators are multiplied down when a
-//     later tap has larger values), so nothing can leave fp16's range whatever the magnitudes are, and an element 2^-18 below the
-//     tile's maximum still has all 22 bits (smaller ones keep 2^-25 of the maximum in absolute terms);
-//   * z in (-1, 1) by 2^13.
-// The inverse scales are folded into the additions that follow the MFMAs (gate pre-activation, residual): no extra pass.
-// Pipeline, registers, stores: k_resblock_fwd_s's.
+// The block-scaled two-piece fp16 split (what is scaled by which power of two, and why: see FwdF16x2): its operand split, its
+// scales and its weight images.
 // ---------------------------------------------------------------------------------------------
 static __host__ __device__ constexpr int fwd16_image_bytes(int K) { return K * 4 * (2 * 128 * 32) + 4 * (2 * 64 * 32) + 64; }
 // split of 8 values times s into the two fp16 pieces of the lane's share of a 16-k block
@@ -1116,73 +799,195 @@ int wn_fused_pack_images16(const float* wd_f, const float* wres_f, const float* 
     return 0;
 }
 
-template <int K>
-__global__ __launch_bounds__(WN_LB) void k_resblock_fwd_h(FwdArgs a) {
-    WN_DYN_SMEM(smem_raw);
-    constexpr int WD_BLK = 2 * 128 * 32, WR_BLK = 2 * 64 * 32;  // bytes of one 16-k block (two fp16 pieces)
-    char* Wd = smem_raw;                                         // [K*4 blocks][piece][128 rows][16 k]
-    char* Wr = Wd + K * 4 * WD_BLK;                              // [4 blocks][piece][64 rows][16 k]
-    float* tail = reinterpret_cast<float*>(Wr + 4 * WR_BLK);     // {1 / 2^ew_taps, 1 / 2^ew_res} (+ padding to 64 bytes)
-    float* cv = tail + 16;                                       // [128]
-    float* rb = cv + 128;                                        // [64]
-#ifdef WN_TIMING
-    if (a.dbg && blockIdx.x == 0 && (threadIdx.x & 63) == 0) {
-        a.dbg[((threadIdx.x >> 6) * 4) * 16 + 5] = (long long)__builtin_readcyclecounter();
-        a.dbg[((threadIdx.x >> 6) * 4) * 16 + 7] = (long long)__builtin_amdgcn_s_memrealtime();
-    }
-    if (a.dbg && threadIdx.x == 0) a.dbg[512 + blockIdx.x * 4 + 0] = (long long)__builtin_amdgcn_s_memrealtime();
-#endif
-    copy_image_to_lds(smem_raw, a.wimg, fwd16_image_bytes(K) - 64);   // (a multiple of 1024)
-    if (threadIdx.x < 2) tail[threadIdx.x] = a.wimg[(fwd16_image_bytes(K) - 64) / 4 + threadIdx.x];
-    if (threadIdx.x < 128) cv[threadIdx.x] = a.cvec[threadIdx.x];
-    if (threadIdx.x < 64) rb[threadIdx.x] = a.res_bias[threadIdx.x];
-    WN_WAIT_VMCNT(0);
-    __syncthreads();
-    const float inv_wd = tail[0], inv_wr = tail[1];
-#ifdef WN_TIMING
-    if (a.dbg && blockIdx.x == 0 && (threadIdx.x & 63) == 0)
-        a.dbg[((threadIdx.x >> 6) * 4) * 16 + 6] = (long long)__builtin_readcyclecounter();
-    const int wave = threadIdx.x >> 6;
-#endif
-    const int lane = threadIdx.x & 63;
-    const int li = lane & 31, hi = lane >> 5;
-    const int T = a.T;
-    const int T4 = T * 4;  // bytes per channel row
-    const int F4 = a.F * 4;
-    const int tiles_per_b = (T + 31) >> 5;
-    const int ntiles = a.B * tiles_per_b;
-    const unsigned slab = (unsigned)(64 * T4);
-    const TileWalk walk = tile_walk(ntiles, threadIdx.x >> 6);
-    const int step = WN_UNIFORM(walk.step), tile_end = WN_UNIFORM(walk.end);
-    constexpr int KH = (K > 1) ? (K - 1) : 1;  // history taps (shift > 0)
-    constexpr int KP = (K >= 3) ? 1 : K - 1;   // ... requested one tile ahead (see k_resblock_fwd_s)
+// ---------------------------------------------------------------------------------------------
+// The arithmetics of k_resblock_fwd.  Each one owns its LDS image (layout, size, staging) and the contractions on it:
+//   lds_bytes(K)                   dynamic LDS of a launch: the image, then cvec [128] and the res bias [64]
+//   stage<K>(smem, a)              fills that LDS (ends with the workgroup's barrier); returns the address of cvec
+//   tap<K>(acc, x, ok, tapblk)     contracts one tap (32 k-steps of this lane half, zero where !ok) into the 128-row accumulators
+//   preact(acc, add)               accumulator element -> pre-activation (after the last tap)
+//   res<K>(z, xb, out)             out = res 1x1 of z + xb
+// The register layouts of the activation operands (xh, xc, z: k-step s of lane half hi = channel kappa64(s, hi)) are those of
+// the f32 kernel; 8 consecutive steps form the lane's share of one 16-k block, i.e. block kb holds channels 16 kb .. 16 kb + 15
+// and position (hi, e) of the block is channel 16 kb + (e&3) + 8 (e>>2) + 4 hi.  The weight images have exactly that k order:
+// [block][piece][row][hi*8 + e].
+// ---------------------------------------------------------------------------------------------
 
-    float xh[KH][32];
-    bool okh[KH];
-    auto issue_hist = [&](int tl_v) {
-        const int tl = WN_UNIFORM(tl_v);
-        const int b = tl / tiles_per_b;
-        const int t = (tl - b * tiles_per_b) * 32 + li;
-        const wn_rsrc_t Xr = wn_make_buf(a.X + (long)b * 64 * T, slab);
-        WN_UNROLL
-        for (int tap = 0; tap < KP; ++tap) {
-            const int ts = t - (K - 1 - tap) * a.dil;
-            const bool ok = (t < T) && ts >= 0;
-            okh[tap] = ok;
-            const int vt = ok ? (4 * hi * T + ts) * 4 : 0;  // dead lanes read a valid dummy address
-            WN_UNROLL
-            for (int s = 0; s < 32; ++s) xh[tap][s] = wn_buf_load(Xr, vt, kappa64(s, 0) * T4);
+// bf16 matrix cores, 3-way operand split, six products, fp32 accumulate: fp32-equivalent, see wn_gemm6.hip.
+struct FwdBf16x3 {
+    static constexpr int WD_BLK = 3 * 128 * 32, WR_BLK = 3 * 64 * 32;  // bytes of one 16-k block
+    // K = 3: the three taps alone fill the LDS (144 KB), so the res-1x1 fragments (24 KB per layer, L2 resident) are read
+    // from the layer's pre-split image in global memory, one 16-k block ahead of their MFMAs (RG = "res from global")
+    static constexpr bool res_from_global(int K) { return K >= 3; }
+    static constexpr int vec_off(int K) { return res_from_global(K) ? K * 4 * WD_BLK : fwd_image_bytes(K); }
+    static constexpr int lds_bytes(int K) { return vec_off(K) + WN_FWD_VEC_FLOATS * 4; }
+
+    const char* Wd;      // [K*4 blocks][piece][128 rows][16 k] bf16
+    const char* Wr;      // [4 blocks][piece][64 rows][16 k] bf16   (not with RG)
+    const float* wimg;
+    int li, hi;
+
+    template <int K>
+    __device__ __forceinline__ float* stage(char* smem, const FwdArgs& a) {
+        Wd = smem;
+        Wr = smem + K * 4 * WD_BLK;
+        wimg = a.wimg;
+        li = threadIdx.x & 31;
+        hi = (threadIdx.x & 63) >> 5;
+        if (res_from_global(K)) {   // (the launcher only takes this kernel with an image)
+            copy_image_to_lds(smem, a.wimg, K * 4 * WD_BLK);
+            WN_WAIT_VMCNT(0);
+        } else if (a.wimg != nullptr) {
+            copy_image_to_lds(smem, a.wimg, fwd_image_bytes(K));   // pre-split once per step (wn_fused_pack_images)
+            WN_WAIT_VMCNT(0);
+        } else {
+            fill_fwd_image<K>(smem, smem + K * 4 * WD_BLK, a.wd_f, a.wres_f, threadIdx.x, WN_FT);
         }
-    };
-    constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};   // small terms first: h l, l h, h h
-    f32x16 acc[4];
-    // one tap: the 4 k-blocks of 16 channels against the tap's 128 weight rows
-    auto tap_mfmas = [&](const float (&xr)[32], bool ok, int tapblk, float sc) {
+        float* cv = reinterpret_cast<float*>(smem + vec_off(K));
+        fwd_stage_vectors(cv, a);
+        __syncthreads();
+        return cv;
+    }
+    // the six products of two rows' weight pieces with the operand's pieces, small terms first
+    static __device__ __forceinline__ void products(const wn_f4 (&af)[2][3], const wn_f4 (&bf)[3], f32x16& c0, f32x16& c1) {
+        constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+        WN_UNROLL
+        for (int t6 = 0; t6 < WN_EXP_NPROD; ++t6) {
+            c0 = mfma_bf16(af[0][PA[t6]], bf[PB[t6]], c0);
+            c1 = mfma_bf16(af[1][PA[t6]], bf[PB[t6]], c1);
+        }
+    }
+    template <int K>
+    __device__ __forceinline__ void tap(f32x16 (&acc)[4], const float (&x)[32], bool ok, int tapblk) {
         WN_UNROLL
         for (int kb = 0; kb < 4; ++kb) {
             float x8[8];
             WN_UNROLL
-            for (int e = 0; e < 8; ++e) x8[e] = ok ? xr[8 * kb + e] : 0.0f;
+            for (int e = 0; e < 8; ++e) x8[e] = ok ? x[8 * kb + e] : 0.0f;
+            wn_f4 bf[3];
+            split8(x8, bf);
+            const char* Wl = Wd + (tapblk * 4 + kb) * WD_BLK + wn_frag_off(li, hi);
+            WN_UNROLL
+            for (int qh = 0; qh < 4; qh += 2) {  // two row tiles at a time (register budget)
+                wn_f4 af[2][3];
+                WN_UNROLL
+                for (int q = 0; q < 2; ++q) {
+                    WN_UNROLL
+                    for (int p = 0; p < 3; ++p) af[q][p] = *reinterpret_cast<const wn_f4*>(Wl + p * (128 * 32) + (qh + q) * 1024);
+                }
+                products(af, bf, acc[qh], acc[qh + 1]);
+            }
+        }
+    }
+    __device__ __forceinline__ float preact(float acc, float add) const { return acc + add; }
+    template <int K>
+    __device__ __forceinline__ void res(const f32x16 (&z)[2], const f32x16 (&xb)[2], f32x16 (&out)[2]) {
+        constexpr bool RG = res_from_global(K);
+        out[0] = f32x16_zero();
+        out[1] = f32x16_zero();
+        const wn_rsrc_t Ir = wn_make_buf(wimg, (unsigned)(RG ? fwd_image_bytes(K) : 16));
+        const int vfrag = wn_frag_off(li, hi);
+        auto res_frags = [&](int kb, wn_f4 (&af)[2][3]) {
+            WN_UNROLL
+            for (int q = 0; q < 2; ++q) {
+                WN_UNROLL
+                for (int p = 0; p < 3; ++p) {
+                    if (RG) {
+                        const float4 f = wn_buf_load4(Ir, vfrag, (unsigned)(K * 4 * WD_BLK + kb * WR_BLK + p * (64 * 32) + q * 1024));
+                        af[q][p] = wn_f4{f.x, f.y, f.z, f.w};
+                    } else {
+                        af[q][p] = *reinterpret_cast<const wn_f4*>(Wr + kb * WR_BLK + vfrag + p * (64 * 32) + q * 1024);
+                    }
+                }
+            }
+        };
+        wn_f4 afr[2][2][3];   // two sets: with RG the fragments of block kb + 1 are in flight under the MFMAs of block kb
+        res_frags(0, afr[0]);
+        WN_UNROLL
+        for (int kb = 0; kb < 4; ++kb) {
+            float x8[8];
+            WN_UNROLL
+            for (int e = 0; e < 8; ++e) x8[e] = z[(8 * kb + e) >> 4][(8 * kb + e) & 15];
+            wn_f4 bf[3];
+            split8(x8, bf);
+            if (kb + 1 < 4) res_frags(kb + 1, afr[(kb + 1) & 1]);
+            products(afr[kb & 1], bf, out[0], out[1]);
+        }
+        WN_UNROLL
+        for (int q = 0; q < 2; ++q) {
+            WN_UNROLL
+            for (int r = 0; r < 16; ++r) out[q][r] += xb[q][r];
+        }
+    }
+};
+
+// FP16 matrix cores with a two-piece operand split (WN_FLAG_FUSED_F16PAIR): x ~ h + l with two fp16 pieces (11 + 11 significand
+// bits), the three products h h + h l + l h on v_mfma_f32_32x32x16_f16, fp32 accumulate -- ~2^-22 |w x| per product (the rounding
+// of an fp32 running sum over the 128 - 192 terms of a tap contraction) at HALF the matrix work of the six bf16 products, a weight
+// image of 80 KB instead of 120 KB (K = 3: 112 KB, so the res-1x1 fragments are back in the LDS), and 6 instead of 11 VALU
+// instructions per operand pair.  fp16 has 5 exponent bits, so everything is BLOCK-SCALED by powers of two (exact):
+//   * each weight image by 2^ew with max |w| 2^ew in [2^11, 2^12) (wn_fused_pack_images16 measures the maximum per layer);
+//   * each 64-channel x 32-sample operand tile by 2^e with max |x| 2^e in [2^13, 2^14) -- the wave reduces the maximum of the tile
+//     it holds in registers; the taps of a tile share ONE scale (the smallest so far: the accumulators are multiplied down when a
+//     later tap has larger values), so nothing can leave fp16's range whatever the magnitudes are, and an element 2^-18 below the
+//     tile's maximum still has all 22 bits (smaller ones keep 2^-25 of the maximum in absolute terms);
+//   * z in (-1, 1) by 2^13.
+// The inverse scales are folded into the additions that follow the MFMAs (gate pre-activation, residual): no extra pass.
+struct FwdF16x2 {
+    static constexpr int WD_BLK = 2 * 128 * 32, WR_BLK = 2 * 64 * 32;  // bytes of one 16-k block (two fp16 pieces)
+    static constexpr int lds_bytes(int K) { return fwd16_image_bytes(K) + WN_FWD_VEC_FLOATS * 4; }
+
+    const char* Wd;      // [K*4 blocks][piece][128 rows][16 k]
+    const char* Wr;      // [4 blocks][piece][64 rows][16 k]
+    float inv_wd, inv_wr;   // {1 / 2^ew_taps, 1 / 2^ew_res}: the image's tail (padded to 64 bytes)
+    float sc, inv;       // this tile's block scale so far; accumulators -> true pre-activations
+    int li, hi;
+
+    template <int K>
+    __device__ __forceinline__ float* stage(char* smem, const FwdArgs& a) {
+        Wd = smem;
+        Wr = smem + K * 4 * WD_BLK;
+        li = threadIdx.x & 31;
+        hi = (threadIdx.x & 63) >> 5;
+        float* tail = reinterpret_cast<float*>(smem + fwd16_image_bytes(K) - 64);
+        float* cv = tail + 16;
+        copy_image_to_lds(smem, a.wimg, fwd16_image_bytes(K) - 64);   // (a multiple of 1024)
+        if (threadIdx.x < 2) tail[threadIdx.x] = a.wimg[(fwd16_image_bytes(K) - 64) / 4 + threadIdx.x];
+        fwd_stage_vectors(cv, a);
+        WN_WAIT_VMCNT(0);
+        __syncthreads();
+        inv_wd = tail[0];
+        inv_wr = tail[1];
+        return cv;
+    }
+    static __device__ __forceinline__ void products(const wn_f4 (&af)[2][2], const wn_f4 (&bf)[2], f32x16& c0, f32x16& c1) {
+        constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};   // small terms first: h l, l h, h h
+        WN_UNROLL
+        for (int t3 = 0; t3 < 3; ++t3) {
+            c0 = mfma_f16(af[0][PA[t3]], bf[PB[t3]], c0);
+            c1 = mfma_f16(af[1][PA[t3]], bf[PB[t3]], c1);
+        }
+    }
+    template <int K>
+    __device__ __forceinline__ void tap(f32x16 (&acc)[4], const float (&x)[32], bool ok, int tapblk) {
+        // The tile's block scale: the smallest of its taps' scales so far; the accumulators follow it down (exact: powers of two).
+        const float st = wn_pow2_scale(wave_amax32(x, ok), 14);
+        if (tapblk == 0) {
+            sc = st;
+        } else {
+            const float sn = fminf(sc, st);
+            const float ratio = sn / sc;     // <= 1
+            WN_UNROLL
+            for (int q = 0; q < 4; ++q) {
+                WN_UNROLL
+                for (int r = 0; r < 16; ++r) acc[q][r] *= ratio;
+            }
+            sc = sn;
+        }
+        WN_UNROLL
+        for (int kb = 0; kb < 4; ++kb) {
+            float x8[8];
+            WN_UNROLL
+            for (int e = 0; e < 8; ++e) x8[e] = ok ? x[8 * kb + e] : 0.0f;
             wn_f4 bf[2];
             split8h(x8, sc, bf);
             const char* Wl = Wd + (tapblk * 4 + kb) * WD_BLK + wn_frag_off(li, hi);
@@ -1194,202 +999,131 @@ __global__ __launch_bounds__(WN_LB) void k_resblock_fwd_h(FwdArgs a) {
                     WN_UNROLL
                     for (int p = 0; p < 2; ++p) af[q][p] = *reinterpret_cast<const wn_f4*>(Wl + p * (128 * 32) + (qh + q) * 1024);
                 }
-                WN_UNROLL
-                for (int t3 = 0; t3 < 3; ++t3) {
-                    acc[qh] = mfma_f16(af[0][PA[t3]], bf[PB[t3]], acc[qh]);
-                    acc[qh + 1] = mfma_f16(af[1][PA[t3]], bf[PB[t3]], acc[qh + 1]);
-                }
+                products(af, bf, acc[qh], acc[qh + 1]);
             }
         }
-    };
-
-    int tile_v = WN_UNIFORM(walk.first);
-    int tcount = 0;
-    (void)tcount;
-    if (K > 1 && tile_v < tile_end) issue_hist(tile_v);
-    while (tile_v < tile_end) {
-        WN_STAMP(0);
-        const int tile = WN_UNIFORM(tile_v);
-        const int b = tile / tiles_per_b;
-        const int t = (tile - b * tiles_per_b) * 32 + li;
-        const bool inb = t < T;
-        const int tc = inb ? t : T - 1;
-        const int vcur = inb ? (4 * hi * T + t) * 4 : 0;
-
-        float xc[32];
-        {
-            const wn_rsrc_t Xr = wn_make_buf(a.X + (long)b * 64 * T, slab);
+        if (tapblk == K - 1) inv = inv_wd / sc;   // (both powers of two)
+    }
+    __device__ __forceinline__ float preact(float acc, float add) const { return fmaf(acc, inv, add); }
+    // z (in (-1, 1)) is scaled by 2^13
+    template <int K>
+    __device__ __forceinline__ void res(const f32x16 (&z)[2], const f32x16 (&xb)[2], f32x16 (&out)[2]) {
+        out[0] = f32x16_zero();
+        out[1] = f32x16_zero();
+        const int vfrag = wn_frag_off(li, hi);
+        WN_UNROLL
+        for (int kb = 0; kb < 4; ++kb) {
+            float x8[8];
             WN_UNROLL
-            for (int tap = KP; tap + 1 < K; ++tap) {   // (K = 3) the history taps that are not requested a tile ahead
-                const int ts = t - (K - 1 - tap) * a.dil;
-                const bool ok = inb && ts >= 0;
-                okh[tap] = ok;
-                const int vt = ok ? (4 * hi * T + ts) * 4 : 0;
-                WN_UNROLL
-                for (int s = 0; s < 32; ++s) xh[tap][s] = wn_buf_load(Xr, vt, kappa64(s, 0) * T4);
-            }
-            WN_UNROLL
-            for (int s = 0; s < 32; ++s) xc[s] = wn_buf_load(Xr, vcur, kappa64(s, 0) * T4);
-        }
-        WN_SCHED_BARRIER();
-        WN_PRIO(WN_PRIO_MFMA);
-        WN_UNROLL
-        for (int q = 0; q < 4; ++q) acc[q] = f32x16_zero();
-        // The tile's block scale: the smallest of its taps' scales so far; the accumulators follow it down (exact: powers of two).
-        float sc = 0.0f;
-        WN_UNROLL
-        for (int tap = 0; tap + 1 < K; ++tap) {
-            const float st = wn_pow2_scale(wave_amax32(xh[tap], okh[tap]), 14);
-            if (tap == 0) {
-                sc = st;
-            } else {
-                const float sn = fminf(sc, st);
-                const float ratio = sn / sc;     // <= 1
-                WN_UNROLL
-                for (int q = 0; q < 4; ++q) {
-                    WN_UNROLL
-                    for (int r = 0; r < 16; ++r) acc[q][r] *= ratio;
-                }
-                sc = sn;
-            }
-            tap_mfmas(xh[tap], okh[tap], tap, sc);
-        }
-        WN_STAMP(1);  // after history-tap MFMAs
-        // aux / gate inputs (frame rate, L2 resident), first 32 gate channels
-        const int fr = tc / a.U;
-        const float upw_j = a.upw[tc - fr * a.U];
-        const wn_rsrc_t Gr = wn_make_buf(a.G + (long)b * a.g_bstride, (unsigned)(128 * F4));
-        const int vg = (4 * hi * a.F + fr) * 4;
-        float ga[16], gg[16];
-        WN_UNROLL
-        for (int r = 0; r < 16; ++r) {
-            ga[r] = wn_buf_load(Gr, vg, mfma32_row(r, 0) * F4);
-            gg[r] = wn_buf_load(Gr, vg, (mfma32_row(r, 0) + 64) * F4);
-        }
-        WN_SCHED_BARRIER();
-        {   // current tap; xc is also the residual input, already in D layout
-            const float st = wn_pow2_scale(wave_amax32(xc, inb), 14);
-            if (K > 1) {
-                const float sn = fminf(sc, st);
-                const float ratio = sn / sc;
-                WN_UNROLL
-                for (int q = 0; q < 4; ++q) {
-                    WN_UNROLL
-                    for (int r = 0; r < 16; ++r) acc[q][r] *= ratio;
-                }
-                sc = sn;
-            } else {
-                sc = st;
-            }
-            tap_mfmas(xc, inb, K - 1, sc);
-        }
-        const float inv = inv_wd / sc;   // (both powers of two) accumulators -> true pre-activations
-        WN_SCHED_BARRIER();
-        WN_PRIO(WN_PRIO_GATE);
-        WN_STAMP(2);  // after current-tap MFMAs
-        f32x16 xb2[2];
-        if (a.Xnext != nullptr) {
-            const float* rbl = rb + 4 * hi;
+            for (int e = 0; e < 8; ++e) x8[e] = z[(8 * kb + e) >> 4][(8 * kb + e) & 15];
+            wn_f4 bf[2];
+            split8h(x8, 8192.0f, bf);
+            wn_f4 afr[2][2];
             WN_UNROLL
             for (int q = 0; q < 2; ++q) {
                 WN_UNROLL
-                for (int r = 0; r < 16; ++r)
-                    xb2[q][r] = (inb ? xc[16 * q + r] : 0.0f) + rbl[32 * q + mfma32_row(r, 0)];
+                for (int p = 0; p < 2; ++p) afr[q][p] = *reinterpret_cast<const wn_f4*>(Wr + kb * WR_BLK + vfrag + p * (64 * 32) + q * 1024);
             }
-            WN_PIN2(xb2[0], xb2[1]);
+            products(afr, bf, out[0], out[1]);
         }
-        const int next_v = tile_v + step;
-        if (K > 1 && next_v < tile_end) issue_hist(next_v);
-        // gate (reference wavenet.py:529-532): P = conv + w[j]*G[row][f] + c[row]; saved for backward
-        const wn_rsrc_t Sr = wn_make_buf(a.S + (long)b * 64 * T, slab);
-        const bool keep_g = a.Gt != nullptr;
-        const wn_rsrc_t Gtr = wn_make_buf((keep_g ? a.Gt : a.S) + (long)b * 64 * T, slab);
-        const wn_rsrc_t Zr = wn_make_buf(a.Z + (long)b * 64 * T, slab);
-        const float* cvl = cv + 4 * hi;
-        f32x16 z[2];
-        const int vst = inb ? vcur : WN_VOFF_DEAD;
-        auto gate_phase = [&](auto keep_tag) {
-        constexpr bool KEEP_G = decltype(keep_tag)::value;
+        const float invr = inv_wr * (1.0f / 8192.0f);
         WN_UNROLL
         for (int q = 0; q < 2; ++q) {
             WN_UNROLL
-            for (int r = 0; r < 16; ++r) {
-                const int row0 = 32 * q + mfma32_row(r, 0);  // + 4*hi is in the per-lane offsets
-                const float pa = fmaf(acc[q][r], inv, upw_j * ga[r] + cvl[row0]);
-                const float pg = fmaf(acc[q + 2][r], inv, upw_j * gg[r] + cvl[row0 + 64]);
-                if (q == 0) {
-                    ga[r] = wn_buf_load(Gr, vg, (32 + mfma32_row(r, 0)) * F4);
-                    gg[r] = wn_buf_load(Gr, vg, (96 + mfma32_row(r, 0)) * F4);
-                }
-                const float s = wn_sigmoid(pa);
-                const float g = wn_tanh(pg);
-                const float zz = s * g;
-                z[q][r] = zz;
-                wn_buf_store(Sr, s, vst, row0 * T4);
-                if (KEEP_G) wn_buf_store(Gtr, g, vst, row0 * T4);
-                wn_buf_store(Zr, zz, vst, row0 * T4);
-            }
+            for (int r = 0; r < 16; ++r) out[q][r] = fmaf(out[q][r], invr, xb[q][r]);
         }
-        };
-        if (keep_g) gate_phase(std::true_type{});
-        else gate_phase(std::false_type{});
-        WN_STAMP(3);  // after gate math + S/Gt/Z stores issued
+    }
+};
+
+// Software pipeline (per wave, per 32-sample tile):
+//   history-tap operands xh : issued before the res MFMAs of the PREVIOUS tile (cross-tile prefetch)
+//   current-tap operands xc : issued at tile start, land under the history-tap MFMAs
+//   aux/gate inputs         : first half issued before the current-tap MFMAs, second half
+//                             before the gate math of the first half
+template <int K, class Arith>
+__global__ __launch_bounds__(WN_LB) void k_resblock_fwd(FwdArgs a) {
+    WN_DYN_SMEM(smem_raw);
+    fwd_timing_begin(a);
+    Arith ar;
+    const float* cv = ar.template stage<K>(smem_raw, a);
+    fwd_timing_staged(a);
+    // De-phase the two waves that share a SIMD (waves w and w+4): started together they would run
+    // their MFMA phases and their gate/store phases in lock step and leave the matrix pipe idle
+    // during the latter; half a tile of head start makes one wave's VALU/VMEM phase coincide with
+    // the other's MFMA phase.
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    (void)lane; (void)wave;
+    const FwdLane g = fwd_lane(a);
+    const TileWalk walk = tile_walk(g.ntiles, threadIdx.x >> 6);
+    const int step = WN_UNIFORM(walk.step), tile_end = WN_UNIFORM(walk.end);
+    constexpr int KH = (K > 1) ? (K - 1) : 1;  // history taps (shift > 0)
+    // history taps requested one tile ahead (across the gate phase of the previous tile).  K = 3 keeps only the oldest tap
+    // that way and requests the middle one at tile start with the current tap: 32 registers less across the gate phase.
+    constexpr int KP = (K >= 3) ? 1 : K - 1;
+
+    float xh[KH][32];
+    bool okh[KH];
+    int tile_v = WN_UNIFORM(walk.first);
+    int tcount = 0;
+    (void)tcount;
+    if (K > 1 && tile_v < tile_end) fwd_issue_hist<K, 0, KP>(a, g, WN_UNIFORM(tile_v), xh, okh);
+    while (tile_v < tile_end) {
+        WN_STAMP(0);
+        const int tile = WN_UNIFORM(tile_v);
+        const FwdTile c = fwd_tile(g, tile);
+        float xc[32];
+        fwd_issue_hist<K, KP, K - 1>(a, g, tile, xh, okh);   // (K = 3) the history taps that are not requested a tile ahead
+        fwd_issue_cur(a, g, c, xc);
         WN_SCHED_BARRIER();
         WN_PRIO(WN_PRIO_MFMA);
-        // res 1x1 + residual; z (in (-1, 1): scaled by 2^13) is consumed straight from the accumulator registers
+        f32x16 acc[4];
+        WN_UNROLL
+        for (int q = 0; q < 4; ++q) acc[q] = f32x16_zero();
+        WN_UNROLL
+        for (int tap = 0; tap + 1 < K; ++tap) ar.template tap<K>(acc, xh[tap], okh[tap], tap);
+        WN_STAMP(1);  // after history-tap MFMAs
+        FwdAux aux;
+        fwd_aux_issue(a, g, c, aux);
+        WN_SCHED_BARRIER();
+        ar.template tap<K>(acc, xc, c.inb, K - 1);
+        WN_SCHED_BARRIER();
+        WN_PRIO(WN_PRIO_GATE);
+        WN_STAMP(2);  // after current-tap MFMAs
+        // residual input + bias, formed NOW: xc dies here, so that in a chain its registers simply become the next tile's
+        // history operands (no second copy of the tile is ever live).  The sums are ADDED to the res products after the last
+        // MFMA instead of being the accumulators' initial value -- products aligned against a large initial value lose their
+        // low bits with a consistent sign, see k_chain64s.
+        f32x16 xb2[2];
         if (a.Xnext != nullptr) {
-            f32x16 racc[2];
-            racc[0] = f32x16_zero();
-            racc[1] = f32x16_zero();
-            const int vfrag = wn_frag_off(li, hi);
-            WN_UNROLL
-            for (int kb = 0; kb < 4; ++kb) {
-                float x8[8];
-                WN_UNROLL
-                for (int e = 0; e < 8; ++e) x8[e] = z[(8 * kb + e) >> 4][(8 * kb + e) & 15];
-                wn_f4 bf[2];
-                split8h(x8, 8192.0f, bf);
-                wn_f4 afr[2][2];
-                WN_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    WN_UNROLL
-                    for (int p = 0; p < 2; ++p) afr[q][p] = *reinterpret_cast<const wn_f4*>(Wr + kb * WR_BLK + vfrag + p * (64 * 32) + q * 1024);
-                }
-                WN_UNROLL
-                for (int t3 = 0; t3 < 3; ++t3) {
-                    racc[0] = mfma_f16(afr[0][PA[t3]], bf[PB[t3]], racc[0]);
-                    racc[1] = mfma_f16(afr[1][PA[t3]], bf[PB[t3]], racc[1]);
-                }
-            }
-            const float invr = inv_wr * (1.0f / 8192.0f);
-            {
-                const wn_rsrc_t Xn = wn_make_buf(a.Xnext + (long)b * 64 * T, slab);
-                WN_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    WN_UNROLL
-                    for (int r = 0; r < 16; ++r)
-                        wn_buf_store(Xn, fmaf(racc[q][r], invr, xb2[q][r]), vst, (32 * q + mfma32_row(r, 0)) * T4);
-                }
-            }
+            fwd_resid_bias(g, c, xc, cv + 128, xb2);
+            // pin: the sums exist from here on (machine sinking would otherwise move them below the branch and keep xc alive)
+            WN_PIN2(xb2[0], xb2[1]);
+        }
+        // Prefetch the history-tap operands of this wave's next tile NOW, i.e. before the stores of the gate phase: vmcnt is
+        // one in-order counter for loads AND stores, so loads issued behind the 64 S/Z stores could only be waited for together
+        // with those stores' acknowledgements.  (A variant that kept the history tap of a d >= 32 layer in registers across
+        // "tile chains" measured slower -- 60 B/lane of scratch and 16-tile runs instead of one contiguous span:
+        // profiles/r02/ab_probe_fwd_chain.txt.)
+        const int next_v = tile_v + step;
+        if (K > 1 && next_v < tile_end) fwd_issue_hist<K, 0, KP>(a, g, WN_UNIFORM(next_v), xh, okh);
+        f32x16 z[2];
+        fwd_gate_phase(a, g, c, acc, aux, cv, z, [&](float v, float add) { return ar.preact(v, add); });
+        WN_STAMP(3);  // after gate math + S/Z stores issued
+        WN_SCHED_BARRIER();
+        WN_PRIO(WN_PRIO_MFMA);
+        // res 1x1 + residual; z is consumed straight from the accumulator registers
+        if (a.Xnext != nullptr) {
+            f32x16 out[2];
+            ar.template res<K>(z, xb2, out);
+            fwd_store_xnext(a, g, c, out);
         }
         WN_PRIO(WN_PRIO_GATE);
         WN_STAMP(4);  // tile done
         ++tcount;
         tile_v = next_v;
     }
-#ifdef WN_TIMING
-    if (a.dbg && blockIdx.x == 0 && lane == 0) {
-        __builtin_amdgcn_s_waitcnt(0);
-        a.dbg[(wave * 4) * 16 + 8] = (long long)__builtin_amdgcn_s_memrealtime();
-        a.dbg[(wave * 4) * 16 + 9] = (long long)__builtin_readcyclecounter();
-    }
-    if (a.dbg && lane == 0) {
-        __builtin_amdgcn_s_waitcnt(0);
-        if (wave == 0) a.dbg[512 + blockIdx.x * 4 + 1] = (long long)__builtin_amdgcn_s_memrealtime();
-        if (wave == 7) a.dbg[512 + blockIdx.x * 4 + 2] = (long long)__builtin_amdgcn_s_memrealtime();
-        if (wave == 0) a.dbg[512 + blockIdx.x * 4 + 3] = tcount;
-    }
-#endif
+    fwd_timing_end(a, tcount);
 }
 
 template <int K>
@@ -1398,34 +1132,33 @@ static int launch_fwd(const FwdArgs& a, int split, wn_stream_t st) {
     const long nblk = balanced_blocks(ntiles);
     if (split == 2) {   // fp16 pair split (needs the two-piece image of wn_fused_pack_images16)
         if (a.wimg == nullptr) return 1;
-        const size_t lds_h = (size_t)fwd16_image_bytes(K) + 192 * sizeof(float);
-        if (wn_dyn_lds<k_resblock_fwd_h<K>>(lds_h)) return 1;
-        WN_LAUNCH((k_resblock_fwd_h<K>), dim3((unsigned)nblk), dim3(WN_FT), lds_h, st, a);
+        constexpr size_t lds = FwdF16x2::lds_bytes(K);
+        if (wn_dyn_lds<k_resblock_fwd<K, FwdF16x2>>(lds)) return 1;
+        WN_LAUNCH((k_resblock_fwd<K, FwdF16x2>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
         return 0;
     }
-    // split arithmetic: taps (+ res 1x1 for K <= 2; K = 3 reads those fragments from the global image) + cvec / bias
-    const size_t lds_s = (size_t)K * 4 * (3 * 128 * 32) + (K >= 3 ? 0 : 4 * (3 * 64 * 32)) + 192 * sizeof(float);
-    if (split && lds_s <= 160 * 1024 && (K < 3 || a.wimg != nullptr)) {  // (K = 3 without a weight image: the f32 MFMA kernel)
-        if (wn_dyn_lds<k_resblock_fwd_s<K>>(lds_s)) return 1;
-        WN_LAUNCH((k_resblock_fwd_s<K>), dim3((unsigned)nblk), dim3(WN_FT), lds_s, st, a);
+    if (split && FwdBf16x3::lds_bytes(K) <= 160 * 1024 && (K < 3 || a.wimg != nullptr)) {  // (K = 3 without a weight image: the f32 MFMA kernel)
+        constexpr size_t lds = FwdBf16x3::lds_bytes(K);
+        if (wn_dyn_lds<k_resblock_fwd<K, FwdBf16x3>>(lds)) return 1;
+        WN_LAUNCH((k_resblock_fwd<K, FwdBf16x3>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
         return 0;
     }
-    const size_t lds = ((size_t)K * 64 * 128 + 64 * 64 + 192) * sizeof(float);
-    if (wn_dyn_lds<k_resblock_fwd<K>>(lds)) return 1;
-    WN_LAUNCH((k_resblock_fwd<K>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
+    constexpr size_t lds = fwd_f32_lds_bytes(K);
+    if (wn_dyn_lds<k_resblock_fwd_f32<K>>(lds)) return 1;
+    WN_LAUNCH((k_resblock_fwd_f32<K>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
     return 0;
 }
 
 int wn_fused_resblock_fwd(const float* wd_f, const float* wres_f, const float* cvec, const float* res_bias, const float* X,
-                          const float* G, long g_bstride, const float* upw, float* Xnext, float* S, float* Gt, float* Z, int B,
-                          int T, int K, int dilation, int U, int F, int split, const float* wimg, wn_stream_t st) {
+                          const float* G, long g_bstride, const float* upw, float* Xnext, float* S, float* Z, int B, int T, int K,
+                          int dilation, int U, int F, int split, const float* wimg, wn_stream_t st) {
     WN_PROF("fused_resblock_fwd", 2.0 * (double)B * T * (K * 64.0 * 128.0 + (Xnext ? 64.0 * 64.0 : 0.0)),
-            4.0 * (double)B * T * 64.0 * ((Xnext ? 4.0 : 3.0) + (Gt ? 1.0 : 0.0)), st);  // X in; S, (Gt,) Z (, Xnext) out
+            4.0 * (double)B * T * 64.0 * (Xnext ? 4.0 : 3.0), st);  // X in; S, Z (, Xnext) out
     FwdArgs a;
     a.wimg = split ? wimg : nullptr;
     a.wd_f = wd_f; a.wres_f = wres_f; a.cvec = cvec; a.res_bias = res_bias;
     a.X = X; a.G = G; a.g_bstride = g_bstride; a.upw = upw;
-    a.Xnext = Xnext; a.S = S; a.Gt = Gt; a.Z = Z;
+    a.Xnext = Xnext; a.S = S; a.Z = Z;
     a.B = B; a.T = T; a.dil = dilation; a.U = U; a.F = F;
 #ifdef WN_TIMING
     a.dbg = g_dbg;
@@ -2033,7 +1766,7 @@ static __device__ __forceinline__ void split8v(const float (&x)[8], bool ok, wn_
 // HEAD = true: the top of the chain.  The last layer's residual output is dead (wavenet.py:231-238), so dP_{L-1} is the gate'
 // epilogue alone on dZs_{L-1} (which bwd_dz_skip_all now produces for ALL layers): no taps, no Wres^T, no dX -- its own
 // instantiation, so that the main one compiles exactly as before.
-// H16 (round 6, WN_FLAG_CHAIN_F16PAIR): the fp16 pair split, block-scaled like k_resblock_fwd_h -- two fp16 pieces per operand, three
+// H16 (round 6, WN_FLAG_CHAIN_F16PAIR): the fp16 pair split, block-scaled like FwdF16x2 -- two fp16 pieces per operand, three
 // products; the weight images by the power of two of their own maximum (wn_fused_pack_images16); the dP operand of a tile by the
 // power of two that puts the maximum of the producer tiles it reads at 2^14 (every launch leaves max |dP| per 32-sample tile beside
 // the tensor it writes: `amaxPm`; the consumer looks up the tiles its shifted taps cover: `amaxP`), the dX operand of the res-1x1

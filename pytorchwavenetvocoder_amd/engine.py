@@ -46,7 +46,7 @@ from . import _lib
 # benchmark's own instance against the reference module (tests/test_gpu_fullsize.py, bench.py `parity`): logits 4.9e-6 (six
 # products 5.5e-6), worst gradient 8.3e-6 (8.2e-6); against the fp64 evaluation of the same step the worst gradient is 6.2e-6 --
 # closer than the reference's own fp32 step (8.3e-6; profiles/r06/adam_gate_study.txt).
-# WN_FLAG_FUSED_F16PAIR (round 6, DEFAULT): the fused 64-channel FORWARD block (taps, gate, res 1x1: k_resblock_fwd_h) on the same
+# WN_FLAG_FUSED_F16PAIR (round 6, DEFAULT): the fused 64-channel FORWARD block (taps, gate, res 1x1: k_resblock_fwd<K, FwdF16x2>) on the same
 # split, block-scaled -- every weight image and every 64 x 32 operand tile by the power of two that puts its maximum at 2^12 /
 # 2^14, so no magnitude leaves fp16's range and no redo exists.  Same box: 8.64 -> 8.43 ms per step (forward blocks 1.79 -> 1.55 ms,
 # profiles/r06/abk_fused_f16.txt).  The backward data chain (k_chain64s) keeps six bf16 products.

@@ -144,6 +144,19 @@ def run_oracle_vs_engine(cfg_tuple, B, T, seed, lib, device, flags=None, scale=0
     return err, worst
 
 
+# The fused forward block (csrc/wn_fused.hip): each arithmetic x each tap count on the smallest shape at which the tile logic can
+# still go wrong -- T = 48 is one full and one half-full 32-sample tile per sequence, two sequences make the tile walk cross a
+# batch boundary, the last layer has no Xnext and the others do, dilation 4 reaches zero history and a previous tile.
+FWD_BLOCK_CONFIGS = {1: (64, 6, 64, 32, 3, 1, 1, 16), 2: (64, 6, 64, 32, 2, 2, 2, 16), 3: (64, 6, 64, 32, 3, 1, 3, 16)}
+FWD_BLOCK_ARITHMETICS = ("exact_f32", "bf16x3", "f16x2")
+
+
+def run_fwd_block_case(arith, K, lib, device):
+    from pytorchwavenetvocoder_amd.engine import SIX_PRODUCT_FLAGS
+    flags = SIX_PRODUCT_FLAGS | {"exact_f32": _lib.FLAG_EXACT_MFMA, "bf16x3": 0, "f16x2": _lib.FLAG_FUSED_F16PAIR}[arith]
+    return run_oracle_vs_engine(FWD_BLOCK_CONFIGS[K], 2, 48, 41, lib, device, flags=flags, scale=0.2)
+
+
 def gemm_reference(M, N, K, A, B):
     return A @ B
 

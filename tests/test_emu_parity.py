@@ -99,6 +99,12 @@ def test_ragged_T_and_odd_channels():
     PC.run_oracle_vs_engine((37, 7, 12, 20, 3, 1, 3, 7), 2, 91, 6, emu_library(), "cpu")
 
 
+@pytest.mark.parametrize("K", [1, 2, 3])
+@pytest.mark.parametrize("arith", PC.FWD_BLOCK_ARITHMETICS)
+def test_fused_forward_block_arithmetic_x_taps(arith, K):
+    PC.run_fwd_block_case(arith, K, emu_library(), "cpu")
+
+
 def test_vector_staging_paths():
     """T large enough for interior 128-wide tiles: exercises the 16-byte staging path of the GEMM (and its
     per-tile fallback to scalar loads for taps whose shift is not a multiple of 4)."""
@@ -1116,7 +1122,7 @@ def test_split_contractions_by_the_fp16_pair_split_and_their_redo():
 
 
 def test_fused_forward_block_on_the_block_scaled_fp16_pair_split():
-    """WN_FLAG_FUSED_F16PAIR (csrc/wn_fused.hip k_resblock_fwd_h): the fused 64-channel residual block with two fp16 pieces per
+    """WN_FLAG_FUSED_F16PAIR (csrc/wn_fused.hip k_resblock_fwd<K, FwdF16x2>): the fused 64-channel residual block with two fp16 pieces per
     operand and three products, every weight image and every 64 x 32 operand tile scaled by the power of two that puts its
     maximum at 2^12 / 2^14.  Golden cases (kernel_size 2 and 3) and the oracle at the gates of every mode; against the six-product
     forward within 2e-6 of the largest logit; and MAGNITUDES: the same model with its front convolution scaled so that the

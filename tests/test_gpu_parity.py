@@ -56,6 +56,12 @@ def test_ragged_and_odd_shapes_vs_oracle():
     PC.run_oracle_vs_engine((48, 9, 96, 160, 2, 1, 2, 4), 1, 72, 7, _lib(), DEV)
 
 
+@pytest.mark.parametrize("K", [1, 2, 3])
+@pytest.mark.parametrize("arith", PC.FWD_BLOCK_ARITHMETICS)
+def test_fused_forward_block_arithmetic_x_taps(arith, K):
+    PC.run_fwd_block_case(arith, K, _lib(), DEV)
+
+
 def test_vector_staging_paths():
     from pytorchwavenetvocoder_amd import _lib as L
     PC.run_oracle_vs_engine((64, 8, 64, 64, 3, 1, 2, 8), 1, 256, 9, _lib(), DEV)

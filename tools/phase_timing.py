@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-phase cycle stamps of the fused forward kernel (k_resblock_fwd) on the GPU.
+"""Per-phase cycle stamps of the fused forward kernels (k_resblock_fwd<K, Arith>, k_resblock_fwd_f32<K>) on the GPU.
 
 Builds an instrumented copy of the library (wn_fused.hip compiled with -DWN_TIMING, which adds
 s_memtime / s_memrealtime stamps at the phase boundaries of block 0 and entry/exit stamps for every
