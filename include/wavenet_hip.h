@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 12
+#define WN_ABI_VERSION 13
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -286,6 +286,37 @@ int wn_forward_loss_ragged(const WnConfig* cfg, int B, int T, const float* param
                            const int64_t* target, int t_start, const int32_t* t_end, int64_t n_loss, float grad_scale,
                            float loss_scale, float* loss, float* dlogits, float* logits_scratch, void* ws, size_t ws_bytes,
                            int flags, void* stream);
+
+/* Scoring held-out data (since ABI v13; additions only): the negative log-likelihood of each sequence of a batch, without a
+ * gradient and without a divisor.
+ *   row_nll : (B,) fp32 out on the device: row_nll[b] = SUM of the per-position negative log-likelihoods of sequence b over
+ *             the positions [t_start, min(t_end[b], T)).  A sum, not a mean: the caller knows the counts, and sums pool
+ *             exactly over batches of any size.  A sequence with no position in that range gets exactly 0.0f, and a batch in
+ *             which no sequence has one succeeds (t_start >= T included).  NULL is an error.
+ *   t_end   : (B,) int32 on the device, or NULL = T for every sequence (as wn_forward_loss_ragged).
+ *   acc     : nullable, ONE double on the device: acc[0] += the fp64 sum of row_nll as returned (the rows rounded to fp32,
+ *             added in double in ascending order), so the total of a pass is the sum of its per-sequence results.  A pass
+ *             over many batches accumulates there and the host reads it once.
+ * Each row is added in double in an order that depends on the number of column blocks alone and rounded to fp32 once; no atomics:
+ * the same inputs give the same bits.  The result does not depend on what the workspace held before the call, with or without
+ * WN_FLAG_WS_FINITE; the calls leave the workspace's max |dlogits| word alone, and the workspace afterwards is NOT an input
+ * of the backward entry points.
+ *   wn_forward_nll      : wn_forward_loss without dlogits (softmax head); logits_scratch (B, Q, T) is needed exactly where
+ *                         wn_forward_loss_fused(cfg, B, T, flags) == 0, NULL otherwise.
+ *   wn_softmax_nll_rows : the same rows from logits (B, Q, T) that already exist.
+ *   wn_mol_nll_rows     : the mixture-of-logistics head, from out (B, 3 * n_mix, T) of wn_forward and the waveform y (B, T);
+ *                         num_classes / log_scale_min as wn_mol_loss. */
+int wn_forward_nll(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                   const int64_t* target, int t_start, const int32_t* t_end, float* row_nll, double* acc,
+                   float* logits_scratch, void* ws, size_t ws_bytes, int flags, void* stream);
+int wn_softmax_nll_rows(const WnConfig* cfg, int B, int T, const float* logits, const int64_t* target, int t_start,
+                        const int32_t* t_end, float* row_nll, double* acc, void* ws, size_t ws_bytes, void* stream);
+int wn_mol_nll_rows(const WnConfig* cfg, int B, int T, const float* out, const float* y, int t_start, const int32_t* t_end,
+                    int num_classes, float log_scale_min, float* row_nll, double* acc, void* ws, size_t ws_bytes, void* stream);
+/* The reduction behind them on its own (op level): row_out[b] = sum of partial[b * nblk .. (b + 1) * nblk), one workgroup.
+ * Here acc[0] += the sum of the row sums as they are in DOUBLE, before their rounding to fp32, rows in ascending order. */
+int wn_op_row_sums(const float* partial /*[B][nblk]*/, int B, int nblk, float* row_out /*B*/, double* acc /*nullable*/,
+                   void* stream);
 
 /* Backward of wn_forward (what autograd does for train.py:538): writes EVERY element of the flat
  * gradient buffer `grads` (the dead range gets zeros).  `ws` must still hold the matching

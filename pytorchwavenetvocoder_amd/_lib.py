@@ -120,7 +120,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -133,6 +133,7 @@ EXPORTS = [
     "wn_decode_ctx_aux", "wn_decode_prefill_workspace_bytes", "wn_decode_prefill",
     "wn_softmax_ce_loss_ragged", "wn_forward_loss_ragged", "wn_mol_loss_ragged",
     "wn_grad_norm_scratch_floats", "wn_grad_norm", "wn_adam_step_guarded",
+    "wn_forward_nll", "wn_softmax_nll_rows", "wn_mol_nll_rows", "wn_op_row_sums",
 ]
 
 
@@ -177,6 +178,11 @@ class WnLibrary(object):
         # the ragged forms: (.., t_start, t_end (device int32 or NULL), n_loss, ..)
         L.wn_softmax_ce_loss_ragged.argtypes = [cfgp, i, i, vp, vp, i, vp, i64, f, f, vp, vp, vp, sz, vp]
         L.wn_forward_loss_ragged.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, i64, f, f, vp, vp, vp, vp, sz, i, vp]
+        # scoring: (.., t_start, t_end (device int32 or NULL), row_nll (B floats), acc (one device double or NULL), ..)
+        L.wn_forward_nll.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, sz, i, vp]
+        L.wn_softmax_nll_rows.argtypes = [cfgp, i, i, vp, vp, i, vp, vp, vp, vp, sz, vp]
+        L.wn_mol_nll_rows.argtypes = [cfgp, i, i, vp, vp, i, vp, i, f, vp, vp, vp, sz, vp]
+        L.wn_op_row_sums.argtypes = [vp, i, i, vp, vp, vp]
         L.wn_backward.argtypes = [cfgp, i, i, vp, vp, vp, vp, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
         L.wn_backward_window.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
         L.wn_backward_dh.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]

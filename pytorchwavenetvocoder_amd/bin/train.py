@@ -124,6 +124,75 @@ class _Done(object):
         return self.value
 
 
+def _load_utterance(wavfile, featfile, feature_type, upsampling_factor, use_upsampling_layer, use_speaker_code,
+                    wav_transform, feat_transform, pre):
+    """one utterance from its two files, trimmed to consistent lengths (train.py:202-212): (x, h, None, None), or with ``pre``
+    (x, h, transformed x, transformed h) -- the transforms applied once per utterance (``transforms_elementwise``)"""
+    x, _fs = read_wav(wavfile)
+    h = read_hdf5(featfile, "/" + feature_type)
+    if not use_upsampling_layer:
+        h = extend_time(h, upsampling_factor)
+    if use_speaker_code:
+        sc = read_hdf5(featfile, "/speaker_code")
+        h = np.concatenate([h, np.tile(sc, [h.shape[0], 1])], axis=1)
+    x, h = validate_length(x, h, upsampling_factor if use_upsampling_layer else None)
+    if not pre:
+        return x, h, None, None
+    # the buffers' dtypes (float32 waveform; features promoted with float32) are what the per-window transforms would see
+    xf = np.asarray(x, dtype=np.float32)
+    hf = np.asarray(h, dtype=np.result_type(np.float32, np.asarray(h).dtype))
+    return xf, hf, (wav_transform(xf) if wav_transform is not None else xf), (feat_transform(hf) if feat_transform is not None else hf)
+
+
+def _prep_window(x_, h_, xt_, ht_, wav_transform, feat_transform):
+    """one window: (tokens, features, un-quantised waveform); xt_ / ht_: the slices of the already transformed utterances"""
+    raw = torch.from_numpy(np.asarray(x_, dtype=np.float32))
+    if xt_ is not None:
+        x_, h_ = xt_, ht_
+    else:
+        if wav_transform is not None:
+            x_ = wav_transform(x_)
+        if feat_transform is not None:
+            h_ = feat_transform(h_)
+    return torch.from_numpy(np.asarray(x_)).long(), torch.from_numpy(np.asarray(h_)).float(), raw
+
+
+def _whole_utterance(x, h, xt, ht, upsampling_factor, use_upsampling_layer):
+    """an utterance as ONE window (the utterance modes, train.py:288-291): with the upsampling layer a whole number of frames"""
+    if use_upsampling_layer:
+        h = h[:-1]
+        x = x[:-upsampling_factor + 1]
+        if xt is not None:
+            ht = ht[:-1]
+            xt = xt[:-upsampling_factor + 1]
+    return x, h, xt, ht
+
+
+def _window_rows(windows, use_upsampling_layer):
+    """prepared windows -> the rows of a minibatch: inputs x[:-1], features (D, frames), targets x[1:] and waveform[1:]"""
+    xs, hs, ts, ys = [], [], [], []
+    for x_, h_, raw in windows:
+        hs.append(h_.transpose(0, 1) if use_upsampling_layer else h_[:-1].transpose(0, 1))
+        xs.append(x_[:-1])
+        ts.append(x_[1:])
+        ys.append(raw[1:])
+    return xs, hs, ts, ys
+
+
+def _pad_rows(xs, hs, ts, ys, n_quantize):
+    """rows of unequal length padded to the longest: tokens and targets with n_quantize // 2, the waveform with 0, the features
+    by repeating the last frame; + the valid positions of every row (CPU int64)"""
+    lengths = torch.tensor([int(v.numel()) for v in xs], dtype=torch.int64)
+    T = int(lengths.max())
+    F = max(int(v.size(1)) for v in hs)
+    fill = int(n_quantize) // 2
+    xs = [torch.nn.functional.pad(v, (0, T - v.numel()), value=fill) for v in xs]
+    ts = [torch.nn.functional.pad(v, (0, T - v.numel()), value=fill) for v in ts]
+    ys = [torch.nn.functional.pad(v, (0, T - v.numel()), value=0.0) for v in ys]
+    hs = [torch.cat([v, v[:, -1:].expand(-1, F - v.size(1))], dim=1) if v.size(1) < F else v for v in hs]
+    return xs, hs, ts, ys, lengths
+
+
 @background(max_prefetch=16)
 def train_generator(wav_list, feat_list, receptive_field,
                     batch_length=None,
@@ -204,63 +273,22 @@ def train_generator(wav_list, feat_list, receptive_field,
         return pool.submit(fn, *a) if pool is not None else _Done(fn(*a))
 
     def load(wavfile, featfile):
-        """one utterance from its two files, trimmed to consistent lengths (train.py:202-212)"""
-        x, _fs = read_wav(wavfile)
-        h = read_hdf5(featfile, "/" + feature_type)
-        if not use_upsampling_layer:
-            h = extend_time(h, upsampling_factor)
-        if use_speaker_code:
-            sc = read_hdf5(featfile, "/speaker_code")
-            h = np.concatenate([h, np.tile(sc, [h.shape[0], 1])], axis=1)
-        x, h = validate_length(x, h, upsampling_factor if use_upsampling_layer else None)
-        if not pre:
-            return x, h, None, None
-        # the buffers' dtypes (float32 waveform; features promoted with float32) are what the per-window transforms would see
-        xf = np.asarray(x, dtype=np.float32)
-        hf = np.asarray(h, dtype=np.result_type(np.float32, np.asarray(h).dtype))
-        return xf, hf, (wav_transform(xf) if wav_transform is not None else xf), (feat_transform(hf) if feat_transform is not None else hf)
+        return _load_utterance(wavfile, featfile, feature_type, upsampling_factor, use_upsampling_layer, use_speaker_code,
+                               wav_transform, feat_transform, pre)
 
     def prep(x_, h_, xt_=None, ht_=None):
-        """one window: (tokens, features, un-quantised waveform); xt_ / ht_: the slices of the already transformed utterances"""
-        raw = torch.from_numpy(np.asarray(x_, dtype=np.float32))
-        if xt_ is not None:
-            x_, h_ = xt_, ht_
-        else:
-            if wav_transform is not None:
-                x_ = wav_transform(x_)
-            if feat_transform is not None:
-                h_ = feat_transform(h_)
-        return torch.from_numpy(np.asarray(x_)).long(), torch.from_numpy(np.asarray(h_)).float(), raw
+        return _prep_window(x_, h_, xt_, ht_, wav_transform, feat_transform)
 
     def assemble(window_jobs):
         """one minibatch from its windows' jobs (submitted before this one: the pool's queue is FIFO, so they are running or done)"""
-        xs, hs, ts, ys = [], [], [], []
-        for job in window_jobs:
-            x_, h_, raw = job.result()
-            hs.append(h_.transpose(0, 1) if use_upsampling_layer else h_[:-1].transpose(0, 1))
-            xs.append(x_[:-1])
-            ts.append(x_[1:])
-            ys.append(raw[1:])
+        xs, hs, ts, ys = _window_rows([job.result() for job in window_jobs], use_upsampling_layer)
         return _to_batch(xs, hs, ts, device, ys if with_wave else None)
 
     def assemble_padded(window_jobs, all_lengths, lo):
         """one minibatch of whole utterances (this rank's rows [lo, lo + len(window_jobs)) of it), padded to the longest row"""
-        xs, hs, ts, ys = [], [], [], []
-        for job in window_jobs:
-            x_, h_, raw = job.result()
-            hs.append(h_.transpose(0, 1) if use_upsampling_layer else h_[:-1].transpose(0, 1))
-            xs.append(x_[:-1])
-            ts.append(x_[1:])
-            ys.append(raw[1:])
-        lengths = torch.tensor([int(v.numel()) for v in xs], dtype=torch.int64)
+        xs, hs, ts, ys = _window_rows([job.result() for job in window_jobs], use_upsampling_layer)
+        xs, hs, ts, ys, lengths = _pad_rows(xs, hs, ts, ys, n_quantize)
         assert lengths.tolist() == all_lengths[lo:lo + len(xs)]
-        T = int(lengths.max())
-        F = max(int(v.size(1)) for v in hs)
-        fill = int(n_quantize) // 2
-        xs = [torch.nn.functional.pad(v, (0, T - v.numel()), value=fill) for v in xs]
-        ts = [torch.nn.functional.pad(v, (0, T - v.numel()), value=fill) for v in ts]
-        ys = [torch.nn.functional.pad(v, (0, T - v.numel()), value=0.0) for v in ys]
-        hs = [torch.cat([v, v[:, -1:].expand(-1, F - v.size(1))], dim=1) if v.size(1) < F else v for v in hs]
         return _to_batch(xs, hs, ts, device, ys if with_wave else None) + (lengths, torch.tensor(all_lengths, dtype=torch.int64))
 
     def utterances():
@@ -348,12 +376,7 @@ def train_generator(wav_list, feat_list, receptive_field,
                 n_seen += 1
                 if not padded and shard is not None and (n_seen - 1) % shard[1] != shard[0]:
                     continue
-                if use_upsampling_layer:
-                    h = h[:-1]
-                    x = x[:-upsampling_factor + 1]
-                    if pre:
-                        ht = ht[:-1]
-                        xt = xt[:-upsampling_factor + 1]
+                x, h, xt, ht = _whole_utterance(x, h, xt, ht, upsampling_factor, use_upsampling_layer)
                 if padded:
                     # batch_size consecutive utterances per minibatch; rows of other ranks only contribute their length
                     if my_lo <= n_in_batch < my_hi:
@@ -376,13 +399,133 @@ def train_generator(wav_list, feat_list, receptive_field,
             pool.shutdown(wait=False)
 
 
-def save_checkpoint(checkpoint_dir, model, optimizer, iterations):
-    """``checkpoint-%d.pkl`` = {"model", "optimizer", "iterations"} (reference train.py:315-332)."""
+def evaluate_corpus(model, wav_list, feat_list, batch_size,
+                    feature_type="world",
+                    wav_transform=None,
+                    feat_transform=None,
+                    upsampling_factor=80,
+                    use_upsampling_layer=True,
+                    use_speaker_code=False,
+                    device=None,
+                    shard=None,
+                    transforms_elementwise=False,
+                    n_quantize=None,
+                    length_cache=None):
+    """Score every utterance of a list exactly once with ``model.evaluate`` (NOT a reference function: the reference has no
+    held-out loss).  Feature, transform and upsampling arguments as ``train_generator``, whose reading and transform code this
+    shares.
+
+    The utterances are sorted by length (ties by list index: little padding, a deterministic order) and grouped ``batch_size`` at
+    a time -- the last group may be smaller, nothing is dropped -- each group padded as ``train_generator(pad_utterances=True)``
+    pads (tokens and targets ``n_quantize // 2``, the last frame repeated, a whole number of frames with the upsampling layer) and
+    scored over the positions behind the receptive field.  ``shard=(rank, world)``: this rank takes the groups ``rank, rank +
+    world, ...`` of the same grouping.  ``length_cache`` (a dict, optional): the lengths found by the first pass over the files
+    are kept in it, so a later call with the same dict reads only the groups it scores.
+
+    Returns ``(nll, positions, per_utterance, n_short)``: the total negative log-likelihood (accumulated on the device in double
+    and read once at the end, with the per-utterance sums: the pass's only device-to-host synchronisation), the number of
+    positions it covers, ``[(index, nll_sum, n_positions)]`` in list order for the utterances this call scored, and how many of
+    them are not longer than the receptive field -- those have no position to score, count 0 and get one warning each.  The
+    mean per position is ``nll / positions``; sums from several ranks or lists simply add."""
+    eng = model.engine
+    device = eng.device if device is None else torch.device(device)
+    n_quantize = model.n_quantize if n_quantize is None else n_quantize
+    rf = model.receptive_field
+    pre = bool(transforms_elementwise)
+    mixture = model.n_mixture > 0
+
+    def load(i, transforms=True):
+        utt = _load_utterance(wav_list[i], feat_list[i], feature_type, upsampling_factor, use_upsampling_layer, use_speaker_code,
+                              wav_transform, feat_transform, pre and transforms)
+        return _whole_utterance(*utt, upsampling_factor, use_upsampling_layer)
+
+    n_lengths = []
+    for i in range(len(wav_list)):
+        key = (wav_list[i], feat_list[i])
+        if length_cache is not None and key in length_cache:
+            n_lengths.append(length_cache[key])
+            continue
+        n = max(len(load(i, transforms=False)[0]) - 1, 0)   # (the trimmed length alone: no mu-law, no scaler)
+        if length_cache is not None:
+            length_cache[key] = n
+        n_lengths.append(n)
+    order = sorted(range(len(wav_list)), key=lambda i: (n_lengths[i], i))
+    groups = [order[g:g + batch_size] for g in range(0, len(order), batch_size)]
+    if shard is not None:
+        groups = groups[shard[0]::shard[1]]
+    acc = torch.zeros(1, dtype=torch.float64, device=device)
+    rows, scored, zeros, n_short = [], [], [], 0
+    for group in groups:
+        for i in group:
+            if n_lengths[i] <= rf:
+                n_short += 1
+                logging.warning("%s is not longer than the receptive field (%d <= %d): no position to score."
+                                % (wav_list[i], n_lengths[i], rf))
+        empty = [i for i in group if n_lengths[i] < 1]   # (not a single input / target pair: nothing to run)
+        group = [i for i in group if n_lengths[i] >= 1]
+        zeros += [(i, 0.0, 0) for i in empty]
+        if not group:
+            continue
+        windows = []
+        for i in group:
+            x, h, xt, ht = load(i)
+            windows.append(_prep_window(x, h, xt, ht, wav_transform, feat_transform))
+        xs, hs, ts, ys, lengths = _pad_rows(*_window_rows(windows, use_upsampling_layer), n_quantize)
+        assert lengths.tolist() == [n_lengths[i] for i in group]
+        if mixture:
+            (bx, bh), _, by = _to_batch(xs, hs, ts, device, ys)
+            row, counts = model.evaluate(bx, bh, y=by, lengths=lengths, acc=acc)
+        else:
+            (bx, bh), bt = _to_batch(xs, hs, ts, device)
+            row, counts = model.evaluate(bx, bh, t=bt, lengths=lengths, acc=acc)
+        rows.append(row)
+        scored += list(zip(group, counts))
+    values = torch.cat([acc] + [r.double() for r in rows]).cpu().tolist()   # the one read of the pass
+    eng.release_eval_workspace()
+    per_utt = sorted([(i, v, n) for (i, n), v in zip(scored, values[1:])] + zeros)
+    return values[0], sum(n for _, n in scored), per_utt, n_short
+
+
+def dev_loss(model, dev, rank, world, device):
+    """One pass over the held-out list ``dev`` = (wav_list, feat_list, batch_size, keyword arguments of evaluate_corpus): every
+    rank scores its shard, ONE all-reduce of the float64 pair [nll, positions]; returns (mean per position, utterances,
+    positions) -- the same numbers on every rank."""
+    import torch.distributed as dist
+    wav_list, feat_list, batch_size, kw = dev
+    nll, npos, per_utt, _ = evaluate_corpus(model, wav_list, feat_list, batch_size, device=device,
+                                            shard=(rank, world) if world > 1 else None, **kw)
+    pair = torch.tensor([nll, float(npos)], dtype=torch.float64, device=device)
+    if world > 1:
+        dist.all_reduce(pair)
+    nll, npos = pair.tolist()
+    return (nll / npos if npos > 0 else float("nan")), len(wav_list), int(npos)
+
+
+def save_checkpoint(checkpoint_dir, model, optimizer, iterations, dev=None):
+    """``checkpoint-%d.pkl`` = {"model", "optimizer", "iterations"} (reference train.py:315-332); with a held-out set
+    (--dev_waveforms) also "dev" = {"best_loss", "best_iterations"}."""
     checkpoint = {"model": model.state_dict(), "optimizer": optimizer.state_dict(), "iterations": iterations}
+    if dev is not None:
+        checkpoint["dev"] = dict(dev)
     if not os.path.exists(checkpoint_dir):
         os.makedirs(checkpoint_dir)
     torch.save(checkpoint, checkpoint_dir + "/checkpoint-%d.pkl" % iterations)
     logging.info("%d-iter checkpoint created." % iterations)
+
+
+def dev_best_state(dev_best):
+    """The "dev" entry of a regular checkpoint from (lowest dev loss so far, its iteration); both None while no pass over the
+    held-out set has given a finite loss yet (a checkpoint written in front of the first pass)."""
+    return {"best_loss": dev_best[0] if dev_best else None, "best_iterations": dev_best[1] if dev_best else None}
+
+
+def dev_best_from_checkpoint(checkpoint):
+    """(lowest dev loss, its iteration) as --resume restores it, or None: a checkpoint of a run without a held-out set has no
+    "dev" entry, one written in front of the first pass holds Nones."""
+    state = checkpoint.get("dev") or {}
+    if state.get("best_loss") is None or state.get("best_iterations") is None:
+        return None
+    return float(state["best_loss"]), int(state["best_iterations"])
 
 
 # (flag, default, type, help) -- the reference's command line, train.py:339-393
@@ -439,8 +582,26 @@ def get_parser():
                         help="clip the global gradient norm to this value before the Adam step (0: off)")
     parser.add_argument("--skip_nonfinite_steps", default=False, type=strtobool,
                         help="skip (and count) a step whose gradient holds a NaN or an inf instead of applying it")
+    # extensions (not reference flags): a held-out set scored during training (evaluate_corpus); off without --dev_waveforms
+    parser.add_argument("--dev_waveforms", default=None, type=str, help="held-out wav directory or .scp list (with --dev_feats)")
+    parser.add_argument("--dev_feats", default=None, type=str, help="held-out aux-feature directory or .scp list")
+    parser.add_argument("--eval_interval", default=0, type=int,
+                        help="iterations between two passes over the held-out set (0: at every --checkpoint_interval)")
+    parser.add_argument("--eval_batch_size", default=8, type=int, help="held-out utterances scored per padded batch")
     parser.add_argument("--resume", default=None, nargs="?", type=str, help="checkpoint to continue from")
     return parser
+
+
+def _file_lists(waveforms, feats, flag):
+    """wav / feature file lists from a directory or a list file (reference train.py:472-482)"""
+    if os.path.isdir(waveforms):
+        filenames = sorted(find_files(waveforms, "*.wav", use_dir_name=False))
+        return ([waveforms + "/" + filename for filename in filenames],
+                [feats + "/" + filename.replace(".wav", ".h5") for filename in filenames])
+    if os.path.isfile(waveforms):
+        return read_txt(waveforms), read_txt(feats)
+    logging.error("%s should be directory or list." % flag)
+    sys.exit(1)
 
 
 def _fmt_eta(seconds):
@@ -512,16 +673,7 @@ def _worker(rank, world, args, port):
     wav_transform = lambda x: encode_mu_law(x, args.n_quantize)   # noqa: E731
     feat_transform = make_feat_transform(mean, scale)
 
-    if os.path.isdir(args.waveforms):
-        filenames = sorted(find_files(args.waveforms, "*.wav", use_dir_name=False))
-        wav_list = [args.waveforms + "/" + filename for filename in filenames]
-        feat_list = [args.feats + "/" + filename.replace(".wav", ".h5") for filename in filenames]
-    elif os.path.isfile(args.waveforms):
-        wav_list = read_txt(args.waveforms)
-        feat_list = read_txt(args.feats)
-    else:
-        logging.error("--waveforms should be directory or list.")
-        sys.exit(1)
+    wav_list, feat_list = _file_lists(args.waveforms, args.feats, "--waveforms")
     assert len(wav_list) == len(feat_list)
     logging.info("number of training data = %d." % len(wav_list))
     utterance_batch = bool(getattr(args, "utterance_batch", False))
@@ -544,6 +696,21 @@ def _worker(rank, world, args, port):
         device=device,
         transforms_elementwise=True)   # mu-law and the standard scaler are per-sample / per-frame maps
 
+    dev, dev_best = None, None   # held-out set (off without --dev_waveforms); (lowest dev loss so far, its iteration)
+    if getattr(args, "dev_waveforms", None):
+        if not getattr(args, "dev_feats", None):
+            logging.error("--dev_waveforms needs --dev_feats.")
+            sys.exit(1)
+        dev_wav, dev_feat = _file_lists(args.dev_waveforms, args.dev_feats, "--dev_waveforms")
+        assert len(dev_wav) == len(dev_feat)
+        logging.info("number of held-out data = %d." % len(dev_wav))
+        dev = (dev_wav, dev_feat, max(1, int(args.eval_batch_size)),
+               dict(feature_type=args.feature_type, wav_transform=wav_transform, feat_transform=feat_transform,
+                    upsampling_factor=args.upsampling_factor, use_upsampling_layer=args.use_upsampling_layer,
+                    use_speaker_code=args.use_speaker_code, transforms_elementwise=True, n_quantize=args.n_quantize,
+                    length_cache={}))
+    eval_interval = (int(getattr(args, "eval_interval", 0)) or args.checkpoint_interval) if dev is not None else 0
+
     max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
     optimizer = FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay,
                           max_grad_norm=max_grad_norm if max_grad_norm > 0.0 else None,
@@ -553,6 +720,8 @@ def _worker(rank, world, args, port):
         iterations = checkpoint["iterations"]
         model.load_state_dict(checkpoint["model"])
         optimizer.load_state_dict(checkpoint["optimizer"])
+        if dev is not None:
+            dev_best = dev_best_from_checkpoint(checkpoint)
         logging.info("restored from %d-iter checkpoint." % iterations)
     else:
         iterations = 0
@@ -613,8 +782,26 @@ def _worker(rank, world, args, port):
                 norm_acc.zero_()
             loss_acc.zero_()
             total = 0.0
+        if eval_interval > 0 and (i + 1) % eval_interval == 0:
+            # every rank scores its shard of the held-out list; one all-reduce of [nll, positions] makes the mean
+            start = time.time()
+            loss_dev, n_utt, n_pos = dev_loss(model, dev, rank, world, device)
+            if is_main:
+                logging.info("(iter:%d) dev loss = %.6f (%d utterances, %d samples, %.3f sec)" % (
+                    i + 1, loss_dev, n_utt, n_pos, time.time() - start))
+                with open(args.expdir + "/dev_loss.txt", "a") as fh:
+                    fh.write("%d %.6f %d %d\n" % (i + 1, loss_dev, n_utt, n_pos))
+            if loss_dev == loss_dev and (dev_best is None or loss_dev < dev_best[0]):   # (same numbers on every rank)
+                dev_best = (loss_dev, i + 1)
+                if is_main:
+                    torch.save({"model": model.state_dict(), "iterations": i + 1, "dev_loss": loss_dev},
+                               args.expdir + "/checkpoint-best.pkl")
+                    logging.info("best checkpoint created (dev loss %.6f)." % loss_dev)
         if (i + 1) % args.checkpoint_interval == 0 and is_main:
-            save_checkpoint(args.expdir, model, optimizer, i + 1)
+            if dev is None:
+                save_checkpoint(args.expdir, model, optimizer, i + 1)
+            else:
+                save_checkpoint(args.expdir, model, optimizer, i + 1, dev=dev_best_state(dev_best))
 
     generator.close()   # stop the producer thread before the interpreter tears the runtime down under it
     if is_main:

@@ -1268,6 +1268,78 @@ extern "C" int wn_mol_loss(const WnConfig* cfg, int B, int T, const float* out, 
 }
 
 // ------------------------------------------------------------------------------------------
+// scoring: per-sequence negative log-likelihood sums, no gradient (since ABI v13)
+// ------------------------------------------------------------------------------------------
+// The loss kernels leave their partial sums as [sequence b][column block]; one single-workgroup launch adds each row
+// (wn_row_sums).  No divisor, so none of loss_count's refusals: a batch without a loss position succeeds with zeros.  acc takes
+// the rows as returned (rounded to fp32): the total of a pass is the fp64 sum of the per-sequence values the caller holds.
+static int nll_check(int B, int T, int t_start, const float* row_nll) {
+    if (!row_nll) return fail(1, "row_nll is NULL");
+    if (B < 1 || T < 1) return fail(1, "B and T must be positive");
+    if (t_start < 0) return fail(1, "t_start=%d is negative", t_start);
+    return 0;
+}
+
+extern "C" int wn_softmax_nll_rows(const WnConfig* cfg, int B, int T, const float* logits, const int64_t* target, int t_start,
+                                   const int32_t* t_end, float* row_nll, double* acc, void* wsp, size_t ws_bytes, void* stream) {
+    api_enter();
+    WN_TRY(nll_check(B, T, t_start, row_nll));
+    Ctx c;
+    WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, 0, stream));
+    if (!logits || !target) return fail(1, "NULL argument");
+    if (t_start >= T) return wn_fill(row_nll, 0.0f, B, c.st) ? fail(100, "wn_fill failed") : rt_check("wn_softmax_nll_rows");
+    int np = 0;
+    WN_TRY(wn_softmax_ce(logits, target, nullptr, c.ws + c.w.loss_partial, &np, B, T, c.d.Qo, t_start, 1.0f, nullptr, t_end, c.st));
+    WN_TRY(wn_row_sums(c.ws + c.w.loss_partial, B, np / B, row_nll, acc, 1, c.st));
+    return rt_check("wn_softmax_nll_rows");
+}
+
+extern "C" int wn_mol_nll_rows(const WnConfig* cfg, int B, int T, const float* out, const float* y, int t_start,
+                               const int32_t* t_end, int num_classes, float log_scale_min, float* row_nll, double* acc, void* wsp,
+                               size_t ws_bytes, void* stream) {
+    api_enter();
+    WN_TRY(nll_check(B, T, t_start, row_nll));
+    Ctx c;
+    WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, 0, stream));
+    if (!out || !y) return fail(1, "NULL argument");
+    if (c.d.Qo % 3 != 0) return fail(1, "out_channels=%d is not 3 * n_mixture", c.d.Qo);
+    if (t_start >= T) return wn_fill(row_nll, 0.0f, B, c.st) ? fail(100, "wn_fill failed") : rt_check("wn_mol_nll_rows");
+    int np = 0;
+    WN_TRY(wn_mol_nll(out, y, nullptr, c.ws + c.w.loss_partial, &np, B, T, c.d.Qo / 3, t_start, 1.0f, num_classes, log_scale_min, t_end, c.st));
+    WN_TRY(wn_row_sums(c.ws + c.w.loss_partial, B, np / B, row_nll, acc, 1, c.st));
+    return rt_check("wn_mol_nll_rows");
+}
+
+extern "C" int wn_forward_nll(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                              const int64_t* target, int t_start, const int32_t* t_end, float* row_nll, double* acc,
+                              float* logits_scratch, void* wsp, size_t ws_bytes, int flags, void* stream) {
+    api_enter();
+    WN_TRY(nll_check(B, T, t_start, row_nll));
+    if (!target) return fail(1, "NULL argument");
+    // No backward pass is defined on the workspace of this call, so nothing ever reads the post-net columns in front of the loss
+    // window: they are neither zero-filled nor trusted, whatever the caller says about the workspace.
+    flags |= WN_FLAG_WS_FINITE;
+    if (t_start >= T) {   // no position of any sequence: nothing to run
+        Ctx c;
+        WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, flags, stream));
+        return wn_fill(row_nll, 0.0f, B, c.st) ? fail(100, "wn_fill failed") : rt_check("wn_forward_nll");
+    }
+    if (!wn_forward_loss_fused(cfg, B, T, flags)) {
+        if (!logits_scratch) return fail(1, "this model / flag set needs the logits scratch buffer (wn_forward_loss_fused() == 0)");
+        WN_TRY(forward_impl(cfg, B, T, params, x, h, logits_scratch, nullptr, wsp, ws_bytes, flags, stream, "wn_forward_nll"));
+        return wn_softmax_nll_rows(cfg, B, T, logits_scratch, target, t_start, t_end, row_nll, acc, wsp, ws_bytes, stream);
+    }
+    CeEpi ce;
+    ce.target = target; ce.t_start = t_start; ce.t_end = t_end; ce.t_origin = 0; ce.gs = 1.0f; ce.partial = nullptr; ce.amax = nullptr;
+    WN_TRY(forward_impl(cfg, B, T, params, x, h, nullptr, &ce, wsp, ws_bytes, flags, stream, "wn_forward_nll"));
+    Ctx c;
+    WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, flags, stream));
+    const int t0w = (t_start / 128) * 128;   // the column window forward_impl ran the loss epilogue over
+    WN_TRY(wn_row_sums(c.ws + c.w.loss_partial, B, (T - t0w + WN_G6_BN - 1) / WN_G6_BN, row_nll, acc, 1, c.st));
+    return rt_check("wn_forward_nll");
+}
+
+// ------------------------------------------------------------------------------------------
 // The rest of the C ABI, by strand (same translation unit: they use the helpers above)
 // ------------------------------------------------------------------------------------------
 #include "wn_api_backward.inl"

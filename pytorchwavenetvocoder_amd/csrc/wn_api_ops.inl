@@ -131,3 +131,12 @@ extern "C" int wn_op_gemm(const struct WnGemmArgs* args, void* stream) {
     WN_TRY(wn_gemm_launch(args, (wn_stream_t)stream));
     return rt_check("wn_op_gemm");
 }
+
+// The per-sequence reduction of the scoring entry points on its own: row_out[b] = sum of partial[b * nblk .. (b + 1) * nblk),
+// acc[0] (nullable, double) += the sum of the row sums as they are in double, before their rounding to float.
+extern "C" int wn_op_row_sums(const float* partial, int B, int nblk, float* row_out, double* acc, void* stream) {
+    api_enter();
+    if (!partial || !row_out || B < 1 || nblk < 1) return fail(1, "bad argument");
+    WN_TRY(wn_row_sums(partial, B, nblk, row_out, acc, 0, (wn_stream_t)stream));
+    return rt_check("wn_op_row_sums");
+}

@@ -43,6 +43,13 @@ int wn_dw_prepare(float* words, float host_mul, const float* scan, int n_scan, i
 // partial[r * nchunk + c] = max |p[r * ld + c0 + 4096 c + j]|, j < min(4096, ncols - 4096 c); nchunk = ceil(ncols / 4096)
 int wn_absmax_rows(const float* p, long rows, long ld, int c0, int ncols, float* partial, wn_stream_t st);
 int wn_softmax_ce_nblocks(int B, int T);
+// Per-sequence sums of the partials the loss kernels leave as [sequence b][column block] (k_softmax_ce, k_mol_nll, the
+// cross-entropy epilogue of k_gemm6): row_out[b] = sum of partial[b * nblk .. (b + 1) * nblk), added in double in an order that
+// depends on nblk alone and rounded to float once.  acc (nullable, one double on the device): acc[0] += the sum of the double row
+// sums in ascending row order -- or, with acc_as_returned, of the rows as rounded to float: acc then is the fp64 sum of exactly
+// the values row_out received (the scoring entry points: a pass's total equals the sum of its per-sequence results).  A pass over
+// many batches accumulates there and the host reads it once.  One workgroup.
+int wn_row_sums(const float* partial, int B, int nblk, float* row_out, double* acc, int acc_as_returned, wn_stream_t st);
 
 // Adam over a flat fp32 buffer (torch.optim.Adam semantics, train.py:457-460): elements in
 // [skip_lo, skip_hi) are left untouched (parameters that never receive a gradient).

@@ -1744,4 +1744,44 @@ int wn_decode_fill_queues(const float* X, float* dst, int L, int B, int R, int T
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-sequence sums of the loss partials (wn_elem.h): ONE workgroup, wave w takes the rows w, w + 4, ...  A row is added in double,
+// lane i its elements i, i + 64, ... front to back, then the xor butterfly of the wave -- an order that depends on nblk alone --
+// and rounded to float once.  Thread 0 adds the double row sums in ascending row order and adds that to acc[0] with a plain
+// load and store: no atomics, the launches of one stream are ordered.  acc_as_returned: thread 0 adds the rows AS ROUNDED to
+// float (in double, the same order), so that acc is the fp64 sum of exactly the values row_out received.
+__global__ __launch_bounds__(WN_TPB) void k_row_sums(const float* __restrict__ partial, int B, int nblk, float* __restrict__ row_out,
+                                                     double* __restrict__ acc, int acc_as_returned) {
+    __shared__ double red[WN_TPB >> 6];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double total = 0.0;
+    for (int b0 = 0; b0 < B; b0 += (WN_TPB >> 6)) {
+        const int b = b0 + wave;   // wave-uniform
+        double s = 0.0;
+        if (b < B) {
+            const float* row = partial + (long)b * nblk;
+            for (int i = lane; i < nblk; i += 64) s += (double)row[i];
+        }
+        s = wn_wave_sum_f64(s);
+        if (lane == 0) {
+            red[wave] = s;
+            if (b < B) row_out[b] = (float)s;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int n = B - b0 < (WN_TPB >> 6) ? B - b0 : (WN_TPB >> 6);
+            for (int i = 0; i < n; ++i) total += acc_as_returned ? (double)(float)red[i] : red[i];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && acc != nullptr) acc[0] = acc[0] + total;
+}
+
+int wn_row_sums(const float* partial, int B, int nblk, float* row_out, double* acc, int acc_as_returned, wn_stream_t st) {
+    WN_PROF("row_sums", 0.0, 4.0 * (double)B * nblk, st);
+    if (!partial || !row_out || B < 1 || nblk < 1) return 1;
+    WN_LAUNCH(k_row_sums, dim3(1), dim3(WN_TPB), 0, st, partial, B, nblk, row_out, acc, acc_as_returned);
+    return 0;
+}
+
 #include "wn_auxdh.inl"

@@ -87,8 +87,11 @@ class WaveNetEngine(object):
         self.flat_grads = None
         self._ws = None
         self._ws_key = None
+        self._eval_ws = None      # forward_nll's own workspace slot: scoring never evicts or rewrites the training one
+        self._eval_ws_key = None
         self._lengths_key = None  # (lengths, device) of the int32 array _lengths_arg uploaded last
         self._lengths_dev = None
+        self._eval_lengths = (None, None)  # the same pair for forward_nll
         self._last_shape = None
         self._fwd_window = 0      # first loss position of the last forward_loss (0: a full forward)
         self._fwd_version = None  # parameter version the last forward packed its weight sets from
@@ -130,6 +133,7 @@ class WaveNetEngine(object):
             self.flat_grads = None if self.flat_grads is None else self.flat_grads.to(device)
             self._ws = None
             self._ws_key = None
+            self.release_eval_workspace()
             self.device = device
         return self
 
@@ -158,6 +162,24 @@ class WaveNetEngine(object):
             self._ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
             self._ws_key = key
         return self._ws
+
+    def eval_workspace(self, B, T):
+        """The workspace of ``forward_nll``: a slot of its own beside ``workspace()``, zero-filled on allocation like it."""
+        key = (B, T)
+        if self._eval_ws_key != key:
+            nbytes = self.lib.wn_workspace_bytes(ctypes.byref(self.cfg), B, T)
+            if nbytes == 0:
+                raise _lib.WnError("wn_workspace_bytes: %s" % self.lib.wn_last_error().decode())
+            self._eval_ws = None  # free first
+            self._eval_ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
+            self._eval_ws_key = key
+        return self._eval_ws
+
+    def release_eval_workspace(self):
+        """Drop the scoring workspace (and the lengths uploaded for it); the next ``forward_nll`` allocates again."""
+        self._eval_ws = None
+        self._eval_ws_key = None
+        self._eval_lengths = (None, None)
 
     def params_version(self):
         """Changes whenever the flat parameter buffer is written: torch's in-place version counter (optimizers working
@@ -264,11 +286,13 @@ class WaveNetEngine(object):
         self._note_bound(dlogits, grad_scale, count)
         return loss, dlogits
 
-    def _lengths_arg(self, lengths, B, T, t_start):
+    def _lengths_arg(self, lengths, B, T, t_start, scoring=False):
         """``lengths`` of a padded batch -> (device int32 array for the ragged C entry points, N).  ``lengths[b]`` is the number of
         valid positions of sequence b, 1 <= lengths[b] <= T; the loss positions of b are [t_start, lengths[b]) and
         N = sum_b max(lengths[b] - t_start, 0) is their count -- known here, on the host, because the lengths are host
-        integers (a sequence of ints or a CPU integer tensor): the step gains no device-to-host synchronisation."""
+        integers (a sequence of ints or a CPU integer tensor): the step gains no device-to-host synchronisation.
+        ``scoring`` (``forward_nll``): N == 0 is allowed -- there is no divisor -- and the uploaded array is kept in a slot of its
+        own, so the training step's stays where it is."""
         if isinstance(lengths, torch.Tensor):
             if lengths.device.type != "cpu":
                 raise ValueError("lengths must be host integers (a sequence of ints or a CPU integer tensor), got a tensor on "
@@ -293,9 +317,13 @@ class WaveNetEngine(object):
             if v < 1 or v > T:
                 raise ValueError("lengths[%d] = %d outside [1, T = %d]" % (b, v, T))
         n = sum(max(v - int(t_start), 0) for v in lens)
-        if n == 0:
+        if n == 0 and not scoring:
             raise ValueError("lengths %s leave no loss position behind t_start = %d (N == 0)" % (lens, int(t_start)))
         key = (tuple(lens), str(self.device))
+        if scoring:
+            if self._eval_lengths[0] != key:
+                self._eval_lengths = (key, torch.tensor(lens, dtype=torch.int32).to(self.device, non_blocking=True))
+            return self._eval_lengths[1], n
         if self._lengths_key != key:   # an upload of B integers, not a launch; the same lengths step after step upload once
             self._lengths_dev = torch.tensor(lens, dtype=torch.int32).to(self.device, non_blocking=True)
             self._lengths_key = key
@@ -381,6 +409,77 @@ class WaveNetEngine(object):
             self.lib.check(rc, "wn_mol_loss_ragged")
         self._dlogits_bound = None   # (the mixture head's loss call measures no maximum: backward scans its gradient)
         return loss, dout
+
+    def forward_nll(self, x, h, target=None, y=None, t_start=None, lengths=None, acc=None, num_classes=65536, log_scale_min=-7.0):
+        """Score a batch: the negative log-likelihood of every sequence, no gradient.  Returns ``(row_nll, counts)``:
+        ``row_nll`` (B,) fp32 on the device, the SUM over the positions [t_start, min(lengths[b], T)) of sequence b (exactly 0.0
+        where there is none), and ``counts``, B host ints ``max(min(lengths[b], T) - t_start, 0)`` -- sums and counts pool
+        exactly over batches of any size, a mean is one division away.  Softmax head: ``target`` (B, T) int64; mixture head:
+        ``y`` (B, T) waveform in [-1, 1], ``num_classes`` / ``log_scale_min`` as ``mol_loss``.  ``lengths``: as ``forward_loss``,
+        except that a batch without any loss position is fine.  ``acc``: a 1-element float64 tensor on the model's device;
+        the batch's total -- the fp64 sum of ``row_nll`` as returned -- is ADDED to it on the device, so a pass over many batches
+        reads the host once.
+
+        The call runs in a workspace of its own (``eval_workspace``) and touches nothing a later ``backward()`` reads: the
+        training workspace, the shapes / inputs / parameter version of the last forward and the gradient buffer stay as
+        they are, so it may sit between ``forward_loss`` and ``backward``."""
+        mixture = self.cfg.out_channels > 0
+        if (target is None) == (y is None):
+            raise ValueError("forward_nll takes exactly one of target (softmax head) and y (mixture-of-logistics head)")
+        if mixture and y is None:
+            raise ValueError("this model has the mixture-of-logistics head: pass the waveform y, not class targets")
+        if not mixture and target is None:
+            raise ValueError("this model has the softmax head: pass the class targets, not a waveform y")
+        ref = target if target is not None else y
+        self._check_device(x, h, ref, acc)
+        if x.dtype != torch.int64 or x.dim() != 2:
+            raise ValueError("x must be a LongTensor (B, T)")
+        B, T = x.shape
+        U = self.cfg.upsampling_factor
+        if U > 0 and T % U != 0:
+            raise ValueError("T must be a multiple of the upsampling factor")
+        flen = T // U if U > 0 else T
+        if h.dim() != 3 or h.size(0) != B or h.size(1) != self.cfg.n_aux or h.size(2) != flen:
+            raise ValueError("h must be (B, n_aux, %d)" % flen)
+        if tuple(ref.shape) != (B, T) or (target is not None and target.dtype != torch.int64):
+            raise ValueError("%s must be a (B, T) %s" % (("target", "LongTensor") if target is not None else ("y", "tensor")))
+        if acc is not None:
+            if not isinstance(acc, torch.Tensor) or acc.dtype != torch.float64 or acc.numel() != 1 or not acc.is_contiguous():
+                raise ValueError("acc must be a 1-element float64 tensor on the model's device, got %s"
+                                 % ("%s %s" % (tuple(acc.shape), acc.dtype) if isinstance(acc, torch.Tensor) else type(acc)))
+        if t_start is None:
+            t_start = self.receptive_field
+        t_start = int(t_start)
+        if t_start < 0:
+            raise ValueError("t_start must not be negative")
+        if lengths is None:
+            t_end, counts = None, [max(T - t_start, 0)] * B
+        else:
+            t_end, _ = self._lengths_arg(lengths, B, T, t_start, scoring=True)
+            counts = [max(min(int(v), T) - t_start, 0) for v in self._eval_lengths[0][0]]
+        x, h = x.contiguous(), h.contiguous().float()
+        cfg = ctypes.byref(self.cfg)
+        ws = self.eval_workspace(B, T)
+        st = _stream_handle(self.device)
+        row_nll = torch.empty(B, dtype=torch.float32, device=self.device)
+        if mixture:
+            if self.out_channels % 3 != 0:
+                raise ValueError("out_channels = %d is not 3 * n_mix" % self.out_channels)
+            y = y.contiguous().float()
+            out = torch.empty((B, self.out_channels, T), dtype=torch.float32, device=self.device)
+            self.lib.check(self.lib.wn_forward(cfg, B, T, _ptr(self.flat_params), _ptr(x), _ptr(h), _ptr(out), _ptr(ws),
+                                               ws.numel() * 4, self.flags, st), "wn_forward")
+            rc = self.lib.wn_mol_nll_rows(cfg, B, T, _ptr(out), _ptr(y), t_start, _ptr(t_end), int(num_classes),
+                                          float(log_scale_min), _ptr(row_nll), _ptr(acc), _ptr(ws), ws.numel() * 4, st)
+            self.lib.check(rc, "wn_mol_nll_rows")
+        else:
+            target = target.contiguous()
+            fused = bool(self.lib.wn_forward_loss_fused(cfg, B, T, self.flags))
+            scratch = None if fused else torch.empty((B, self.out_channels, T), dtype=torch.float32, device=self.device)
+            rc = self.lib.wn_forward_nll(cfg, B, T, _ptr(self.flat_params), _ptr(x), _ptr(h), _ptr(target), t_start, _ptr(t_end),
+                                         _ptr(row_nll), _ptr(acc), _ptr(scratch), _ptr(ws), ws.numel() * 4, self.flags, st)
+            self.lib.check(rc, "wn_forward_nll")
+        return row_nll, counts
 
     def backward(self, dlogits, events=None, layers_per_bucket=0, t_first=None, repack=False, dlogits_bound=None, dh=None,
                  param_grads=True):

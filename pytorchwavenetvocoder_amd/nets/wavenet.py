@@ -368,6 +368,7 @@ class WaveNet(nn.Module):
         eng.flat_grads = None
         eng._ws = None
         eng._ws_key = None
+        eng.release_eval_workspace()
         eng._version_sources = tuple(p for _, p in named)
         eng._fwd_version = None
         self._param_slices = slices
@@ -458,6 +459,25 @@ class WaveNet(nn.Module):
         for p, (off, n, shape, dead) in zip(self.parameters(), self._param_slices):
             p.grad = None if dead else flat[off:off + n].view(shape)
         return (loss, dh) if aux_grad else loss
+
+    def evaluate(self, x, h, t=None, y=None, t_start=None, lengths=None, acc=None, num_classes=65536):
+        """Score held-out data: ``(row_nll, counts)`` -- per sequence the SUM of the negative log-likelihoods over the positions
+        ``[t_start, lengths[b])`` (device tensor (B,), no host sync) and the number of those positions (host ints), see
+        ``WaveNetEngine.forward_nll``.  Softmax head: the class targets ``t``; mixture head: the waveform ``y``.  ``acc``:
+        a 1-element float64 device tensor the batch total is added to.  No gradient exists afterwards and none is touched:
+        ``p.grad``, the training workspace and a pending ``backward`` of an earlier forward stay valid, in ``train()`` and
+        ``eval()`` mode alike (the network has no mode-dependent layer)."""
+        if (t is None) == (y is None):
+            raise ValueError("evaluate takes exactly one of t (softmax head) and y (mixture-of-logistics head)")
+        if self.n_mixture > 0:
+            if y is None:
+                raise ValueError("this model has the mixture-of-logistics head (n_mixture = %d): pass the waveform y"
+                                 % self.n_mixture)
+            return self._engine.forward_nll(x, h, y=y, t_start=t_start, lengths=lengths, acc=acc, num_classes=num_classes,
+                                            log_scale_min=self.log_scale_min)
+        if t is None:
+            raise ValueError("this model has the softmax head (n_mixture = 0): pass the class targets t")
+        return self._engine.forward_nll(x, h, target=t, t_start=t_start, lengths=lengths, acc=acc)
 
     # ---- generation (reference wavenet.py:243-511) --------------------------------------------
     def _window_logits(self, x, h_up):
