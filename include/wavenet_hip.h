@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 13
+#define WN_ABI_VERSION 14
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -406,7 +406,35 @@ int wn_grad_norm(const float* grads, int64_t n, int64_t skip_lo, int64_t skip_hi
 int wn_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float eps,
                          float weight_decay, int64_t skip_lo, int64_t skip_hi, const WnOptState* state, void* stream);
 
+/* ---- exponential moving average of the weights inside the Adam launch (since ABI v14; additions only) ----
+ * wn_adam_step / wn_adam_step_guarded with one more flat fp32 buffer `ema` of n elements: params, exp_avg and exp_avg_sq receive
+ * exactly the bits of the plain calls, and with the new weight p_new still in a register the same launch does
+ *     ema[i] = fmaf(w, p_new - ema[i], ema[i]),    w = (float)(1.0 - d_t), formed in double,
+ *     d_t = ema_warmup != 0 ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay.
+ * The increment form is the contract: ema == p_new is its exact fixed point, which d * ema + (1 - d) * p_new is not (for d = 0.9999
+ * the two fp32 coefficients no longer sum to 1 and the fixed point sits about 3e-4 relative off p).  An increment below half an
+ * ulp of ema[i] is lost, as in any fp32 average.
+ * t is the 1-based count of APPLIED steps including this one: `step` in wn_adam_step_ema (the host forms w), the state block's
+ * steps_applied as the preceding wn_grad_norm left it in wn_adam_step_guarded_ema (every thread forms w from it, with the same
+ * double arithmetic: the same t gives the same w bits on both paths).
+ * Skip rule: ema[skip_lo, skip_hi) is never written, like the other three buffers.
+ * Apply rule (guarded): when state->apply == 0 nothing at all is written -- weights, moments and ema stay, and t does not advance.
+ * WnOptState keeps its 56 bytes.  One launch each (the guarded step stays 3 launches with its norm).
+ * Errors (wn_last_error): ema == NULL, ema_decay outside [0, 1), ema overlapping params. */
+int wn_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, int64_t step,
+                     float lr, float beta1, float beta2, float eps, float weight_decay, int64_t skip_lo, int64_t skip_hi,
+                     double ema_decay, int ema_warmup, void* stream);
+int wn_adam_step_guarded_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float eps,
+                             float weight_decay, int64_t skip_lo, int64_t skip_hi, const WnOptState* state, double ema_decay,
+                             int ema_warmup, void* stream);
+
 /* ---- op-level entry points (used by the composite calls above; exported for parity tests) ---- */
+
+/* a[i] <-> b[i] for i < n, in place and without a temporary buffer (since ABI v14): how the weights and their moving average change
+ * places around a scoring pass.  Both pointers need 4-byte alignment only; pointers that share their address modulo 16 are moved
+ * by 16-byte accesses with a scalar head and tail.  Bit patterns are moved as they are (NaN payloads included).  Overlapping
+ * ranges are an error. */
+int wn_op_swap(float* a, float* b, int64_t n, void* stream);
 
 /* OneHot + CausalConv1d(Q->R,K) as a gather (wavenet.py:78-92,513-516).  weight (R,Q,K), bias (R). */
 int wn_op_front(const float* weight, const float* bias, const int64_t* x, float* out /*(B,R,T)*/, float* scratch /*K*Q*R*/,

@@ -120,7 +120,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -134,6 +134,7 @@ EXPORTS = [
     "wn_softmax_ce_loss_ragged", "wn_forward_loss_ragged", "wn_mol_loss_ragged",
     "wn_grad_norm_scratch_floats", "wn_grad_norm", "wn_adam_step_guarded",
     "wn_forward_nll", "wn_softmax_nll_rows", "wn_mol_nll_rows", "wn_op_row_sums",
+    "wn_adam_step_ema", "wn_adam_step_guarded_ema", "wn_op_swap",
 ]
 
 
@@ -191,6 +192,10 @@ class WnLibrary(object):
         L.wn_grad_norm_scratch_floats.restype = i64
         L.wn_grad_norm.argtypes = [vp, i64, i64, i64, f, i, f, f, f, vp, vp, vp]
         L.wn_adam_step_guarded.argtypes = [vp, vp, vp, vp, i64, f, f, i64, i64, vp, vp]
+        d = ctypes.c_double
+        L.wn_adam_step_ema.argtypes = [vp, vp, vp, vp, vp, i64, i64, f, f, f, f, f, i64, i64, d, i, vp]
+        L.wn_adam_step_guarded_ema.argtypes = [vp, vp, vp, vp, vp, i64, f, f, i64, i64, vp, d, i, vp]
+        L.wn_op_swap.argtypes = [vp, vp, i64, vp]
         L.wn_op_front.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.wn_op_causal_conv.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.wn_op_causal_conv_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]

@@ -47,7 +47,21 @@ def get_parser():
             parser.add_argument("--" + name, required=True, type=typ, help=text)
         else:
             parser.add_argument("--" + name, default=default, type=typ, help=text)
+    # extension (not a reference flag): decode from the moving average of the weights that train.py --ema_decay keeps
+    parser.add_argument("--weights", default="model", choices=["model", "ema"], type=str,
+                        help="which weights of the checkpoint to decode from: the last iterate (\"model\") or their "
+                             "exponential moving average (\"ema\", written by train.py --ema_decay)")
     return parser
+
+
+def checkpoint_weights(path, which="model"):
+    """The state dict to decode from: ``checkpoint["model"]``, or ``checkpoint["ema"]`` (KeyError with a clear message when the
+    checkpoint was written without --ema_decay)."""
+    checkpoint = torch.load(path, map_location="cpu", weights_only=False)
+    if which == "ema" and "ema" not in checkpoint:
+        raise KeyError("--weights ema: %s holds no \"ema\" entry (it was written by a run without --ema_decay; "
+                       "checkpoint-best.pkl of a run with it holds the averaged weights as \"model\")." % path)
+    return checkpoint[which]
 
 
 def pad_list(batch_list, pad_value=0.0):
@@ -136,7 +150,7 @@ def _decode_files(gpu, feat_list, args, config, mean, scale):
     torch.cuda.set_device(gpu)
     device = torch.device("cuda", gpu)
     model = build_model(config)
-    model.load_state_dict(torch.load(args.checkpoint, map_location="cpu", weights_only=False)["model"])
+    model.load_state_dict(checkpoint_weights(args.checkpoint, getattr(args, "weights", "model")))
     model.eval()
     model.to(device)
     generator = decode_generator(
@@ -184,6 +198,12 @@ def main(argv=None):
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     config = torch.load(args.config, weights_only=False)
+    if args.weights == "ema":   # fail here, with the reason, not in a worker process
+        try:
+            checkpoint_weights(args.checkpoint, "ema")
+        except KeyError as e:
+            logging.error(e.args[0])
+            sys.exit(1)
     if os.path.isdir(args.feats):
         feat_list = sorted(find_files(args.feats, "*.h5"))
     elif os.path.isfile(args.feats):

@@ -17,6 +17,7 @@ runs unchanged.  What differs is how a step is executed:
   * the wav / feature / stats readers fall back to scipy / .npz when soundfile / h5py are absent.
 """
 import argparse
+import contextlib
 import logging
 import os
 import sys
@@ -503,10 +504,13 @@ def dev_loss(model, dev, rank, world, device):
 
 def save_checkpoint(checkpoint_dir, model, optimizer, iterations, dev=None):
     """``checkpoint-%d.pkl`` = {"model", "optimizer", "iterations"} (reference train.py:315-332); with a held-out set
-    (--dev_waveforms) also "dev" = {"best_loss", "best_iterations"}."""
+    (--dev_waveforms) also "dev" = {"best_loss", "best_iterations"}; with a moving average of the weights (--ema_decay) also
+    "ema" = the averaged weights under the keys of "model"."""
     checkpoint = {"model": model.state_dict(), "optimizer": optimizer.state_dict(), "iterations": iterations}
     if dev is not None:
         checkpoint["dev"] = dict(dev)
+    if getattr(optimizer, "ema_decay", None) is not None:
+        checkpoint["ema"] = optimizer.ema_state_dict()
     if not os.path.exists(checkpoint_dir):
         os.makedirs(checkpoint_dir)
     torch.save(checkpoint, checkpoint_dir + "/checkpoint-%d.pkl" % iterations)
@@ -588,6 +592,12 @@ def get_parser():
     parser.add_argument("--eval_interval", default=0, type=int,
                         help="iterations between two passes over the held-out set (0: at every --checkpoint_interval)")
     parser.add_argument("--eval_batch_size", default=8, type=int, help="held-out utterances scored per padded batch")
+    # extensions (not reference flags): an exponential moving average of the weights, updated inside the Adam launch
+    parser.add_argument("--ema_decay", default=0.0, type=float,
+                        help="decay of the moving average of the weights that the held-out set is scored with and "
+                             "checkpoint-best.pkl holds (0: off)")
+    parser.add_argument("--ema_warmup", default=True, type=strtobool,
+                        help="decay min(ema_decay, (1 + t) / (10 + t)) at applied step t, so the average forgets the initial weights")
     parser.add_argument("--resume", default=None, nargs="?", type=str, help="checkpoint to continue from")
     return parser
 
@@ -712,9 +722,11 @@ def _worker(rank, world, args, port):
     eval_interval = (int(getattr(args, "eval_interval", 0)) or args.checkpoint_interval) if dev is not None else 0
 
     max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
+    ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
     optimizer = FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay,
                           max_grad_norm=max_grad_norm if max_grad_norm > 0.0 else None,
-                          skip_nonfinite=bool(getattr(args, "skip_nonfinite_steps", False)))
+                          skip_nonfinite=bool(getattr(args, "skip_nonfinite_steps", False)),
+                          ema_decay=ema_decay if ema_decay > 0.0 else None, ema_warmup=bool(getattr(args, "ema_warmup", True)))
     if args.resume is not None and len(args.resume) != 0:
         checkpoint = torch.load(args.resume, map_location=lambda storage, loc: storage, weights_only=False)
         iterations = checkpoint["iterations"]
@@ -722,6 +734,11 @@ def _worker(rank, world, args, port):
         optimizer.load_state_dict(checkpoint["optimizer"])
         if dev is not None:
             dev_best = dev_best_from_checkpoint(checkpoint)
+        if optimizer.ema_decay is not None:
+            if "ema" in checkpoint:
+                optimizer.load_ema_state_dict(checkpoint["ema"])
+            else:
+                logging.warning("the checkpoint holds no moving average (\"ema\"): it starts from the model weights.")
         logging.info("restored from %d-iter checkpoint." % iterations)
     else:
         iterations = 0
@@ -785,8 +802,12 @@ def _worker(rank, world, args, port):
         if eval_interval > 0 and (i + 1) % eval_interval == 0:
             # every rank scores its shard of the held-out list; one all-reduce of [nll, positions] makes the mean
             start = time.time()
-            loss_dev, n_utt, n_pos = dev_loss(model, dev, rank, world, device)
+            # with a moving average the pass scores the AVERAGED weights, and those are what checkpoint-best.pkl keeps
+            with (optimizer.ema_weights() if optimizer.ema_decay is not None else contextlib.nullcontext()):
+                loss_dev, n_utt, n_pos = dev_loss(model, dev, rank, world, device)
             if is_main:
+                if optimizer.ema_decay is not None:
+                    logging.info("(iter:%d) the dev loss is that of the averaged weights (ema_decay %g)." % (i + 1, ema_decay))
                 logging.info("(iter:%d) dev loss = %.6f (%d utterances, %d samples, %.3f sec)" % (
                     i + 1, loss_dev, n_utt, n_pos, time.time() - start))
                 with open(args.expdir + "/dev_loss.txt", "a") as fh:
@@ -794,8 +815,11 @@ def _worker(rank, world, args, port):
             if loss_dev == loss_dev and (dev_best is None or loss_dev < dev_best[0]):   # (same numbers on every rank)
                 dev_best = (loss_dev, i + 1)
                 if is_main:
-                    torch.save({"model": model.state_dict(), "iterations": i + 1, "dev_loss": loss_dev},
-                               args.expdir + "/checkpoint-best.pkl")
+                    best = {"model": model.state_dict(), "iterations": i + 1, "dev_loss": loss_dev}
+                    if optimizer.ema_decay is not None:   # "model" = what was scored: the reference's decode tool reads it as it is
+                        best["model"] = optimizer.ema_state_dict()
+                        best["ema_decay"] = ema_decay
+                    torch.save(best, args.expdir + "/checkpoint-best.pkl")
                     logging.info("best checkpoint created (dev loss %.6f)." % loss_dev)
         if (i + 1) % args.checkpoint_interval == 0 and is_main:
             if dev is None:
@@ -805,7 +829,10 @@ def _worker(rank, world, args, port):
 
     generator.close()   # stop the producer thread before the interpreter tears the runtime down under it
     if is_main:
-        torch.save({"model": model.state_dict()}, args.expdir + "/checkpoint-final.pkl")
+        final = {"model": model.state_dict()}
+        if optimizer.ema_decay is not None:
+            final["ema"] = optimizer.ema_state_dict()
+        torch.save(final, args.expdir + "/checkpoint-final.pkl")
         logging.info("final checkpoint created.")
     if world > 1:
         dist.barrier()

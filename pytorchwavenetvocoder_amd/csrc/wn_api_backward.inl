@@ -523,3 +523,42 @@ extern "C" int wn_adam_step_guarded(float* params, const float* grads, float* ex
                            (wn_stream_t)stream));
     return rt_check("wn_adam_step_guarded");
 }
+
+// ------------------------------------------------------------------------------------------
+// Exponential moving average of the weights in the Adam launch (ABI v14) and the in-place exchange of two buffers.
+static bool ranges_overlap(const float* a, const float* b, int64_t n) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b), len = (uintptr_t)n * sizeof(float);
+    return a0 < b0 + len && b0 < a0 + len;
+}
+
+static const char* ema_argument_error(const float* params, const float* ema, int64_t n, double ema_decay) {
+    if (!ema) return "ema is NULL";
+    if (!(ema_decay >= 0.0 && ema_decay < 1.0)) return "ema_decay outside [0, 1)";
+    if (ranges_overlap(params, ema, n)) return "ema overlaps params";
+    return nullptr;
+}
+
+extern "C" int wn_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t skip_lo,
+                                int64_t skip_hi, double ema_decay, int ema_warmup, void* stream) {
+    api_enter();
+    if (!params || !grads || !exp_avg || !exp_avg_sq || n <= 0 || step < 1) return fail(1, "bad wn_adam_step_ema argument");
+    if (const char* why = ema_argument_error(params, ema, n, ema_decay)) return fail(1, "wn_adam_step_ema: %s", why);
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    WN_TRY(wn_adam_ema(params, grads, exp_avg, exp_avg_sq, ema, (long)n, (float)((double)lr / bc1), (float)sqrt(bc2), beta1, beta2,
+                       eps, weight_decay, (long)skip_lo, (long)skip_hi, wn_ema_weight(ema_decay, ema_warmup, step),
+                       (wn_stream_t)stream));
+    return rt_check("wn_adam_step_ema");
+}
+
+extern "C" int wn_adam_step_guarded_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                        float eps, float weight_decay, int64_t skip_lo, int64_t skip_hi, const WnOptState* state,
+                                        double ema_decay, int ema_warmup, void* stream) {
+    api_enter();
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || n <= 0) return fail(1, "bad wn_adam_step_guarded_ema argument");
+    if (const char* why = ema_argument_error(params, ema, n, ema_decay)) return fail(1, "wn_adam_step_guarded_ema: %s", why);
+    WN_TRY(wn_adam_guarded_ema(params, grads, exp_avg, exp_avg_sq, ema, (long)n, eps, weight_decay, (long)skip_lo, (long)skip_hi,
+                               state, ema_decay, ema_warmup, (wn_stream_t)stream));
+    return rt_check("wn_adam_step_guarded_ema");
+}

@@ -140,3 +140,13 @@ extern "C" int wn_op_row_sums(const float* partial, int B, int nblk, float* row_
     WN_TRY(wn_row_sums(partial, B, nblk, row_out, acc, 0, (wn_stream_t)stream));
     return rt_check("wn_op_row_sums");
 }
+
+// a[i] <-> b[i] in place (FusedAdam.ema_weights: the weights and their moving average change places, one launch each way).
+extern "C" int wn_op_swap(float* a, float* b, int64_t n, void* stream) {
+    api_enter();
+    if (!a || !b || n <= 0) return fail(1, "bad wn_op_swap argument");
+    if ((reinterpret_cast<uintptr_t>(a) & 3) || (reinterpret_cast<uintptr_t>(b) & 3)) return fail(1, "wn_op_swap: the buffers need 4-byte alignment");
+    if (ranges_overlap(a, b, n)) return fail(1, "wn_op_swap: the two ranges overlap");
+    WN_TRY(wn_swap(a, b, (long)n, (wn_stream_t)stream));
+    return rt_check("wn_op_swap");
+}

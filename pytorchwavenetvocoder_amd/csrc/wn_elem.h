@@ -70,6 +70,25 @@ int wn_grad_norm_finalize(const double* partial, int nb, float max_norm, int gua
 int wn_adam_guarded(float* p, const float* g, float* m, float* v, long n, float eps, float weight_decay, long skip_lo, long skip_hi,
                     const struct WnOptState* state, wn_stream_t st);
 
+// Exponential moving average of the weights inside the Adam launch (include/wavenet_hip.h, ABI v14): e += w (p_new - e).
+// wn_ema_weight is the ONE place the averaging weight w = (float)(1 - d_t) is formed, in double, for the host (unguarded step: t =
+// the caller's step) and for every thread of the guarded launch (t = the state block's steps_applied): the same t gives the same
+// bits.  d_t = min(decay, (1 + t) / (10 + t)) with the warm-up, else decay; t counts the applied steps from 1.
+static __host__ __device__ __forceinline__ float wn_ema_weight(double decay, int warmup, int64_t t) {
+    double d = decay;
+    if (warmup) {
+        const double dw = (1.0 + (double)t) / (10.0 + (double)t);
+        if (dw < d) d = dw;
+    }
+    return (float)(1.0 - d);
+}
+int wn_adam_ema(float* p, const float* g, float* m, float* v, float* e, long n, float lr_over_bc1, float sqrt_bc2, float beta1,
+                float beta2, float eps, float weight_decay, long skip_lo, long skip_hi, float w, wn_stream_t st);
+int wn_adam_guarded_ema(float* p, const float* g, float* m, float* v, float* e, long n, float eps, float weight_decay, long skip_lo,
+                        long skip_hi, const struct WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st);
+// a[i] <-> b[i], i < n: two non-overlapping fp32 buffers of 4-byte alignment, exchanged in place
+int wn_swap(float* a, float* b, long n, wn_stream_t st);
+
 // dst[d_off + i0*d0 + i1*d1 + i2*d2 + l*dl] = src[s_off + i0*s0 + i1*s1 + i2*s2 + l*sl]
 typedef struct WnCopy4 {
     int n0, n1, n2, nl;

@@ -595,6 +595,136 @@ int wn_adam_guarded(float* p, const float* g, float* m, float* v, long n, float 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Adam with an exponential moving average of the weights (wn_adam_step_ema / wn_adam_step_guarded_ema): the
+// arithmetic of k_adam (GUARDED: of k_adam_guarded) expression for expression -- p, m, v get the bits of the plain launches -- and,
+// with the new weight still in a register, e += w (p_new - e) as ONE fma.  The increment form has e == p_new as its exact fixed
+// point; d e + (1 - d) p_new has not (the two fp32 coefficients of d = 0.9999 do not sum to 1).  k_adam and k_adam_guarded are
+// left as they are: the EMA-off paths keep their code objects.  9 words per element move instead of 7.
+template <bool GUARDED>
+static __device__ __forceinline__ void wn_adam_ema_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, float* __restrict__ e, long n, float lr_over_bc1,
+                                                         float sqrt_bc2, float coef, float beta1, float beta2, float eps, float wd,
+                                                         long skip_lo, long skip_hi, float w) {
+    const long stride = (long)gridDim.x * WN_TPB;
+    for (long i = (long)blockIdx.x * WN_TPB + threadIdx.x; i < n; i += stride) {
+        if (i >= skip_lo && i < skip_hi) continue;
+        const float pv = p[i];
+        const float ev = e[i];
+        float gv = GUARDED ? wn_fmul_rn(coef, g[i]) : g[i];
+        if (wd != 0.0f) gv += wd * pv;
+        const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
+        const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
+        m[i] = mv;
+        v[i] = vv;
+        const float denom = sqrtf(vv) / sqrt_bc2 + eps;
+        const float pn = pv - lr_over_bc1 * (mv / denom);
+        p[i] = pn;
+        e[i] = fmaf(w, pn - ev, ev);
+    }
+}
+
+__global__ __launch_bounds__(WN_TPB) void k_adam_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                     float* __restrict__ v, float* __restrict__ e, long n, float lr_over_bc1,
+                                                     float sqrt_bc2, float beta1, float beta2, float eps, float wd, long skip_lo,
+                                                     long skip_hi, float w) {
+    wn_adam_ema_sweep<false>(p, g, m, v, e, n, lr_over_bc1, sqrt_bc2, 1.0f, beta1, beta2, eps, wd, skip_lo, skip_hi, w);
+}
+
+// the averaging weight from the device's own count of applied steps (this one included: the finalize launch has counted it)
+__global__ __launch_bounds__(WN_TPB) void k_adam_guarded_ema(float* __restrict__ p, const float* __restrict__ g,
+                                                             float* __restrict__ m, float* __restrict__ v, float* __restrict__ e,
+                                                             long n, float eps, float wd, long skip_lo, long skip_hi,
+                                                             const WnOptState* __restrict__ state, double ema_decay,
+                                                             int ema_warmup) {
+    if (!state->apply) return;
+    const float w = wn_ema_weight(ema_decay, ema_warmup, state->steps_applied);
+    wn_adam_ema_sweep<true>(p, g, m, v, e, n, state->lr_over_bc1, state->sqrt_bc2, state->clip_coef, state->beta1, state->beta2,
+                            eps, wd, skip_lo, skip_hi, w);
+}
+
+static unsigned wn_adam_blocks(long n) {
+    long nb = (n + WN_TPB - 1) / WN_TPB;
+    return (unsigned)(nb > 2048 ? 2048 : (nb < 1 ? 1 : nb));
+}
+
+int wn_adam_ema(float* p, const float* g, float* m, float* v, float* e, long n, float lr_over_bc1, float sqrt_bc2, float beta1,
+                float beta2, float eps, float weight_decay, long skip_lo, long skip_hi, float w, wn_stream_t st) {
+    WN_PROF("adam_ema", 0.0, 36.0 * (double)n, st);
+    WN_LAUNCH(k_adam_ema, dim3(wn_adam_blocks(n)), dim3(WN_TPB), 0, st, p, g, m, v, e, n, lr_over_bc1, sqrt_bc2, beta1, beta2, eps,
+              weight_decay, skip_lo, skip_hi, w);
+    return 0;
+}
+
+int wn_adam_guarded_ema(float* p, const float* g, float* m, float* v, float* e, long n, float eps, float weight_decay, long skip_lo,
+                        long skip_hi, const WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st) {
+    WN_PROF("adam_guarded_ema", 0.0, 36.0 * (double)n, st);
+    WN_LAUNCH(k_adam_guarded_ema, dim3(wn_adam_blocks(n)), dim3(WN_TPB), 0, st, p, g, m, v, e, n, eps, weight_decay, skip_lo, skip_hi,
+              state, ema_decay, ema_warmup);
+    return 0;
+}
+
+// a[i] <-> b[i] with no temporary buffer.  The pointers are 4-byte aligned only: when they share their address modulo 16 the body
+// moves 16-byte quads (WN_SWAP_BATCH of each buffer in flight per thread) behind a scalar head and in front of a scalar tail, as in
+// k_grad_sumsq; otherwise every element goes alone.  a and b do not overlap (the entry point refuses that), so every element is
+// read and written by exactly one thread.
+#define WN_SWAP_MAXBLOCKS 512
+#define WN_SWAP_BATCH 2
+__global__ __launch_bounds__(WN_TPB) void k_swap(float* a, float* b, long n) {
+    const long stride = (long)gridDim.x * WN_TPB;
+    const long tid = (long)blockIdx.x * WN_TPB + threadIdx.x;
+    if ((reinterpret_cast<uintptr_t>(a) & 15) != (reinterpret_cast<uintptr_t>(b) & 15)) {
+        for (long i = tid; i < n; i += stride) {
+            const float x = a[i], y = b[i];
+            a[i] = y;
+            b[i] = x;
+        }
+        return;
+    }
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(a) & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const long n4 = (n - head) >> 2;
+    float4* a4 = reinterpret_cast<float4*>(a + head);
+    float4* b4 = reinterpret_cast<float4*>(b + head);
+    for (long j = tid; j < n4; j += WN_SWAP_BATCH * stride) {
+        float4 x[WN_SWAP_BATCH], y[WN_SWAP_BATCH];
+        WN_UNROLL
+        for (int k = 0; k < WN_SWAP_BATCH; ++k) {
+            const long jk = j + k * stride;
+            if (jk < n4) {
+                x[k] = a4[jk];
+                y[k] = b4[jk];
+            }
+        }
+        WN_UNROLL
+        for (int k = 0; k < WN_SWAP_BATCH; ++k) {
+            const long jk = j + k * stride;
+            if (jk < n4) {
+                a4[jk] = y[k];
+                b4[jk] = x[k];
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 8) {   // scalar head (threads 0..3) and tail (threads 4..7): at most 3 elements each
+        const long t = threadIdx.x & 3;
+        const long i = threadIdx.x < 4 ? t : head + 4 * n4 + t;
+        const long end = threadIdx.x < 4 ? head : n;
+        if (i < end) {
+            const float x = a[i], y = b[i];
+            a[i] = y;
+            b[i] = x;
+        }
+    }
+}
+
+int wn_swap(float* a, float* b, long n, wn_stream_t st) {
+    WN_PROF("swap", 0.0, 16.0 * (double)n, st);
+    long nb = ((n + 3) / 4 + WN_TPB - 1) / WN_TPB;
+    nb = nb < 1 ? 1 : (nb > WN_SWAP_MAXBLOCKS ? WN_SWAP_MAXBLOCKS : nb);
+    WN_LAUNCH(k_swap, dim3((unsigned)nb), dim3(WN_TPB), 0, st, a, b, n);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WN_TPB) void k_copy4(float* __restrict__ dst, const float* __restrict__ src, WnCopy4 c) {
     const long total = (long)c.nl * c.n0 * c.n1 * c.n2;
     const long i = (long)blockIdx.x * WN_TPB + threadIdx.x;

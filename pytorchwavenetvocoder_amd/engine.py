@@ -609,6 +609,41 @@ class WaveNetEngine(object):
         self.lib.check(rc, "wn_adam_step_guarded")
         self._params_epoch += 1
 
+    # ---- exponential moving average of the weights (include/wavenet_hip.h, ABI v14) -----------------
+    def adam_step_ema(self, exp_avg, exp_avg_sq, ema, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.999,
+                      ema_warmup=True):
+        """``adam_step`` that also moves the flat buffer ``ema`` towards the new weights in the same launch:
+        ``ema += (1 - d_t) (p_new - ema)``, ``d_t = min(ema_decay, (1 + step) / (10 + step))`` with the warm-up."""
+        self._check_device(exp_avg, exp_avg_sq, ema)
+        rc = self.lib.wn_adam_step_ema(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(ema),
+                                       self.n_params, int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                       float(weight_decay), self.dead_range[0], self.dead_range[1], float(ema_decay),
+                                       int(bool(ema_warmup)), _stream_handle(self.device))
+        self.lib.check(rc, "wn_adam_step_ema")
+        self._params_epoch += 1
+
+    def adam_step_guarded_ema(self, exp_avg, exp_avg_sq, ema, state, eps=1e-8, weight_decay=0.0, ema_decay=0.999,
+                              ema_warmup=True):
+        """``adam_step_guarded`` with the moving average: the warm-up index is the device's count of applied steps, and a step
+        that does not apply leaves ``ema`` alone like everything else."""
+        self._check_device(exp_avg, exp_avg_sq, ema, state)
+        rc = self.lib.wn_adam_step_guarded_ema(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                               _ptr(ema), self.n_params, float(eps), float(weight_decay), self.dead_range[0],
+                                               self.dead_range[1], _ptr(state), float(ema_decay), int(bool(ema_warmup)),
+                                               _stream_handle(self.device))
+        self.lib.check(rc, "wn_adam_step_guarded_ema")
+        self._params_epoch += 1
+
+    def swap_params(self, other):
+        """Exchange the flat parameter buffer with ``other`` (same length, same device) element by element: one launch, no
+        temporary.  The parameter version changes, so everything derived from the weights (packed weight sets) follows."""
+        self._check_device(other)
+        if other.dtype != torch.float32 or other.numel() != self.n_params or not other.is_contiguous():
+            raise ValueError("swap_params takes a contiguous fp32 tensor of n_params elements")
+        rc = self.lib.wn_op_swap(_ptr(self.flat_params), _ptr(other), self.n_params, _stream_handle(self.device))
+        self.lib.check(rc, "wn_op_swap")
+        self._params_epoch += 1
+
     # ---- autoregressive decode (reference wavenet.py:309-511) ---------------------------------
     def decode_supported(self):
         return bool(self.lib.wn_decode_supported(ctypes.byref(self.cfg)))

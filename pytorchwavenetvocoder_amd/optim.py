@@ -17,8 +17,20 @@ Opt-in, both free of host synchronisation:
 ``skip_nonfinite=True`` a step whose gradient holds a NaN or an inf changes nothing (weights, moments, step count) and is
                         counted in ``steps_skipped()``.
 
-With both at their defaults ``step()`` is the one ``adam`` launch with the host's step count, bit for bit as before.
+``ema_decay=d``          an exponential moving average of the weights, kept in a second flat buffer and updated by
+                        the Adam launch itself while the new weight is in a register: ``e += (1 - d_t) (p_new - e)`` with
+                        ``d_t = min(d, (1 + t) / (10 + t))`` (``ema_warmup=True``; t = applied steps, this one included) or
+                        ``d_t = d``.  A skipped step leaves the average alone and does not advance t.  Weights and moments get
+                        the bits they get without it.  ``opt.ema`` is the flat buffer, ``ema_state_dict()`` /
+                        ``load_ema_state_dict()`` (de)serialise it under the model's keys, and ``with opt.ema_weights():``
+                        runs its body on the averaged weights.  Ranks of a data-parallel run hold identical weights and
+                        gradients, hence identical averages, without communication.
+
+With all three at their defaults ``step()`` is the one ``adam`` launch with the host's step count, bit for bit as before.
+``state_dict()`` never holds the average: it stays in torch.optim.Adam's format.
 """
+import contextlib
+
 import torch
 
 from . import _lib
@@ -26,7 +38,7 @@ from . import _lib
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, ema_decay=None, ema_warmup=True):
         if not hasattr(model, "engine"):
             raise TypeError("FusedAdam takes the WaveNet model (it updates the model's flat buffer)")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
@@ -43,6 +55,12 @@ class FusedAdam(torch.optim.Optimizer):
         self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
         self._opt_state = None     # device WnOptState + the norm's scratch: allocated once, on the first guarded use
         self._norm_scratch = None
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must lie in [0, 1) (None = no moving average)")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self._ema = None           # the shadow buffer: a copy of the flat weights at its first use
+        self._ema_swapped = False  # inside ema_weights(): the two buffers have changed places
 
     def _guard_buffers(self):
         eng = self.model.engine
@@ -88,14 +106,74 @@ class FusedAdam(torch.optim.Optimizer):
                 self._exp_avg_sq.copy_(old[1])
         return self._exp_avg, self._exp_avg_sq
 
+    def _ema_buffer(self):
+        eng = self.model.engine
+        if self._ema is None:
+            self._ema = eng.flat_params.detach().clone()
+        elif self._ema.device != eng.flat_params.device:
+            self._ema = self._ema.to(eng.flat_params.device)
+        return self._ema
+
+    @property
+    def ema(self):
+        """The flat moving average (same layout as ``engine.flat_params``), None when ``ema_decay`` is None.  Inside
+        ``ema_weights()`` this buffer holds the training weights."""
+        return None if self.ema_decay is None else self._ema_buffer()
+
+    def _need_ema(self):
+        if self.ema_decay is None:
+            raise RuntimeError("this optimizer keeps no moving average (ema_decay=None)")
+
+    def ema_state_dict(self):
+        """Clones of the averaged weights under the model's ``state_dict`` keys and shapes (a dict ``load_state_dict`` of a
+        model, or the reference's decode tool, takes as it is)."""
+        self._need_ema()
+        src = self.model.engine.flat_params if self._ema_swapped else self._ema_buffer()
+        return {k: src[off:off + n].view(shape).detach().clone()
+                for (k, _), (off, n, shape, dead) in zip(self.model.named_parameters(), self.model._param_slices)}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd):
+        self._need_ema()
+        if self._ema_swapped:
+            raise RuntimeError("load_ema_state_dict() inside ema_weights()")
+        names = [k for k, _ in self.model.named_parameters()]
+        if set(sd.keys()) != set(names):
+            raise KeyError("the EMA state dict does not have the model's keys: %s" % sorted(set(sd.keys()) ^ set(names)))
+        ema = self._ema_buffer()
+        for k, (off, n, shape, dead) in zip(names, self.model._param_slices):
+            if tuple(sd[k].shape) != tuple(shape):
+                raise ValueError("%s: shape %s, the model has %s" % (k, tuple(sd[k].shape), tuple(shape)))
+            ema[off:off + n].copy_(sd[k].reshape(-1))
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the body on the averaged weights: the weights and the average change places (one ``swap`` launch, no temporary)
+        and change back on exit, also when the body raises.  ``step()`` inside and nesting raise RuntimeError.  The parameter
+        version changes on entry and on exit, so the block must not sit between a forward and its ``backward()``."""
+        self._need_ema()
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() is already active")
+        eng = self.model.engine
+        eng.swap_params(self._ema_buffer())
+        self._ema_swapped = True
+        try:
+            yield self.model
+        finally:
+            eng.swap_params(self._ema_buffer())
+            self._ema_swapped = False
+
     @torch.no_grad()
     def step(self, closure=None):
+        if self._ema_swapped:
+            raise RuntimeError("step() inside ema_weights(): the model holds the averaged weights")
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         eng = self.model.engine
         m, v = self._buffers()
+        ema = self.ema
         flat_g = eng.grads()
         # gradients produced by the autograd path live in separate tensors: gather them
         lo = flat_g.data_ptr()
@@ -106,7 +184,8 @@ class FusedAdam(torch.optim.Optimizer):
                 if not dead:
                     flat_g[off:off + n].zero_()
                     sl = slice(off, off + n)
-                    skipped.append((sl, eng.flat_params[sl].clone(), m[sl].clone(), v[sl].clone()))
+                    skipped.append((sl, eng.flat_params[sl].clone(), m[sl].clone(), v[sl].clone(),
+                                    None if ema is None else ema[sl].clone()))
                 continue
             if not (lo <= p.grad.data_ptr() < hi):
                 flat_g[off:off + n].copy_(p.grad.reshape(-1))
@@ -116,14 +195,23 @@ class FusedAdam(torch.optim.Optimizer):
             # without a gradient add 0, which is torch leaving them out)
             state, scratch = self._guard_buffers()
             eng.grad_norm(state, scratch, self.max_grad_norm, self.skip_nonfinite, group["lr"], group["betas"])
-            eng.adam_step_guarded(m, v, state, group["eps"], group["weight_decay"])
+            if ema is None:
+                eng.adam_step_guarded(m, v, state, group["eps"], group["weight_decay"])
+            else:
+                eng.adam_step_guarded_ema(m, v, ema, state, group["eps"], group["weight_decay"], self.ema_decay, self.ema_warmup)
         else:
             self._step += 1
-            eng.adam_step(m, v, self._step, group["lr"], group["betas"], group["eps"], group["weight_decay"])
-        for sl, p0, m0, v0 in skipped:   # the one launch covers the whole flat buffer: put the skipped slices back
+            if ema is None:
+                eng.adam_step(m, v, self._step, group["lr"], group["betas"], group["eps"], group["weight_decay"])
+            else:
+                eng.adam_step_ema(m, v, ema, self._step, group["lr"], group["betas"], group["eps"], group["weight_decay"],
+                                  self.ema_decay, self.ema_warmup)
+        for sl, p0, m0, v0, e0 in skipped:   # the one launch covers the whole flat buffer: put the skipped slices back
             eng.flat_params[sl].copy_(p0)
             m[sl].copy_(m0)
             v[sl].copy_(v0)
+            if e0 is not None:
+                ema[sl].copy_(e0)
         return loss
 
     # ---- torch.optim.Adam compatible (de)serialisation --------------------------------------
