@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 14
+#define WN_ABI_VERSION 15
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -435,6 +435,22 @@ int wn_adam_step_guarded_ema(float* params, const float* grads, float* exp_avg, 
  * by 16-byte accesses with a scalar head and tail.  Bit patterns are moved as they are (NaN payloads included).  Overlapping
  * ranges are an error. */
 int wn_op_swap(float* a, float* b, int64_t n, void* stream);
+
+/* Gradient accumulation over micro-batches (since ABI v15): the sum of the gradients of several backward passes in front of
+ * ONE optimizer step.  `acc` is the caller's accumulator, `grad` the gradient buffer wn_backward fills; both hold n floats.
+ *     WN_ACCUM_SET     acc[i]  = grad[i]              first micro-batch: opens the sum, whatever acc held before
+ *     WN_ACCUM_ADD     acc[i]  = acc[i] + grad[i]     a middle micro-batch
+ *     WN_ACCUM_FINISH  grad[i] = acc[i] + grad[i]     last micro-batch: the sum lands in the gradient buffer itself, where
+ *                                                     wn_grad_norm / wn_adam_step* and an all-reduce read it
+ * One plain fp32 add per element, no scaling, no compensation: after SET, ADD, ..., FINISH over g0, g1, g2, ... the gradient
+ * buffer holds ((g0 + g1) + g2) + ..., the bits of torch's `p.grad += g` in the same order.  NaN and +-inf propagate, so the
+ * non-finite guard of wn_grad_norm sees a bad micro-batch in the sum.  The buffer a mode does not write is not written at all.
+ * A pointer and a length: the call may cover a sub-range of the two flat buffers (a gradient bucket, wn_bucket_range), so both
+ * pointers need 4-byte alignment only; pointers that share their address modulo 16 are moved by 16-byte accesses with a scalar
+ * head and tail.  The grid depends on n alone.  One launch, 12 n bytes of traffic (8 n for WN_ACCUM_SET).
+ * Errors (wn_last_error): NULL, n <= 0, a mode that is none of the three, overlapping ranges. */
+enum { WN_ACCUM_SET = 0, WN_ACCUM_ADD = 1, WN_ACCUM_FINISH = 2 };
+int wn_op_accumulate(float* acc, float* grad, int64_t n, int mode, void* stream);
 
 /* OneHot + CausalConv1d(Q->R,K) as a gather (wavenet.py:78-92,513-516).  weight (R,Q,K), bias (R). */
 int wn_op_front(const float* weight, const float* bias, const int64_t* x, float* out /*(B,R,T)*/, float* scratch /*K*Q*R*/,

@@ -113,6 +113,8 @@ FLAG_CHAIN_F16PAIR = 1 << 30  # the fused backward chain on the block-scaled fp1
 # every flag that narrows a contraction below the six bf16 products (engine.SIX_PRODUCT_FLAGS = DEFAULT_FLAGS without them)
 NARROW_FLAGS = FLAG_DW_3PRODUCT | FLAG_DW_F16PAIR | FLAG_MM_F16PAIR | FLAG_FUSED_F16PAIR | FLAG_CHAIN_F16PAIR
 FLAG_REPACK = 1 << 17  # wn_backward: rebuild the packed / pre-split weight sets from the params given to that call
+# wn_op_accumulate modes (include/wavenet_hip.h WN_ACCUM_*): acc = grad, acc = acc + grad, grad = acc + grad
+ACCUM_SET, ACCUM_ADD, ACCUM_FINISH = range(3)
 
 
 def flag_dw_flush(n):
@@ -120,7 +122,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -135,6 +137,7 @@ EXPORTS = [
     "wn_grad_norm_scratch_floats", "wn_grad_norm", "wn_adam_step_guarded",
     "wn_forward_nll", "wn_softmax_nll_rows", "wn_mol_nll_rows", "wn_op_row_sums",
     "wn_adam_step_ema", "wn_adam_step_guarded_ema", "wn_op_swap",
+    "wn_op_accumulate",
 ]
 
 
@@ -196,6 +199,7 @@ class WnLibrary(object):
         L.wn_adam_step_ema.argtypes = [vp, vp, vp, vp, vp, i64, i64, f, f, f, f, f, i64, i64, d, i, vp]
         L.wn_adam_step_guarded_ema.argtypes = [vp, vp, vp, vp, vp, i64, f, f, i64, i64, vp, d, i, vp]
         L.wn_op_swap.argtypes = [vp, vp, i64, vp]
+        L.wn_op_accumulate.argtypes = [vp, vp, i64, i, vp]
         L.wn_op_front.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.wn_op_causal_conv.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.wn_op_causal_conv_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]

@@ -598,6 +598,12 @@ def get_parser():
                              "checkpoint-best.pkl holds (0: off)")
     parser.add_argument("--ema_warmup", default=True, type=strtobool,
                         help="decay min(ema_decay, (1 + t) / (10 + t)) at applied step t, so the average forgets the initial weights")
+    # extension (not a reference flag): gradient accumulation -- A minibatches per optimizer step, their gradients summed on the
+    # device (WaveNet.loss_and_backward(micro_step=)) and exchanged between ranks once
+    parser.add_argument("--accum_steps", default=1, type=int,
+                        help="minibatches per optimizer step (1: off); an iteration is one optimizer step and draws this many "
+                             "minibatches.  The step is the mean over all their loss positions; one-utterance batches (whose "
+                             "lengths the other ranks do not know) are weighted equally, 1 / (ranks * accum_steps)")
     parser.add_argument("--resume", default=None, nargs="?", type=str, help="checkpoint to continue from")
     return parser
 
@@ -751,28 +757,52 @@ def _worker(rank, world, args, port):
     norm_acc = torch.zeros(1, device=device)     # guarded optimizer: sum of the finite pre-clip gradient norms of the interval
     skipped_seen = optimizer.steps_skipped()
     total = 0.0
+    accum_steps = int(getattr(args, "accum_steps", 1) or 1)
+    if accum_steps < 1:
+        logging.error("--accum_steps must be at least 1.")
+        sys.exit(1)
+
+    def shares_of(items):
+        """Per minibatch of one optimizer step: (this rank's share of the step's loss positions, the ``lengths=`` keyword)."""
+        out = []
+        for item in items:
+            batch_x = item[0][0]
+            # A rank's loss is the mean over ITS windows: weighting it (and its gradients) by B_local / batch_size makes the
+            # sum over ranks the mean over the whole minibatch -- what the reference's single CrossEntropyLoss over the
+            # gathered logits computes (train.py:534-536) -- also when batch_size is not a multiple of the rank count.
+            share = batch_x.size(0) / float(args.batch_size) if (world > 1 and args.batch_length is not None) else 1.0 / world
+            ragged, n_global = {}, None
+            if utterance_batch and args.batch_size > 1:
+                # padded whole utterances: the loss is the mean over the valid positions behind the receptive field.  This rank's
+                # share of the minibatch is N_local / N_global loss positions (every rank knows every length: no communication).
+                lengths, all_lengths = item[-2], item[-1]
+                rf = model.receptive_field
+                n_local = int((lengths - rf).clamp_(min=0).sum())
+                n_global = int((all_lengths - rf).clamp_(min=0).sum())
+                ragged["lengths"] = lengths
+                share = n_local / float(max(n_global, 1))
+            out.append([share, ragged, n_global])
+        if len(items) > 1:
+            # --accum_steps: the step's loss is the mean over the loss positions of ALL its micro-batches.  Padded utterance
+            # batches: N_local,i / sum_j N_global,j.  Windows (equal counts) and single utterances (lengths unknown to the other
+            # ranks: weighted equally, as the ranks are): the minibatch's own share / A.
+            n_step = sum(o[2] for o in out) if out[0][2] is not None else None
+            for o in out:
+                o[0] = o[0] * o[2] / float(max(n_step, 1)) if n_step is not None else o[0] / len(items)
+        return out
+
     for i in range(iterations, args.iters):
         start = time.time()
-        item = generator.next()
-        (batch_x, batch_h), batch_t = item[0], item[1]
-        # A rank's loss is the mean over ITS windows: weighting it (and its gradients) by B_local / batch_size makes the
-        # sum over ranks the mean over the whole minibatch -- what the reference's single CrossEntropyLoss over the
-        # gathered logits computes (train.py:534-536) -- also when batch_size is not a multiple of the rank count.
-        share = batch_x.size(0) / float(args.batch_size) if (world > 1 and args.batch_length is not None) else 1.0 / world
-        ragged = {}
-        if utterance_batch and args.batch_size > 1:
-            # padded whole utterances: the loss is the mean over the valid positions behind the receptive field.  This rank's
-            # share of the minibatch is N_local / N_global loss positions (every rank knows every length: no communication).
-            lengths, all_lengths = item[-2], item[-1]
-            rf = model.receptive_field
-            n_local = int((lengths - rf).clamp_(min=0).sum())
-            n_global = int((all_lengths - rf).clamp_(min=0).sum())
-            ragged["lengths"] = lengths
-            share = n_local / float(max(n_global, 1))
-        batch_loss = reducer.loss_and_backward(batch_x, batch_h, batch_t, y=item[2] if args.n_mixture > 0 else None,
-                                               grad_scale=share, **ragged)
-        optimizer.step()
-        loss_acc += batch_loss.detach() * (share * world)
+        items = [generator.next() for _ in range(accum_steps)]   # drawn first, then run as micro-steps (k, A)
+        for k, (item, (share, ragged, _)) in enumerate(zip(items, shares_of(items))):
+            (batch_x, batch_h), batch_t = item[0], item[1]
+            if accum_steps > 1:
+                ragged["micro_step"] = (k, accum_steps)
+            batch_loss = reducer.loss_and_backward(batch_x, batch_h, batch_t, y=item[2] if args.n_mixture > 0 else None,
+                                                   grad_scale=share, **ragged)
+            if k == accum_steps - 1:
+                optimizer.step()
+            loss_acc += batch_loss.detach() * (share * world)
         if optimizer.guarded:   # device-side accumulation, read at the interval's synchronisation below
             norm_acc += torch.nan_to_num(optimizer.grad_norm, nan=0.0, posinf=0.0)
         if args.verbose > 1:

@@ -150,3 +150,16 @@ extern "C" int wn_op_swap(float* a, float* b, int64_t n, void* stream) {
     WN_TRY(wn_swap(a, b, (long)n, (wn_stream_t)stream));
     return rt_check("wn_op_swap");
 }
+
+// Gradient accumulation over micro-batches: WN_ACCUM_SET acc = grad, WN_ACCUM_ADD acc = acc + grad, WN_ACCUM_FINISH
+// grad = acc + grad (WaveNet.loss_and_backward(micro_step=(i, A)); a pointer and a length, so a gradient bucket is a call).
+extern "C" int wn_op_accumulate(float* acc, float* grad, int64_t n, int mode, void* stream) {
+    api_enter();
+    if (!acc || !grad || n <= 0) return fail(1, "bad wn_op_accumulate argument");
+    if (mode != WN_ACCUM_SET && mode != WN_ACCUM_ADD && mode != WN_ACCUM_FINISH)
+        return fail(1, "wn_op_accumulate: mode %d is none of WN_ACCUM_SET, WN_ACCUM_ADD, WN_ACCUM_FINISH", mode);
+    if ((reinterpret_cast<uintptr_t>(acc) & 3) || (reinterpret_cast<uintptr_t>(grad) & 3)) return fail(1, "wn_op_accumulate: the buffers need 4-byte alignment");
+    if (ranges_overlap(acc, grad, n)) return fail(1, "wn_op_accumulate: the two ranges overlap");
+    WN_TRY(wn_grad_accumulate(acc, grad, (long)n, mode, (wn_stream_t)stream));
+    return rt_check("wn_op_accumulate");
+}

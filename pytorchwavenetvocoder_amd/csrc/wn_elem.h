@@ -88,6 +88,9 @@ int wn_adam_guarded_ema(float* p, const float* g, float* m, float* v, float* e, 
                         long skip_hi, const struct WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st);
 // a[i] <-> b[i], i < n: two non-overlapping fp32 buffers of 4-byte alignment, exchanged in place
 int wn_swap(float* a, float* b, long n, wn_stream_t st);
+// gradient accumulation over micro-batches (include/wavenet_hip.h WN_ACCUM_*, ABI v15): SET acc = grad, ADD acc = acc + grad,
+// FINISH grad = acc + grad; two non-overlapping fp32 buffers of 4-byte alignment, one plain fp32 add per element
+int wn_grad_accumulate(float* acc, float* grad, long n, int mode, wn_stream_t st);
 
 // dst[d_off + i0*d0 + i1*d1 + i2*d2 + l*dl] = src[s_off + i0*s0 + i1*s1 + i2*s2 + l*sl]
 typedef struct WnCopy4 {

@@ -724,6 +724,84 @@ int wn_swap(float* a, float* b, long n, wn_stream_t st) {
     return 0;
 }
 
+// Gradient accumulation over micro-batches (include/wavenet_hip.h, ABI v15): one plain fp32 add per element, nothing else.
+//   WN_ACCUM_SET     acc[i]  = grad[i]             (grad is only read)
+//   WN_ACCUM_ADD     acc[i]  = acc[i] + grad[i]    (grad is only read)
+//   WN_ACCUM_FINISH  grad[i] = acc[i] + grad[i]    (acc is only read)
+// Shaped like k_swap: the pointers are 4-byte aligned only (a bucket range starts at any float offset); when they share their
+// address modulo 16 the body moves 16-byte quads (WN_ACCUM_BATCH of each buffer in flight per thread) behind a scalar head and in
+// front of a scalar tail, otherwise every element goes alone.  acc and grad do not overlap (the entry point refuses that), so
+// every element is read and written by exactly one thread.
+#define WN_ACCUM_MAXBLOCKS 1024
+#define WN_ACCUM_BATCH 2
+template <int MODE>
+static __device__ __forceinline__ void wn_accum_one(float* __restrict__ acc, float* __restrict__ grad, long i) {
+    if (MODE == WN_ACCUM_SET) acc[i] = grad[i];
+    else if (MODE == WN_ACCUM_ADD) acc[i] = acc[i] + grad[i];
+    else grad[i] = acc[i] + grad[i];
+}
+
+template <int MODE>
+__global__ __launch_bounds__(WN_TPB) void k_grad_accumulate(float* __restrict__ acc, float* __restrict__ grad, long n) {
+    const long stride = (long)gridDim.x * WN_TPB;
+    const long tid = (long)blockIdx.x * WN_TPB + threadIdx.x;
+    if ((reinterpret_cast<uintptr_t>(acc) & 15) != (reinterpret_cast<uintptr_t>(grad) & 15)) {
+        for (long i = tid; i < n; i += stride) wn_accum_one<MODE>(acc, grad, i);
+        return;
+    }
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(acc) & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const long n4 = (n - head) >> 2;
+    float4* __restrict__ a4 = reinterpret_cast<float4*>(acc + head);
+    float4* __restrict__ g4 = reinterpret_cast<float4*>(grad + head);
+    for (long j = tid; j < n4; j += WN_ACCUM_BATCH * stride) {
+        float4 x[WN_ACCUM_BATCH], y[WN_ACCUM_BATCH];
+        WN_UNROLL
+        for (int k = 0; k < WN_ACCUM_BATCH; ++k) {
+            const long jk = j + k * stride;
+            if (jk < n4) {
+                y[k] = g4[jk];
+                if (MODE != WN_ACCUM_SET) x[k] = a4[jk];
+            }
+        }
+        WN_UNROLL
+        for (int k = 0; k < WN_ACCUM_BATCH; ++k) {
+            const long jk = j + k * stride;
+            if (jk < n4) {
+                if (MODE != WN_ACCUM_SET) {
+                    y[k].x = x[k].x + y[k].x;
+                    y[k].y = x[k].y + y[k].y;
+                    y[k].z = x[k].z + y[k].z;
+                    y[k].w = x[k].w + y[k].w;
+                }
+                if (MODE == WN_ACCUM_FINISH) g4[jk] = y[k];
+                else a4[jk] = y[k];
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 8) {   // scalar head (threads 0..3) and tail (threads 4..7): at most 3 elements each
+        const long t = threadIdx.x & 3;
+        const long i = threadIdx.x < 4 ? t : head + 4 * n4 + t;
+        const long end = threadIdx.x < 4 ? head : n;
+        if (i < end) wn_accum_one<MODE>(acc, grad, i);
+    }
+}
+
+int wn_grad_accumulate(float* acc, float* grad, long n, int mode, wn_stream_t st) {
+    if (mode != WN_ACCUM_SET && mode != WN_ACCUM_ADD && mode != WN_ACCUM_FINISH) return 1;
+    WN_PROF("grad_accumulate", 0.0, 12.0 * (double)n, st);
+    long nb = ((n + 3) / 4 + WN_TPB - 1) / WN_TPB;
+    nb = nb < 1 ? 1 : (nb > WN_ACCUM_MAXBLOCKS ? WN_ACCUM_MAXBLOCKS : nb);
+    if (mode == WN_ACCUM_SET) {
+        WN_LAUNCH(k_grad_accumulate<WN_ACCUM_SET>, dim3((unsigned)nb), dim3(WN_TPB), 0, st, acc, grad, n);
+    } else if (mode == WN_ACCUM_ADD) {
+        WN_LAUNCH(k_grad_accumulate<WN_ACCUM_ADD>, dim3((unsigned)nb), dim3(WN_TPB), 0, st, acc, grad, n);
+    } else {
+        WN_LAUNCH(k_grad_accumulate<WN_ACCUM_FINISH>, dim3((unsigned)nb), dim3(WN_TPB), 0, st, acc, grad, n);
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WN_TPB) void k_copy4(float* __restrict__ dst, const float* __restrict__ src, WnCopy4 c) {
     const long total = (long)c.nl * c.n0 * c.n1 * c.n2;

@@ -15,6 +15,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from ._lib import ACCUM_FINISH as _ACCUM_FINISH
+
 
 def rccl_footprint_defaults():
     """Call before ``init_process_group("nccl")``.  The fused chain kernels are persistent grids that need a whole CU
@@ -60,6 +62,10 @@ class GradientReducer(object):
             big = 4 * int(self.eng.n_params) > 32 * 1024 * 1024
             self.lpb = min(10, int(self.eng.n_layers)) if big else int(self.eng.n_layers)
         self.ranges = self.eng.bucket_ranges(self.lpb)
+        # what the buckets leave uncovered of [0, n_params) -- nothing, for every layout wn_bucket_range makes; a final micro-step
+        # of an accumulation cycle would finish such a gap on the caller's stream
+        edges = [0] + [v for r in sorted(self.ranges) for v in r] + [int(self.eng.n_params)]
+        self._gaps = [(a, b) for a, b in zip(edges[0::2], edges[1::2]) if a < b]
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         # tests: run the bucket-event / side-stream / all-reduce branch with a single rank too (RCCL then executes, on this GPU)
         self.exchange_alone = bool(exchange_when_alone) and dist.is_initialized()
@@ -86,7 +92,7 @@ class GradientReducer(object):
             return self.model.mol_loss_and_backward(x, h, y, **kw)
         return self.model.loss_and_backward(x, h, t, **kw)
 
-    def loss_and_backward(self, x, h, t, t_start=None, y=None, grad_scale=None, lengths=None):
+    def loss_and_backward(self, x, h, t, t_start=None, y=None, grad_scale=None, lengths=None, micro_step=None):
         """forward + loss + backward with the bucketed all-reduce overlapped; returns the local
         mean loss (device tensor).  ``y`` (B, T) float selects the mixture-of-logistics loss.
         ``grad_scale``: this rank's share of the global minibatch (default 1/world = equal shards; pass
@@ -94,8 +100,17 @@ class GradientReducer(object):
         ``lengths``: this rank's padded shard of sequences of unequal length (``WaveNet.loss_and_backward``).  The local loss
         is then the mean over the rank's own N_local = sum_b max(lengths[b] - t_start, 0) loss positions, so the right share
         is ``grad_scale = N_local / N_global`` (N_global: the same count over every rank's shard): the summed gradient is the
-        gradient of the mean over all N_global positions.  Ranks may run different T."""
+        gradient of the mean over all N_global positions.  Ranks may run different T.
+
+        ``micro_step=(i, A)``: gradient accumulation (``WaveNet.loss_and_backward``).  The all-reduce is linear, so the SUM over
+        the A micro-batches is exchanged once: a non-final micro-step exchanges nothing (same ``layers_per_bucket`` launch
+        structure, no events, no side-stream work; its ``grad_accumulate`` launch covers the whole buffer on the caller's stream);
+        the final one keeps the overlap -- per bucket the side stream waits for the bucket's event, finishes the sum on the
+        bucket's range and all-reduces it.  ``grad_scale`` is then this rank's share of the loss positions of the whole
+        optimizer step, over all ranks and micro-steps (default 1 / (world * A): equal shards, equal micro-batches)."""
         kw = {} if lengths is None else {"lengths": lengths}
+        if self.eng.begin_micro_step(micro_step) is not None:   # (checks the pair against the cycle; None: a plain call, A = 1 included)
+            return self._micro_step(x, h, t, y, t_start, grad_scale, micro_step, kw)
         if self.world == 1 and not self.exchange_alone:   # same launch structure as N > 1 (weight gradients flushed per bucket), no exchange
             return self._step(x, h, t, y, t_start=t_start, layers_per_bucket=self.lpb, **kw)
         gscale = self.grad_scale if grad_scale is None else float(grad_scale)
@@ -108,6 +123,12 @@ class GradientReducer(object):
         handles = [e.cuda_event for e in self.events]
         loss = self._step(x, h, t, y, t_start=t_start, grad_scale=gscale, events=handles,
                           layers_per_bucket=self.lpb, **kw)
+        self._exchange()
+        return loss
+
+    def _exchange(self, finish=False):
+        """The side-stream half of a step whose backward recorded the bucket events: per bucket wait for its event, (``finish``:
+        add the accumulator into the bucket's range,) all-reduce the range; then the caller's stream joins."""
         flat = self.eng.grads()
         main = torch.cuda.current_stream(self.eng.device)
         pair = None
@@ -117,11 +138,35 @@ class GradientReducer(object):
         with torch.cuda.stream(self.side):
             for (lo, hi), ev in zip(self.ranges, self.events):
                 self.side.wait_event(ev)
+                if finish:
+                    self.eng.accumulate_grads(_ACCUM_FINISH, lo, hi)
                 dist.all_reduce(flat[lo:hi], group=self.group)
         main.wait_stream(self.side)
+        if finish:
+            for lo, hi in self._gaps:   # (empty for every layout wn_bucket_range makes: the buckets tile the buffer)
+                self.eng.accumulate_grads(_ACCUM_FINISH, lo, hi)
         if pair is not None:
             pair[1].record(main)     # the caller's stream has joined the exchange
             self._exposed.append(pair)
+
+    def _micro_step(self, x, h, t, y, t_start, grad_scale, micro_step, kw):
+        i, A = int(micro_step[0]), int(micro_step[1])
+        gscale = 1.0 / (self.world * A) if grad_scale is None else float(grad_scale)
+        alone = self.world == 1 and not self.exchange_alone
+        if i != A - 1 or alone or not self.cuda:
+            # whole-buffer accumulate launch behind the backward on the caller's stream (FINISH on the last micro-step), then,
+            # on the last micro-step of the gloo path, the all-reduces of the sum
+            lpb = {} if (not self.cuda and not alone) else {"layers_per_bucket": self.lpb}
+            loss = self._step(x, h, t, y, t_start=t_start, grad_scale=gscale, micro_step=micro_step, **lpb, **kw)
+            if i == A - 1 and not alone:
+                flat = self.eng.grads()
+                for lo, hi in self.ranges:
+                    dist.all_reduce(flat[lo:hi], group=self.group)
+            return loss
+        handles = [e.cuda_event for e in self.events]
+        loss = self._step(x, h, t, y, t_start=t_start, grad_scale=gscale, events=handles, layers_per_bucket=self.lpb,
+                          micro_step=micro_step, _accumulate=False, **kw)
+        self._exchange(finish=True)
         return loss
 
     def comm_report(self):

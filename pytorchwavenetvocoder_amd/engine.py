@@ -85,6 +85,8 @@ class WaveNetEngine(object):
         self.receptive_field = self.lib.wn_receptive_field(ctypes.byref(self.cfg))
         self.flat_params = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         self.flat_grads = None
+        self.grad_accum = None    # the sum over the micro-batches of an accumulation cycle (layout of grads()); allocated by the first cycle
+        self._accum = None        # an open cycle: (micro-steps done, A)
         self._ws = None
         self._ws_key = None
         self._eval_ws = None      # forward_nll's own workspace slot: scoring never evicts or rewrites the training one
@@ -131,6 +133,7 @@ class WaveNetEngine(object):
         if device != self.device:
             self.flat_params = self.flat_params.to(device)
             self.flat_grads = None if self.flat_grads is None else self.flat_grads.to(device)
+            self.release_accumulation()
             self._ws = None
             self._ws_key = None
             self.release_eval_workspace()
@@ -206,6 +209,78 @@ class WaveNetEngine(object):
         if self.flat_grads is None:
             self.flat_grads = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         return self.flat_grads
+
+    # ---- gradient accumulation over micro-batches (include/wavenet_hip.h, ABI v15) -----------------
+    @property
+    def accumulation(self):
+        """None, or ``(micro-steps done, A)`` of the open cycle."""
+        return self._accum
+
+    def abandon_accumulation(self):
+        """Forget an open cycle (after an error, or to drop the micro-batches seen so far).  The accumulator stays allocated; the
+        next cycle's first micro-step overwrites it, so nothing of the abandoned one leaks."""
+        self._accum = None
+
+    def release_accumulation(self):
+        """``abandon_accumulation`` and drop the accumulator itself (a move to another device, a re-built flat buffer)."""
+        self._accum = None
+        self.grad_accum = None
+
+    def accumulate_grads(self, mode, lo=0, hi=None):
+        """One ``grad_accumulate`` launch on the current stream over ``[lo, hi)`` of the two flat buffers (default: all of them):
+        ``_lib.ACCUM_SET`` accumulator = gradient, ``ACCUM_ADD`` accumulator += gradient, ``ACCUM_FINISH`` gradient = accumulator +
+        gradient.  The thin call: it knows nothing of cycles (``begin_micro_step`` / ``end_micro_step`` keep that state)."""
+        hi = self.n_params if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= self.n_params:
+            raise ValueError("accumulate_grads: [%d, %d) is not a range of the %d parameters" % (lo, hi, self.n_params))
+        g = self.grads()
+        if self.grad_accum is None:
+            self.grad_accum = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
+        rc = self.lib.wn_op_accumulate(ctypes.c_void_p(self.grad_accum.data_ptr() + 4 * lo), ctypes.c_void_p(g.data_ptr() + 4 * lo),
+                                       hi - lo, int(mode), _stream_handle(self.device))
+        self.lib.check(rc, "wn_op_accumulate")
+
+    def begin_micro_step(self, micro_step):
+        """Check ``micro_step`` against the state of the cycle.  Returns None for a plain call (``None`` or ``A == 1``) and the
+        mode of this micro-step's ``accumulate_grads`` otherwise; changes nothing (``end_micro_step`` does, once the launches are
+        issued, so a call that raises half-way leaves the cycle where it was)."""
+        if micro_step is not None:
+            try:
+                i, A = micro_step
+                ok = int(i) == i and int(A) == A and not isinstance(i, bool) and not isinstance(A, bool)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok or not 0 <= int(i) < int(A):
+                raise ValueError("micro_step must be (i, A) with integers 0 <= i < A, got %r" % (micro_step,))
+            i, A = int(i), int(A)
+        if micro_step is None or A == 1:
+            if self._accum is not None:
+                raise RuntimeError("an accumulation cycle is open (%d of %d micro-steps done): pass micro_step=(%d, %d), or call "
+                                   "engine.abandon_accumulation() to drop it" % (self._accum + self._accum))
+            return None
+        if self._accum is None:
+            if i != 0:
+                raise RuntimeError("micro_step=(%d, %d) but no accumulation cycle is open: a cycle starts with micro_step=(0, %d)"
+                                   % (i, A, A))
+            return _lib.ACCUM_SET
+        done, A0 = self._accum
+        if A != A0:
+            raise RuntimeError("micro_step=(%d, %d) inside a cycle of %d micro-steps (%d done): A must not change inside a cycle -- "
+                               "finish it with micro_step=(%d, %d) ..., or call engine.abandon_accumulation()"
+                               % (i, A, A0, done, done, A0))
+        if i == 0:
+            raise RuntimeError("micro_step=(0, %d) while a cycle is open (%d of %d micro-steps done): finish it, or call "
+                               "engine.abandon_accumulation() to start over" % (A, done, A0))
+        if i != done:
+            raise RuntimeError("micro_step=(%d, %d) is not the next micro-step: the cycle expects micro_step=(%d, %d) (call "
+                               "engine.abandon_accumulation() to drop it)" % (i, A, done, A0))
+        return _lib.ACCUM_FINISH if i == A - 1 else _lib.ACCUM_ADD
+
+    def end_micro_step(self, micro_step):
+        """Advance the cycle after the launches of ``micro_step`` (one ``begin_micro_step`` accepted) have been issued."""
+        i, A = int(micro_step[0]), int(micro_step[1])
+        self._accum = None if i == A - 1 else (i + 1, A)
 
     # ---- C-ABI calls ------------------------------------------------------------------------
     def forward(self, x, h):

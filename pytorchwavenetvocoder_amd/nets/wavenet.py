@@ -366,6 +366,7 @@ class WaveNet(nn.Module):
         eng.device = device
         eng.flat_params = flat
         eng.flat_grads = None
+        eng.release_accumulation()
         eng._ws = None
         eng._ws_key = None
         eng.release_eval_workspace()
@@ -399,7 +400,7 @@ class WaveNet(nn.Module):
         return _WaveNetFunction.apply(self, x, h, *params)
 
     def loss_and_backward(self, x, h, t, t_start=None, grad_scale=1.0, events=None, layers_per_bucket=0, aux_grad=False,
-                          lengths=None):
+                          lengths=None, micro_step=None, _accumulate=True):
         """Fused training half-step: forward -> CrossEntropy on ``[:, t_start:]`` -> backward
         (reference train.py:533-538) without an autograd graph.
 
@@ -413,8 +414,21 @@ class WaveNet(nn.Module):
         sequence, i.e. ``nn.CrossEntropyLoss()`` with the targets behind each end set to -100; x, h and t may hold anything
         finite on the padding.  Only the loss knows the lengths: the network is causal, so the padding reaches no valid
         position, its ``dlogits`` is exactly zero and so is ``dh`` on every frame wholly behind a sequence's end.  The
-        residual stack still computes the whole (B, T) rectangle.  None: every sequence runs to T."""
+        residual stack still computes the whole (B, T) rectangle.  None: every sequence runs to T.
+
+        ``micro_step=(i, A)``, ``0 <= i < A``: gradient accumulation -- this call is micro-batch i of A whose gradients are
+        summed in front of ONE ``optimizer.step()``.  One ``grad_accumulate`` launch follows the backward launches on the
+        caller's stream (nothing synchronises): i = 0 opens a cycle and sets the engine's accumulator (``engine.grad_accum``,
+        allocated by the first cycle) to this gradient, 0 < i < A - 1 adds to it, i = A - 1 adds the accumulator INTO the gradient
+        buffer and closes the cycle.  So after a non-final micro-step ``p.grad`` (the flat buffer) holds that micro-batch's own
+        gradient, after the final one the sum ((g0 + g1) + g2) + ... in plain fp32 -- the bits torch's ``p.grad += g`` gives.
+        ``grad_scale`` keeps its meaning, it multiplies this micro-batch's gradient: ``grad_scale_i = N_i / sum_j N_j`` (N: loss
+        positions) makes the sum the gradient of the mean over all loss positions of the cycle.  The micro-batches may differ in
+        B, T, ``lengths`` and ``aux_grad`` (``dh`` belongs to its micro-batch and is never accumulated).  ``None`` or A = 1:
+        the plain call, no launch, no accumulator.  Out of order, a changed A, a plain call or ``optimizer.step()`` inside a
+        cycle raise; ``engine.abandon_accumulation()`` drops a cycle."""
         eng = self._engine
+        mode = eng.begin_micro_step(micro_step)
         if t_start is None:
             t_start = eng.receptive_field
         # forward + loss in one call: the cross-entropy is the epilogue of conv_post_2 where the model allows it (the logits
@@ -424,19 +438,30 @@ class WaveNet(nn.Module):
         self._fwd_serial += 1
         dh = self._aux_grad_buffer(h) if aux_grad else None
         flat = eng.backward(dlogits, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh)
+        self._finish_micro_step(micro_step, mode, _accumulate)
         for p, (off, n, shape, dead) in zip(self.parameters(), self._param_slices):
             p.grad = None if dead else flat[off:off + n].view(shape)
         return (loss, dh) if aux_grad else loss
+
+    def _finish_micro_step(self, micro_step, mode, accumulate):
+        """The ``grad_accumulate`` launch of a micro-step behind its backward launches, and the cycle's next state.
+        ``accumulate=False`` (GradientReducer on the final micro-step): the caller issues the launch itself, bucket by bucket."""
+        if mode is None:
+            return
+        if accumulate:
+            self._engine.accumulate_grads(mode)
+        self._engine.end_micro_step(micro_step)
 
     def _aux_grad_buffer(self, h):
         return torch.empty(h.shape, dtype=torch.float32, device=self._engine.device)
 
     def mol_loss_and_backward(self, x, h, y, t_start=None, grad_scale=1.0, num_classes=65536, log_scale_min=None,
-                              events=None, layers_per_bucket=0, aux_grad=False, lengths=None):
+                              events=None, layers_per_bucket=0, aux_grad=False, lengths=None, micro_step=None, _accumulate=True):
         """Training half-step of the mixture-of-logistics head (``n_mixture > 0``): forward -> mean negative
         log-likelihood of the waveform ``y`` (B, T) in [-1, 1] (the value of the NEXT sample at every position,
         like ``t`` of the softmax head) on ``[:, t_start:]`` -> backward.  Gradients land as in
-        ``loss_and_backward``; ``aux_grad=True`` returns ``(loss, dh)`` and ``lengths`` masks the padding as there."""
+        ``loss_and_backward``; ``aux_grad=True`` returns ``(loss, dh)``, ``lengths`` masks the padding and ``micro_step=(i, A)``
+        accumulates the gradient over micro-batches as there."""
         if self.n_mixture <= 0:
             raise ValueError("this model has the softmax head (n_mixture = 0)")
         # ONE clamp for the likelihood and for sampling: the constructor's value (it travels in model.conf; a per-call
@@ -447,6 +472,7 @@ class WaveNet(nn.Module):
                              % (float(log_scale_min), self.log_scale_min))
         log_scale_min = self.log_scale_min
         eng = self._engine
+        mode = eng.begin_micro_step(micro_step)
         out = eng.forward(x, h)
         self._fwd_serial += 1
         if t_start is None:
@@ -456,6 +482,7 @@ class WaveNet(nn.Module):
                                   log_scale_min=log_scale_min, **ragged)
         dh = self._aux_grad_buffer(h) if aux_grad else None
         flat = eng.backward(dout, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh)
+        self._finish_micro_step(micro_step, mode, _accumulate)
         for p, (off, n, shape, dead) in zip(self.parameters(), self._param_slices):
             p.grad = None if dead else flat[off:off + n].view(shape)
         return (loss, dh) if aux_grad else loss

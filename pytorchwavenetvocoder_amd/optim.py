@@ -26,6 +26,10 @@ Opt-in, both free of host synchronisation:
                         runs its body on the averaged weights.  Ranks of a data-parallel run hold identical weights and
                         gradients, hence identical averages, without communication.
 
+Gradient accumulation (``loss_and_backward(micro_step=(i, A))``) needs nothing here: the final micro-step leaves
+the sum in the gradient buffer this optimizer reads, so the norm, the guard and the average see the accumulated (and reduced)
+gradient and count optimizer steps.  ``step()`` inside an open cycle raises RuntimeError.
+
 With all three at their defaults ``step()`` is the one ``adam`` launch with the host's step count, bit for bit as before.
 ``state_dict()`` never holds the average: it stays in torch.optim.Adam's format.
 """
@@ -167,6 +171,10 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         if self._ema_swapped:
             raise RuntimeError("step() inside ema_weights(): the model holds the averaged weights")
+        if self.model.engine.accumulation is not None:
+            raise RuntimeError("step() inside an accumulation cycle (%d of %d micro-steps done): the gradient buffer holds one "
+                               "micro-batch, not the sum -- run the remaining micro-steps first, or call "
+                               "model.engine.abandon_accumulation()" % self.model.engine.accumulation)
         loss = None
         if closure is not None:
             with torch.enable_grad():
