@@ -2,7 +2,7 @@
 //
 // Host-side orchestration only: parameter layout, workspace carving and the launch sequence of
 // the forward / loss / backward / Adam steps of the WaveNet training path.  All arithmetic is in
-// the HIP kernels of wn_gemm.hip, wn_elem.hip and wn_fused.hip.
+// the HIP kernels of wn_gemm.hip, wn_elem.hip, wn_fused.hip (the optimizer side: wn_optim.inl, a part of wn_elem.hip).
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,6 +15,7 @@
 #include "wn_fused.h"
 #include "wn_gemm.h"
 #include "wn_gemm6.h"
+#include "wn_optim.h"
 #include "wn_prof.h"
 
 // ------------------------------------------------------------------------------------------

@@ -482,15 +482,30 @@ extern "C" int wn_backward_dh(const WnConfig* cfg, int B, int T, const float* pa
 }
 
 // ------------------------------------------------------------------------------------------
+// What the four Adam entry points ask of the buffers they share (each tests its own step count or state block beside it).
+static bool adam_buffers_ok(const float* params, const float* grads, const float* exp_avg, const float* exp_avg_sq, int64_t n) {
+    return params && grads && exp_avg && exp_avg_sq && n > 0;
+}
+
+// The bias correction of the host-stepped entry points: lr / bc1 and sqrt(bc2) in double, each rounded to float once
+// (k_grad_norm_finalize forms the same two from the device's own count of applied steps).
+struct AdamBias {
+    float lr_over_bc1, sqrt_bc2;
+};
+static AdamBias adam_bias(float lr, float beta1, float beta2, int64_t step) {
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    return {(float)((double)lr / bc1), (float)sqrt(bc2)};
+}
+
 extern "C" int wn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step,
                             float lr, float beta1, float beta2, float eps, float weight_decay, int64_t skip_lo,
                             int64_t skip_hi, void* stream) {
     api_enter();
-    if (!params || !grads || !exp_avg || !exp_avg_sq || n <= 0 || step < 1) return fail(1, "bad wn_adam_step argument");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    WN_TRY(wn_adam(params, grads, exp_avg, exp_avg_sq, (long)n, (float)((double)lr / bc1), (float)sqrt(bc2), beta1, beta2, eps,
-                   weight_decay, (long)skip_lo, (long)skip_hi, (wn_stream_t)stream));
+    if (!adam_buffers_ok(params, grads, exp_avg, exp_avg_sq, n) || step < 1) return fail(1, "bad wn_adam_step argument");
+    const AdamBias b = adam_bias(lr, beta1, beta2, step);
+    WN_TRY(wn_adam(params, grads, exp_avg, exp_avg_sq, (long)n, b.lr_over_bc1, b.sqrt_bc2, beta1, beta2, eps, weight_decay,
+                   (long)skip_lo, (long)skip_hi, (wn_stream_t)stream));
     return rt_check("wn_adam_step");
 }
 
@@ -518,7 +533,7 @@ extern "C" int wn_grad_norm(const float* grads, int64_t n, int64_t skip_lo, int6
 extern "C" int wn_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float eps,
                                     float weight_decay, int64_t skip_lo, int64_t skip_hi, const WnOptState* state, void* stream) {
     api_enter();
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || n <= 0) return fail(1, "bad wn_adam_step_guarded argument");
+    if (!adam_buffers_ok(params, grads, exp_avg, exp_avg_sq, n) || !state) return fail(1, "bad wn_adam_step_guarded argument");
     WN_TRY(wn_adam_guarded(params, grads, exp_avg, exp_avg_sq, (long)n, eps, weight_decay, (long)skip_lo, (long)skip_hi, state,
                            (wn_stream_t)stream));
     return rt_check("wn_adam_step_guarded");
@@ -542,13 +557,11 @@ extern "C" int wn_adam_step_ema(float* params, const float* grads, float* exp_av
                                 int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t skip_lo,
                                 int64_t skip_hi, double ema_decay, int ema_warmup, void* stream) {
     api_enter();
-    if (!params || !grads || !exp_avg || !exp_avg_sq || n <= 0 || step < 1) return fail(1, "bad wn_adam_step_ema argument");
+    if (!adam_buffers_ok(params, grads, exp_avg, exp_avg_sq, n) || step < 1) return fail(1, "bad wn_adam_step_ema argument");
     if (const char* why = ema_argument_error(params, ema, n, ema_decay)) return fail(1, "wn_adam_step_ema: %s", why);
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    WN_TRY(wn_adam_ema(params, grads, exp_avg, exp_avg_sq, ema, (long)n, (float)((double)lr / bc1), (float)sqrt(bc2), beta1, beta2,
-                       eps, weight_decay, (long)skip_lo, (long)skip_hi, wn_ema_weight(ema_decay, ema_warmup, step),
-                       (wn_stream_t)stream));
+    const AdamBias b = adam_bias(lr, beta1, beta2, step);
+    WN_TRY(wn_adam_ema(params, grads, exp_avg, exp_avg_sq, ema, (long)n, b.lr_over_bc1, b.sqrt_bc2, beta1, beta2, eps, weight_decay,
+                       (long)skip_lo, (long)skip_hi, wn_ema_weight(ema_decay, ema_warmup, step), (wn_stream_t)stream));
     return rt_check("wn_adam_step_ema");
 }
 
@@ -556,7 +569,7 @@ extern "C" int wn_adam_step_guarded_ema(float* params, const float* grads, float
                                         float eps, float weight_decay, int64_t skip_lo, int64_t skip_hi, const WnOptState* state,
                                         double ema_decay, int ema_warmup, void* stream) {
     api_enter();
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || n <= 0) return fail(1, "bad wn_adam_step_guarded_ema argument");
+    if (!adam_buffers_ok(params, grads, exp_avg, exp_avg_sq, n) || !state) return fail(1, "bad wn_adam_step_guarded_ema argument");
     if (const char* why = ema_argument_error(params, ema, n, ema_decay)) return fail(1, "wn_adam_step_guarded_ema: %s", why);
     WN_TRY(wn_adam_guarded_ema(params, grads, exp_avg, exp_avg_sq, ema, (long)n, eps, weight_decay, (long)skip_lo, (long)skip_hi,
                                state, ema_decay, ema_warmup, (wn_stream_t)stream));

@@ -483,3 +483,8 @@ static __device__ __forceinline__ float wave_reduce_max(float v) {
     for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
     return v;
 }
+static __device__ __forceinline__ double wn_wave_sum_f64(double v) {
+    WN_UNROLL
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}

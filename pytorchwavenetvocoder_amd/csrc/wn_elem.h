@@ -51,47 +51,6 @@ int wn_softmax_ce_nblocks(int B, int T);
 // many batches accumulates there and the host reads it once.  One workgroup.
 int wn_row_sums(const float* partial, int B, int nblk, float* row_out, double* acc, int acc_as_returned, wn_stream_t st);
 
-// Adam over a flat fp32 buffer (torch.optim.Adam semantics, train.py:457-460): elements in
-// [skip_lo, skip_hi) are left untouched (parameters that never receive a gradient).
-int wn_adam(float* p, const float* g, float* m, float* v, long n, float lr_over_bc1, float inv_sqrt_bc2,
-            float beta1, float beta2, float eps, float weight_decay, long skip_lo, long skip_hi, wn_stream_t st);
-
-// Global gradient norm for clipping / the non-finite-step guard (struct WnOptState: include/wavenet_hip.h).
-//   wn_grad_sumsq:         partial[b] = sum of g[i]^2 in double over block b's share of [0, n) minus [skip_lo, skip_hi);
-//                          wn_grad_sumsq_blocks(n) partials, a function of n alone (never of the device)
-//   wn_grad_norm_finalize: the partials in a fixed order -> norm, clip coefficient, apply flag, step counters and this step's
-//                          lr / bc1, sqrt(bc2) in the state block
-//   wn_adam_guarded:       wn_adam with those scalars read from the state block; writes nothing when the step does not apply
-struct WnOptState;
-int wn_grad_sumsq_blocks(long n);
-int wn_grad_sumsq(const float* g, long n, long skip_lo, long skip_hi, double* partial, wn_stream_t st);
-int wn_grad_norm_finalize(const double* partial, int nb, float max_norm, int guard, float lr, float beta1, float beta2,
-                          struct WnOptState* state, wn_stream_t st);
-int wn_adam_guarded(float* p, const float* g, float* m, float* v, long n, float eps, float weight_decay, long skip_lo, long skip_hi,
-                    const struct WnOptState* state, wn_stream_t st);
-
-// Exponential moving average of the weights inside the Adam launch (include/wavenet_hip.h, ABI v14): e += w (p_new - e).
-// wn_ema_weight is the ONE place the averaging weight w = (float)(1 - d_t) is formed, in double, for the host (unguarded step: t =
-// the caller's step) and for every thread of the guarded launch (t = the state block's steps_applied): the same t gives the same
-// bits.  d_t = min(decay, (1 + t) / (10 + t)) with the warm-up, else decay; t counts the applied steps from 1.
-static __host__ __device__ __forceinline__ float wn_ema_weight(double decay, int warmup, int64_t t) {
-    double d = decay;
-    if (warmup) {
-        const double dw = (1.0 + (double)t) / (10.0 + (double)t);
-        if (dw < d) d = dw;
-    }
-    return (float)(1.0 - d);
-}
-int wn_adam_ema(float* p, const float* g, float* m, float* v, float* e, long n, float lr_over_bc1, float sqrt_bc2, float beta1,
-                float beta2, float eps, float weight_decay, long skip_lo, long skip_hi, float w, wn_stream_t st);
-int wn_adam_guarded_ema(float* p, const float* g, float* m, float* v, float* e, long n, float eps, float weight_decay, long skip_lo,
-                        long skip_hi, const struct WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st);
-// a[i] <-> b[i], i < n: two non-overlapping fp32 buffers of 4-byte alignment, exchanged in place
-int wn_swap(float* a, float* b, long n, wn_stream_t st);
-// gradient accumulation over micro-batches (include/wavenet_hip.h WN_ACCUM_*, ABI v15): SET acc = grad, ADD acc = acc + grad,
-// FINISH grad = acc + grad; two non-overlapping fp32 buffers of 4-byte alignment, one plain fp32 add per element
-int wn_grad_accumulate(float* acc, float* grad, long n, int mode, wn_stream_t st);
-
 // dst[d_off + i0*d0 + i1*d1 + i2*d2 + l*dl] = src[s_off + i0*s0 + i1*s1 + i2*s2 + l*sl]
 typedef struct WnCopy4 {
     int n0, n1, n2, nl;

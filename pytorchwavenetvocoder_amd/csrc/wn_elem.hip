@@ -5,8 +5,6 @@
 #include "wn_elem.h"
 #include "wn_prof.h"
 
-#include "../../include/wavenet_hip.h"   // struct WnOptState
-
 #define WN_TPB 256
 
 static __device__ __forceinline__ float block_reduce_sum(float v, float* red /*[4]*/) {
@@ -395,410 +393,6 @@ int wn_absmax_rows(const float* p, long rows, long ld, int c0, int ncols, float*
     if (rows < 1 || ncols < 1) return 1;
     WN_LAUNCH(k_absmax_rows, dim3((unsigned)((ncols + 4095) / 4096), (unsigned)(rows < 32768 ? rows : 32768)), dim3(WN_TPB), 0, st, p,
               rows, ld, c0, ncols, partial);
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WN_TPB) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                 float* __restrict__ v, long n, float lr_over_bc1, float sqrt_bc2, float beta1,
-                                                 float beta2, float eps, float wd, long skip_lo, long skip_hi) {
-    const long stride = (long)gridDim.x * WN_TPB;
-    for (long i = (long)blockIdx.x * WN_TPB + threadIdx.x; i < n; i += stride) {
-        if (i >= skip_lo && i < skip_hi) continue;
-        const float pv = p[i];
-        float gv = g[i];
-        if (wd != 0.0f) gv += wd * pv;
-        const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
-        const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
-        m[i] = mv;
-        v[i] = vv;
-        const float denom = sqrtf(vv) / sqrt_bc2 + eps;
-        p[i] = pv - lr_over_bc1 * (mv / denom);
-    }
-}
-
-int wn_adam(float* p, const float* g, float* m, float* v, long n, float lr_over_bc1, float sqrt_bc2, float beta1, float beta2,
-            float eps, float weight_decay, long skip_lo, long skip_hi, wn_stream_t st) {
-    WN_PROF("adam", 0.0, 0.0, st);
-    long nb = (n + WN_TPB - 1) / WN_TPB;
-    if (nb > 2048) nb = 2048;
-    if (nb < 1) nb = 1;
-    WN_LAUNCH(k_adam, dim3((unsigned)nb), dim3(WN_TPB), 0, st, p, g, m, v, n, lr_over_bc1, sqrt_bc2, beta1, beta2, eps,
-              weight_decay, skip_lo, skip_hi);
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Global-norm clipping and the non-finite-step guard (wn_grad_norm / wn_adam_step_guarded).
-// k_grad_sumsq: one double per block = sum of g[i]^2 over the block's share of [0, n) minus [skip_lo, skip_hi).  Every product
-// (double)g * (double)g is exact (48 significand bits) and no sum of n such squares can leave double's range, so the total is
-// non-finite exactly when an element outside the skip range is.  The grid (wn_grad_sumsq_blocks) depends on n alone and every
-// level of the sum -- per thread front to back, the xor butterfly of a wave, the waves of a block in order, the blocks in the
-// finalize launch -- is a fixed order: the same buffer at the same address modulo 16 gives the same bits on every device.
-#define WN_GN_MAXBLOCKS 512
-#define WN_GN_BATCH 4
-int wn_grad_sumsq_blocks(long n) {
-    long nb = ((n + 3) / 4 + WN_TPB - 1) / WN_TPB;
-    return (int)(nb < 1 ? 1 : (nb > WN_GN_MAXBLOCKS ? WN_GN_MAXBLOCKS : nb));
-}
-
-static __device__ __forceinline__ double wn_wave_sum_f64(double v) {
-    WN_UNROLL
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-__global__ __launch_bounds__(WN_TPB) void k_grad_sumsq(const float* __restrict__ g, long n, long skip_lo, long skip_hi,
-                                                       double* __restrict__ partial) {
-    __shared__ double red[WN_TPB >> 6];
-    // a base pointer that is only 4-byte aligned: `head` scalar elements in front of the first 16-byte boundary
-    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) >> 2);
-    if (head > n) head = n;
-    const long n4 = (n - head) >> 2;
-    const float4* q = reinterpret_cast<const float4*>(g + head);
-    const long stride = (long)gridDim.x * WN_TPB;
-    double acc = 0.0;
-    // WN_GN_BATCH quads per thread and trip, their 16-byte loads issued back to back (32 KiB in flight per CU at 8 waves per CU) and
-    // no early exit in the body: a quad beyond the end re-reads quad j and adds zeros, an element inside the skip range adds
-    // zero whatever it holds.  A thread still adds its quads j, j + stride, j + 2 stride, ... front to back.
-    for (long j = (long)blockIdx.x * WN_TPB + threadIdx.x; j < n4; j += WN_GN_BATCH * stride) {
-        float4 v[WN_GN_BATCH];
-        WN_UNROLL
-        for (int k = 0; k < WN_GN_BATCH; ++k) {
-            const long jk = j + k * stride;
-            v[k] = q[jk < n4 ? jk : j];
-        }
-        WN_UNROLL
-        for (int k = 0; k < WN_GN_BATCH; ++k) {
-            const long jk = j + k * stride;
-            const long i0 = head + 4 * jk;
-            const bool in = jk < n4;
-            const double x = (in && (i0 < skip_lo || i0 >= skip_hi)) ? (double)v[k].x : 0.0;
-            const double y = (in && (i0 + 1 < skip_lo || i0 + 1 >= skip_hi)) ? (double)v[k].y : 0.0;
-            const double z = (in && (i0 + 2 < skip_lo || i0 + 2 >= skip_hi)) ? (double)v[k].z : 0.0;
-            const double w = (in && (i0 + 3 < skip_lo || i0 + 3 >= skip_hi)) ? (double)v[k].w : 0.0;
-            acc += x * x;
-            acc += y * y;
-            acc += z * z;
-            acc += w * w;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 8) {   // scalar head (threads 0..3) and tail (threads 4..7): at most 3 elements each
-        const long t = threadIdx.x & 3;
-        const long i = threadIdx.x < 4 ? t : head + 4 * n4 + t;
-        const long end = threadIdx.x < 4 ? head : n;
-        if (i < end && (i < skip_lo || i >= skip_hi)) acc += (double)g[i] * (double)g[i];
-    }
-    acc = wn_wave_sum_f64(acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = red[0];
-        for (int i = 1; i < (WN_TPB >> 6); ++i) s += red[i];
-        partial[blockIdx.x] = s;
-    }
-}
-
-int wn_grad_sumsq(const float* g, long n, long skip_lo, long skip_hi, double* partial, wn_stream_t st) {
-    WN_PROF("grad_sumsq", 2.0 * (double)n, 4.0 * (double)n, st);
-    if (skip_hi <= skip_lo) skip_lo = skip_hi = 0;
-    WN_LAUNCH(k_grad_sumsq, dim3((unsigned)wn_grad_sumsq_blocks(n)), dim3(WN_TPB), 0, st, g, n, skip_lo, skip_hi, partial);
-    return 0;
-}
-
-// One block: the partials in a fixed order, then every scalar the guarded Adam launch reads.  Everything in the state block except
-// the two step counters is written from scratch (nothing depends on what the block held before).
-__global__ __launch_bounds__(WN_TPB) void k_grad_norm_finalize(const double* __restrict__ partial, int nb, float max_norm, int guard,
-                                                               float lr, float beta1, float beta2, WnOptState* __restrict__ state) {
-    __shared__ double red[WN_TPB >> 6];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nb; i += WN_TPB) acc += partial[i];
-    acc = wn_wave_sum_f64(acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    double s = red[0];
-    for (int i = 1; i < (WN_TPB >> 6); ++i) s += red[i];
-    // judged on the double sum (exponent field not all ones): finite elements, +-3e38 included, can never make it inf or NaN
-    const bool finite = ((__builtin_bit_cast(unsigned long long, s) >> 52) & 0x7ffULL) != 0x7ffULL;
-    const double norm = sqrt(s);
-    // torch.nn.utils.clip_grad_norm_ (norm_type 2): min(1, max_norm / (total_norm + 1e-6)); a NaN norm gives a NaN coefficient there
-    // too (the guard is what stops it).  max_norm <= 0 or inf: measure only, the coefficient is exactly 1.
-    double coef = 1.0;
-    if (max_norm > 0.0f && max_norm <= 3.402823466e38f) {
-        coef = (double)max_norm / (norm + 1e-6);
-        if (coef > 1.0) coef = 1.0;
-    }
-    const int apply = (guard && !finite) ? 0 : 1;
-    state->sumsq = s;
-    state->total_norm = (float)norm;
-    state->clip_coef = (float)coef;
-    state->apply = apply;
-    state->reserved = 0;
-    state->beta1 = beta1;
-    state->beta2 = beta2;
-    if (apply) {
-        const int64_t step = state->steps_applied + 1;
-        state->steps_applied = step;
-        // the formulas of wn_adam_step, with the device's own count of applied steps
-        const double bc1 = 1.0 - pow((double)beta1, (double)step);
-        const double bc2 = 1.0 - pow((double)beta2, (double)step);
-        state->lr_over_bc1 = (float)((double)lr / bc1);
-        state->sqrt_bc2 = (float)sqrt(bc2);
-    } else {
-        state->steps_skipped = state->steps_skipped + 1;
-        state->lr_over_bc1 = 0.0f;
-        state->sqrt_bc2 = 0.0f;
-    }
-}
-
-int wn_grad_norm_finalize(const double* partial, int nb, float max_norm, int guard, float lr, float beta1, float beta2,
-                          WnOptState* state, wn_stream_t st) {
-    WN_PROF("grad_norm_finalize", 0.0, 8.0 * (double)nb, st);
-    WN_LAUNCH(k_grad_norm_finalize, dim3(1), dim3(WN_TPB), 0, st, partial, nb, max_norm, guard, lr, beta1, beta2, state);
-    return 0;
-}
-
-// k_adam with its scalars from the state block: the gradient is scaled by clip_coef BEFORE the weight-decay term (torch clips the
-// raw gradient, the optimizer adds L2 decay afterwards), g itself is left as it is, and a step that does not apply writes nothing.
-__global__ __launch_bounds__(WN_TPB) void k_adam_guarded(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, long n, float eps, float wd, long skip_lo,
-                                                         long skip_hi, const WnOptState* __restrict__ state) {
-    if (!state->apply) return;
-    const float lr_over_bc1 = state->lr_over_bc1, sqrt_bc2 = state->sqrt_bc2, coef = state->clip_coef;
-    const float beta1 = state->beta1, beta2 = state->beta2;
-    const long stride = (long)gridDim.x * WN_TPB;
-    for (long i = (long)blockIdx.x * WN_TPB + threadIdx.x; i < n; i += stride) {
-        if (i >= skip_lo && i < skip_hi) continue;
-        const float pv = p[i];
-        float gv = wn_fmul_rn(coef, g[i]);   // never contracted into the decay term's fma: coef == 1 leaves k_adam's arithmetic
-        if (wd != 0.0f) gv += wd * pv;
-        const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
-        const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
-        m[i] = mv;
-        v[i] = vv;
-        const float denom = sqrtf(vv) / sqrt_bc2 + eps;
-        p[i] = pv - lr_over_bc1 * (mv / denom);
-    }
-}
-
-int wn_adam_guarded(float* p, const float* g, float* m, float* v, long n, float eps, float weight_decay, long skip_lo, long skip_hi,
-                    const WnOptState* state, wn_stream_t st) {
-    WN_PROF("adam_guarded", 0.0, 0.0, st);
-    long nb = (n + WN_TPB - 1) / WN_TPB;
-    if (nb > 2048) nb = 2048;
-    if (nb < 1) nb = 1;
-    WN_LAUNCH(k_adam_guarded, dim3((unsigned)nb), dim3(WN_TPB), 0, st, p, g, m, v, n, eps, weight_decay, skip_lo, skip_hi, state);
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Adam with an exponential moving average of the weights (wn_adam_step_ema / wn_adam_step_guarded_ema): the
-// arithmetic of k_adam (GUARDED: of k_adam_guarded) expression for expression -- p, m, v get the bits of the plain launches -- and,
-// with the new weight still in a register, e += w (p_new - e) as ONE fma.  The increment form has e == p_new as its exact fixed
-// point; d e + (1 - d) p_new has not (the two fp32 coefficients of d = 0.9999 do not sum to 1).  k_adam and k_adam_guarded are
-// left as they are: the EMA-off paths keep their code objects.  9 words per element move instead of 7.
-template <bool GUARDED>
-static __device__ __forceinline__ void wn_adam_ema_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, float* __restrict__ e, long n, float lr_over_bc1,
-                                                         float sqrt_bc2, float coef, float beta1, float beta2, float eps, float wd,
-                                                         long skip_lo, long skip_hi, float w) {
-    const long stride = (long)gridDim.x * WN_TPB;
-    for (long i = (long)blockIdx.x * WN_TPB + threadIdx.x; i < n; i += stride) {
-        if (i >= skip_lo && i < skip_hi) continue;
-        const float pv = p[i];
-        const float ev = e[i];
-        float gv = GUARDED ? wn_fmul_rn(coef, g[i]) : g[i];
-        if (wd != 0.0f) gv += wd * pv;
-        const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
-        const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
-        m[i] = mv;
-        v[i] = vv;
-        const float denom = sqrtf(vv) / sqrt_bc2 + eps;
-        const float pn = pv - lr_over_bc1 * (mv / denom);
-        p[i] = pn;
-        e[i] = fmaf(w, pn - ev, ev);
-    }
-}
-
-__global__ __launch_bounds__(WN_TPB) void k_adam_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                     float* __restrict__ v, float* __restrict__ e, long n, float lr_over_bc1,
-                                                     float sqrt_bc2, float beta1, float beta2, float eps, float wd, long skip_lo,
-                                                     long skip_hi, float w) {
-    wn_adam_ema_sweep<false>(p, g, m, v, e, n, lr_over_bc1, sqrt_bc2, 1.0f, beta1, beta2, eps, wd, skip_lo, skip_hi, w);
-}
-
-// the averaging weight from the device's own count of applied steps (this one included: the finalize launch has counted it)
-__global__ __launch_bounds__(WN_TPB) void k_adam_guarded_ema(float* __restrict__ p, const float* __restrict__ g,
-                                                             float* __restrict__ m, float* __restrict__ v, float* __restrict__ e,
-                                                             long n, float eps, float wd, long skip_lo, long skip_hi,
-                                                             const WnOptState* __restrict__ state, double ema_decay,
-                                                             int ema_warmup) {
-    if (!state->apply) return;
-    const float w = wn_ema_weight(ema_decay, ema_warmup, state->steps_applied);
-    wn_adam_ema_sweep<true>(p, g, m, v, e, n, state->lr_over_bc1, state->sqrt_bc2, state->clip_coef, state->beta1, state->beta2,
-                            eps, wd, skip_lo, skip_hi, w);
-}
-
-static unsigned wn_adam_blocks(long n) {
-    long nb = (n + WN_TPB - 1) / WN_TPB;
-    return (unsigned)(nb > 2048 ? 2048 : (nb < 1 ? 1 : nb));
-}
-
-int wn_adam_ema(float* p, const float* g, float* m, float* v, float* e, long n, float lr_over_bc1, float sqrt_bc2, float beta1,
-                float beta2, float eps, float weight_decay, long skip_lo, long skip_hi, float w, wn_stream_t st) {
-    WN_PROF("adam_ema", 0.0, 36.0 * (double)n, st);
-    WN_LAUNCH(k_adam_ema, dim3(wn_adam_blocks(n)), dim3(WN_TPB), 0, st, p, g, m, v, e, n, lr_over_bc1, sqrt_bc2, beta1, beta2, eps,
-              weight_decay, skip_lo, skip_hi, w);
-    return 0;
-}
-
-int wn_adam_guarded_ema(float* p, const float* g, float* m, float* v, float* e, long n, float eps, float weight_decay, long skip_lo,
-                        long skip_hi, const WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st) {
-    WN_PROF("adam_guarded_ema", 0.0, 36.0 * (double)n, st);
-    WN_LAUNCH(k_adam_guarded_ema, dim3(wn_adam_blocks(n)), dim3(WN_TPB), 0, st, p, g, m, v, e, n, eps, weight_decay, skip_lo, skip_hi,
-              state, ema_decay, ema_warmup);
-    return 0;
-}
-
-// a[i] <-> b[i] with no temporary buffer.  The pointers are 4-byte aligned only: when they share their address modulo 16 the body
-// moves 16-byte quads (WN_SWAP_BATCH of each buffer in flight per thread) behind a scalar head and in front of a scalar tail, as in
-// k_grad_sumsq; otherwise every element goes alone.  a and b do not overlap (the entry point refuses that), so every element is
-// read and written by exactly one thread.
-#define WN_SWAP_MAXBLOCKS 512
-#define WN_SWAP_BATCH 2
-__global__ __launch_bounds__(WN_TPB) void k_swap(float* a, float* b, long n) {
-    const long stride = (long)gridDim.x * WN_TPB;
-    const long tid = (long)blockIdx.x * WN_TPB + threadIdx.x;
-    if ((reinterpret_cast<uintptr_t>(a) & 15) != (reinterpret_cast<uintptr_t>(b) & 15)) {
-        for (long i = tid; i < n; i += stride) {
-            const float x = a[i], y = b[i];
-            a[i] = y;
-            b[i] = x;
-        }
-        return;
-    }
-    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(a) & 15)) & 15) >> 2);
-    if (head > n) head = n;
-    const long n4 = (n - head) >> 2;
-    float4* a4 = reinterpret_cast<float4*>(a + head);
-    float4* b4 = reinterpret_cast<float4*>(b + head);
-    for (long j = tid; j < n4; j += WN_SWAP_BATCH * stride) {
-        float4 x[WN_SWAP_BATCH], y[WN_SWAP_BATCH];
-        WN_UNROLL
-        for (int k = 0; k < WN_SWAP_BATCH; ++k) {
-            const long jk = j + k * stride;
-            if (jk < n4) {
-                x[k] = a4[jk];
-                y[k] = b4[jk];
-            }
-        }
-        WN_UNROLL
-        for (int k = 0; k < WN_SWAP_BATCH; ++k) {
-            const long jk = j + k * stride;
-            if (jk < n4) {
-                a4[jk] = y[k];
-                b4[jk] = x[k];
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 8) {   // scalar head (threads 0..3) and tail (threads 4..7): at most 3 elements each
-        const long t = threadIdx.x & 3;
-        const long i = threadIdx.x < 4 ? t : head + 4 * n4 + t;
-        const long end = threadIdx.x < 4 ? head : n;
-        if (i < end) {
-            const float x = a[i], y = b[i];
-            a[i] = y;
-            b[i] = x;
-        }
-    }
-}
-
-int wn_swap(float* a, float* b, long n, wn_stream_t st) {
-    WN_PROF("swap", 0.0, 16.0 * (double)n, st);
-    long nb = ((n + 3) / 4 + WN_TPB - 1) / WN_TPB;
-    nb = nb < 1 ? 1 : (nb > WN_SWAP_MAXBLOCKS ? WN_SWAP_MAXBLOCKS : nb);
-    WN_LAUNCH(k_swap, dim3((unsigned)nb), dim3(WN_TPB), 0, st, a, b, n);
-    return 0;
-}
-
-// Gradient accumulation over micro-batches (include/wavenet_hip.h, ABI v15): one plain fp32 add per element, nothing else.
-//   WN_ACCUM_SET     acc[i]  = grad[i]             (grad is only read)
-//   WN_ACCUM_ADD     acc[i]  = acc[i] + grad[i]    (grad is only read)
-//   WN_ACCUM_FINISH  grad[i] = acc[i] + grad[i]    (acc is only read)
-// Shaped like k_swap: the pointers are 4-byte aligned only (a bucket range starts at any float offset); when they share their
-// address modulo 16 the body moves 16-byte quads (WN_ACCUM_BATCH of each buffer in flight per thread) behind a scalar head and in
-// front of a scalar tail, otherwise every element goes alone.  acc and grad do not overlap (the entry point refuses that), so
-// every element is read and written by exactly one thread.
-#define WN_ACCUM_MAXBLOCKS 1024
-#define WN_ACCUM_BATCH 2
-template <int MODE>
-static __device__ __forceinline__ void wn_accum_one(float* __restrict__ acc, float* __restrict__ grad, long i) {
-    if (MODE == WN_ACCUM_SET) acc[i] = grad[i];
-    else if (MODE == WN_ACCUM_ADD) acc[i] = acc[i] + grad[i];
-    else grad[i] = acc[i] + grad[i];
-}
-
-template <int MODE>
-__global__ __launch_bounds__(WN_TPB) void k_grad_accumulate(float* __restrict__ acc, float* __restrict__ grad, long n) {
-    const long stride = (long)gridDim.x * WN_TPB;
-    const long tid = (long)blockIdx.x * WN_TPB + threadIdx.x;
-    if ((reinterpret_cast<uintptr_t>(acc) & 15) != (reinterpret_cast<uintptr_t>(grad) & 15)) {
-        for (long i = tid; i < n; i += stride) wn_accum_one<MODE>(acc, grad, i);
-        return;
-    }
-    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(acc) & 15)) & 15) >> 2);
-    if (head > n) head = n;
-    const long n4 = (n - head) >> 2;
-    float4* __restrict__ a4 = reinterpret_cast<float4*>(acc + head);
-    float4* __restrict__ g4 = reinterpret_cast<float4*>(grad + head);
-    for (long j = tid; j < n4; j += WN_ACCUM_BATCH * stride) {
-        float4 x[WN_ACCUM_BATCH], y[WN_ACCUM_BATCH];
-        WN_UNROLL
-        for (int k = 0; k < WN_ACCUM_BATCH; ++k) {
-            const long jk = j + k * stride;
-            if (jk < n4) {
-                y[k] = g4[jk];
-                if (MODE != WN_ACCUM_SET) x[k] = a4[jk];
-            }
-        }
-        WN_UNROLL
-        for (int k = 0; k < WN_ACCUM_BATCH; ++k) {
-            const long jk = j + k * stride;
-            if (jk < n4) {
-                if (MODE != WN_ACCUM_SET) {
-                    y[k].x = x[k].x + y[k].x;
-                    y[k].y = x[k].y + y[k].y;
-                    y[k].z = x[k].z + y[k].z;
-                    y[k].w = x[k].w + y[k].w;
-                }
-                if (MODE == WN_ACCUM_FINISH) g4[jk] = y[k];
-                else a4[jk] = y[k];
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 8) {   // scalar head (threads 0..3) and tail (threads 4..7): at most 3 elements each
-        const long t = threadIdx.x & 3;
-        const long i = threadIdx.x < 4 ? t : head + 4 * n4 + t;
-        const long end = threadIdx.x < 4 ? head : n;
-        if (i < end) wn_accum_one<MODE>(acc, grad, i);
-    }
-}
-
-int wn_grad_accumulate(float* acc, float* grad, long n, int mode, wn_stream_t st) {
-    if (mode != WN_ACCUM_SET && mode != WN_ACCUM_ADD && mode != WN_ACCUM_FINISH) return 1;
-    WN_PROF("grad_accumulate", 0.0, 12.0 * (double)n, st);
-    long nb = ((n + 3) / 4 + WN_TPB - 1) / WN_TPB;
-    nb = nb < 1 ? 1 : (nb > WN_ACCUM_MAXBLOCKS ? WN_ACCUM_MAXBLOCKS : nb);
-    if (mode == WN_ACCUM_SET) {
-        WN_LAUNCH(k_grad_accumulate<WN_ACCUM_SET>, dim3((unsigned)nb), dim3(WN_TPB), 0, st, acc, grad, n);
-    } else if (mode == WN_ACCUM_ADD) {
-        WN_LAUNCH(k_grad_accumulate<WN_ACCUM_ADD>, dim3((unsigned)nb), dim3(WN_TPB), 0, st, acc, grad, n);
-    } else {
-        WN_LAUNCH(k_grad_accumulate<WN_ACCUM_FINISH>, dim3((unsigned)nb), dim3(WN_TPB), 0, st, acc, grad, n);
-    }
     return 0;
 }
 
@@ -1993,3 +1587,4 @@ int wn_row_sums(const float* partial, int B, int nblk, float* row_out, double* a
 }
 
 #include "wn_auxdh.inl"
+#include "wn_optim.inl"

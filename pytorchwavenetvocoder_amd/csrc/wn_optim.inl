@@ -1,0 +1,360 @@
+// wn_optim.inl -- the optimizer side of the training step (gfx950): Adam over one flat fp32 buffer, the global gradient norm
+// behind clipping and the non-finite-step guard, the in-place exchange of two buffers and gradient accumulation.  All of it is
+// HBM-bound streaming over flat buffers; nothing here knows the network (struct WnOptState and WN_ACCUM_* are the whole interface).
+// Part of wn_elem.hip (included at its end, like wn_auxdh.inl; WN_TPB is that file's).  Not compiled on its own.
+#include "wn_optim.h"
+
+#include "../../include/wavenet_hip.h"   // struct WnOptState, WN_ACCUM_*
+
+// ---------------------------------------------------------------------------------------------
+// Buffers here are 4-byte aligned only (a view, a bucket range, starts at any float offset).  A kernel that wants 16-byte accesses
+// walks `n4` quads behind `head` scalar elements in front of the first 16-byte boundary; the up to 3 + 3 scalar elements of head
+// and tail go to threads 0..3 and 4..7 of block 0.
+struct WnQuadSplit {
+    long head, n4;
+};
+static __device__ __forceinline__ WnQuadSplit wn_quad_split(const float* p, long n) {
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    return {head, (n - head) >> 2};
+}
+// true for the threads that own a scalar head or tail element, *i = its index
+static __device__ __forceinline__ bool wn_quad_edge(const WnQuadSplit& s, long n, long* i) {
+    if (blockIdx.x != 0 || threadIdx.x >= 8) return false;
+    const long t = threadIdx.x & 3;
+    *i = threadIdx.x < 4 ? t : s.head + 4 * s.n4 + t;
+    return *i < (threadIdx.x < 4 ? s.head : n);
+}
+// one thread per quad, at most `cap` blocks: a function of n alone (never of the device)
+static unsigned wn_quad_blocks(long n, long cap) {
+    const long nb = ((n + 3) / 4 + WN_TPB - 1) / WN_TPB;
+    return (unsigned)(nb < 1 ? 1 : (nb > cap ? cap : nb));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adam (torch.optim.Adam semantics) in its four variants, the update written ONCE:
+//   GUARDED  the scalars come from the state block wn_grad_norm_finalize left; the gradient is scaled by clip_coef
+//            BEFORE the weight-decay term (torch clips the raw gradient, the optimizer adds L2 decay afterwards), g itself is left
+//            as it is, and a step that does not apply writes nothing (the kernels return before the sweep)
+//   EMA      with the new weight still in a register, e += w (p_new - e) as ONE fma.  The increment form has
+//            e == p_new as its exact fixed point; d e + (1 - d) p_new has not (the two fp32 coefficients of d = 0.9999 do not sum
+//            to 1).  9 words per element move instead of 7.
+// Both are compile-time: a plain kernel carries no multiply by a coefficient and no access to e.  p, m and v get the same bits
+// from all four kernels because there is one expression for them, which no flag changes: GUARDED only puts a separately rounded
+// product in place of g[i], and the EMA only reads pn.
+template <bool GUARDED, bool EMA>
+static __device__ __forceinline__ void wn_adam_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                     float* __restrict__ v, float* __restrict__ e, long n, float lr_over_bc1,
+                                                     float sqrt_bc2, float coef, float beta1, float beta2, float eps, float wd,
+                                                     long skip_lo, long skip_hi, float w) {
+    const long stride = (long)gridDim.x * WN_TPB;
+    for (long i = (long)blockIdx.x * WN_TPB + threadIdx.x; i < n; i += stride) {
+        if (i >= skip_lo && i < skip_hi) continue;
+        const float pv = p[i];
+        float ev = 0.0f;
+        if (EMA) ev = e[i];
+        // never contracted into the decay term's fma: coef == 1 leaves the unguarded arithmetic
+        float gv = GUARDED ? wn_fmul_rn(coef, g[i]) : g[i];
+        if (wd != 0.0f) gv += wd * pv;
+        const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
+        const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
+        m[i] = mv;
+        v[i] = vv;
+        const float denom = sqrtf(vv) / sqrt_bc2 + eps;
+        const float pn = pv - lr_over_bc1 * (mv / denom);
+        p[i] = pn;
+        if (EMA) e[i] = fmaf(w, pn - ev, ev);
+    }
+}
+
+__global__ __launch_bounds__(WN_TPB) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, long n, float lr_over_bc1, float sqrt_bc2, float beta1,
+                                                 float beta2, float eps, float wd, long skip_lo, long skip_hi) {
+    wn_adam_sweep<false, false>(p, g, m, v, nullptr, n, lr_over_bc1, sqrt_bc2, 1.0f, beta1, beta2, eps, wd, skip_lo, skip_hi, 0.0f);
+}
+
+__global__ __launch_bounds__(WN_TPB) void k_adam_guarded(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, long n, float eps, float wd, long skip_lo,
+                                                         long skip_hi, const WnOptState* __restrict__ state) {
+    if (!state->apply) return;
+    wn_adam_sweep<true, false>(p, g, m, v, nullptr, n, state->lr_over_bc1, state->sqrt_bc2, state->clip_coef, state->beta1,
+                               state->beta2, eps, wd, skip_lo, skip_hi, 0.0f);
+}
+
+__global__ __launch_bounds__(WN_TPB) void k_adam_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                     float* __restrict__ v, float* __restrict__ e, long n, float lr_over_bc1,
+                                                     float sqrt_bc2, float beta1, float beta2, float eps, float wd, long skip_lo,
+                                                     long skip_hi, float w) {
+    wn_adam_sweep<false, true>(p, g, m, v, e, n, lr_over_bc1, sqrt_bc2, 1.0f, beta1, beta2, eps, wd, skip_lo, skip_hi, w);
+}
+
+// the averaging weight from the device's own count of applied steps (this one included: the finalize launch has counted it)
+__global__ __launch_bounds__(WN_TPB) void k_adam_guarded_ema(float* __restrict__ p, const float* __restrict__ g,
+                                                             float* __restrict__ m, float* __restrict__ v, float* __restrict__ e,
+                                                             long n, float eps, float wd, long skip_lo, long skip_hi,
+                                                             const WnOptState* __restrict__ state, double ema_decay,
+                                                             int ema_warmup) {
+    if (!state->apply) return;
+    const float w = wn_ema_weight(ema_decay, ema_warmup, state->steps_applied);
+    wn_adam_sweep<true, true>(p, g, m, v, e, n, state->lr_over_bc1, state->sqrt_bc2, state->clip_coef, state->beta1, state->beta2,
+                              eps, wd, skip_lo, skip_hi, w);
+}
+
+static unsigned wn_adam_blocks(long n) {
+    long nb = (n + WN_TPB - 1) / WN_TPB;
+    return (unsigned)(nb > 2048 ? 2048 : (nb < 1 ? 1 : nb));
+}
+
+int wn_adam(float* p, const float* g, float* m, float* v, long n, float lr_over_bc1, float sqrt_bc2, float beta1, float beta2,
+            float eps, float weight_decay, long skip_lo, long skip_hi, wn_stream_t st) {
+    WN_PROF("adam", 0.0, 0.0, st);
+    WN_LAUNCH(k_adam, dim3(wn_adam_blocks(n)), dim3(WN_TPB), 0, st, p, g, m, v, n, lr_over_bc1, sqrt_bc2, beta1, beta2, eps,
+              weight_decay, skip_lo, skip_hi);
+    return 0;
+}
+
+int wn_adam_guarded(float* p, const float* g, float* m, float* v, long n, float eps, float weight_decay, long skip_lo, long skip_hi,
+                    const WnOptState* state, wn_stream_t st) {
+    WN_PROF("adam_guarded", 0.0, 0.0, st);
+    WN_LAUNCH(k_adam_guarded, dim3(wn_adam_blocks(n)), dim3(WN_TPB), 0, st, p, g, m, v, n, eps, weight_decay, skip_lo, skip_hi,
+              state);
+    return 0;
+}
+
+int wn_adam_ema(float* p, const float* g, float* m, float* v, float* e, long n, float lr_over_bc1, float sqrt_bc2, float beta1,
+                float beta2, float eps, float weight_decay, long skip_lo, long skip_hi, float w, wn_stream_t st) {
+    WN_PROF("adam_ema", 0.0, 36.0 * (double)n, st);
+    WN_LAUNCH(k_adam_ema, dim3(wn_adam_blocks(n)), dim3(WN_TPB), 0, st, p, g, m, v, e, n, lr_over_bc1, sqrt_bc2, beta1, beta2, eps,
+              weight_decay, skip_lo, skip_hi, w);
+    return 0;
+}
+
+int wn_adam_guarded_ema(float* p, const float* g, float* m, float* v, float* e, long n, float eps, float weight_decay, long skip_lo,
+                        long skip_hi, const WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st) {
+    WN_PROF("adam_guarded_ema", 0.0, 36.0 * (double)n, st);
+    WN_LAUNCH(k_adam_guarded_ema, dim3(wn_adam_blocks(n)), dim3(WN_TPB), 0, st, p, g, m, v, e, n, eps, weight_decay, skip_lo, skip_hi,
+              state, ema_decay, ema_warmup);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Global-norm clipping and the non-finite-step guard (wn_grad_norm / wn_adam_step_guarded).
+// k_grad_sumsq: one double per block = sum of g[i]^2 over the block's share of [0, n) minus [skip_lo, skip_hi).  Every product
+// (double)g * (double)g is exact (48 significand bits) and no sum of n such squares can leave double's range, so the total is
+// non-finite exactly when an element outside the skip range is.  The grid (wn_grad_sumsq_blocks) depends on n alone and every
+// level of the sum -- per thread front to back, the xor butterfly of a wave, the waves of a block in order, the blocks in the
+// finalize launch -- is a fixed order: the same buffer at the same address modulo 16 gives the same bits on every device.
+#define WN_GN_MAXBLOCKS 512
+#define WN_GN_BATCH 4
+int wn_grad_sumsq_blocks(long n) { return (int)wn_quad_blocks(n, WN_GN_MAXBLOCKS); }
+
+__global__ __launch_bounds__(WN_TPB) void k_grad_sumsq(const float* __restrict__ g, long n, long skip_lo, long skip_hi,
+                                                       double* __restrict__ partial) {
+    __shared__ double red[WN_TPB >> 6];
+    const WnQuadSplit qs = wn_quad_split(g, n);
+    const long head = qs.head, n4 = qs.n4;
+    const float4* q = reinterpret_cast<const float4*>(g + head);
+    const long stride = (long)gridDim.x * WN_TPB;
+    double acc = 0.0;
+    // WN_GN_BATCH quads per thread and trip, their 16-byte loads issued back to back (32 KiB in flight per CU at 8 waves per CU) and
+    // no early exit in the body: a quad beyond the end re-reads quad j and adds zeros, an element inside the skip range adds
+    // zero whatever it holds.  A thread still adds its quads j, j + stride, j + 2 stride, ... front to back.
+    for (long j = (long)blockIdx.x * WN_TPB + threadIdx.x; j < n4; j += WN_GN_BATCH * stride) {
+        float4 v[WN_GN_BATCH];
+        WN_UNROLL
+        for (int k = 0; k < WN_GN_BATCH; ++k) {
+            const long jk = j + k * stride;
+            v[k] = q[jk < n4 ? jk : j];
+        }
+        WN_UNROLL
+        for (int k = 0; k < WN_GN_BATCH; ++k) {
+            const long jk = j + k * stride;
+            const long i0 = head + 4 * jk;
+            const bool in = jk < n4;
+            const double x = (in && (i0 < skip_lo || i0 >= skip_hi)) ? (double)v[k].x : 0.0;
+            const double y = (in && (i0 + 1 < skip_lo || i0 + 1 >= skip_hi)) ? (double)v[k].y : 0.0;
+            const double z = (in && (i0 + 2 < skip_lo || i0 + 2 >= skip_hi)) ? (double)v[k].z : 0.0;
+            const double w = (in && (i0 + 3 < skip_lo || i0 + 3 >= skip_hi)) ? (double)v[k].w : 0.0;
+            acc += x * x;
+            acc += y * y;
+            acc += z * z;
+            acc += w * w;
+        }
+    }
+    long e;   // scalar head and tail
+    if (wn_quad_edge(qs, n, &e) && (e < skip_lo || e >= skip_hi)) acc += (double)g[e] * (double)g[e];
+    acc = wn_wave_sum_f64(acc);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = red[0];
+        for (int i = 1; i < (WN_TPB >> 6); ++i) s += red[i];
+        partial[blockIdx.x] = s;
+    }
+}
+
+int wn_grad_sumsq(const float* g, long n, long skip_lo, long skip_hi, double* partial, wn_stream_t st) {
+    WN_PROF("grad_sumsq", 2.0 * (double)n, 4.0 * (double)n, st);
+    if (skip_hi <= skip_lo) skip_lo = skip_hi = 0;
+    WN_LAUNCH(k_grad_sumsq, dim3((unsigned)wn_grad_sumsq_blocks(n)), dim3(WN_TPB), 0, st, g, n, skip_lo, skip_hi, partial);
+    return 0;
+}
+
+// One block: the partials in a fixed order, then every scalar the guarded Adam launch reads.  Everything in the state block except
+// the two step counters is written from scratch (nothing depends on what the block held before).
+__global__ __launch_bounds__(WN_TPB) void k_grad_norm_finalize(const double* __restrict__ partial, int nb, float max_norm, int guard,
+                                                               float lr, float beta1, float beta2, WnOptState* __restrict__ state) {
+    __shared__ double red[WN_TPB >> 6];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nb; i += WN_TPB) acc += partial[i];
+    acc = wn_wave_sum_f64(acc);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double s = red[0];
+    for (int i = 1; i < (WN_TPB >> 6); ++i) s += red[i];
+    // judged on the double sum (exponent field not all ones): finite elements, +-3e38 included, can never make it inf or NaN
+    const bool finite = ((__builtin_bit_cast(unsigned long long, s) >> 52) & 0x7ffULL) != 0x7ffULL;
+    const double norm = sqrt(s);
+    // torch.nn.utils.clip_grad_norm_ (norm_type 2): min(1, max_norm / (total_norm + 1e-6)); a NaN norm gives a NaN coefficient there
+    // too (the guard is what stops it).  max_norm <= 0 or inf: measure only, the coefficient is exactly 1.
+    double coef = 1.0;
+    if (max_norm > 0.0f && max_norm <= 3.402823466e38f) {
+        coef = (double)max_norm / (norm + 1e-6);
+        if (coef > 1.0) coef = 1.0;
+    }
+    const int apply = (guard && !finite) ? 0 : 1;
+    state->sumsq = s;
+    state->total_norm = (float)norm;
+    state->clip_coef = (float)coef;
+    state->apply = apply;
+    state->reserved = 0;
+    state->beta1 = beta1;
+    state->beta2 = beta2;
+    if (apply) {
+        const int64_t step = state->steps_applied + 1;
+        state->steps_applied = step;
+        // the formulas of wn_adam_step, with the device's own count of applied steps
+        const double bc1 = 1.0 - pow((double)beta1, (double)step);
+        const double bc2 = 1.0 - pow((double)beta2, (double)step);
+        state->lr_over_bc1 = (float)((double)lr / bc1);
+        state->sqrt_bc2 = (float)sqrt(bc2);
+    } else {
+        state->steps_skipped = state->steps_skipped + 1;
+        state->lr_over_bc1 = 0.0f;
+        state->sqrt_bc2 = 0.0f;
+    }
+}
+
+int wn_grad_norm_finalize(const double* partial, int nb, float max_norm, int guard, float lr, float beta1, float beta2,
+                          WnOptState* state, wn_stream_t st) {
+    WN_PROF("grad_norm_finalize", 0.0, 8.0 * (double)nb, st);
+    WN_LAUNCH(k_grad_norm_finalize, dim3(1), dim3(WN_TPB), 0, st, partial, nb, max_norm, guard, lr, beta1, beta2, state);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// One walk over two non-overlapping buffers a and b (the entry points refuse an overlap, so every element is read and written
+// by exactly one thread), one OP per element.  When a and b share their address modulo 16 the body moves 16-byte quads (BATCH
+// of each buffer in flight per thread) behind a scalar head and in front of a scalar tail; otherwise every element goes alone.
+// OP names what it needs: b is always read, a only with READ_A, and WRITE_A / WRITE_B say which side apply() changed.
+//   WnSwapOp                   a[i] <-> b[i] with no temporary buffer
+//   WnAccumOp<WN_ACCUM_SET>    a[i] = b[i]            gradient accumulation over micro-batches (include/wavenet_hip.h, ABI v15),
+//   WnAccumOp<WN_ACCUM_ADD>    a[i] = a[i] + b[i]     a = acc, b = grad: one plain fp32 add per element, nothing else
+//   WnAccumOp<WN_ACCUM_FINISH> b[i] = a[i] + b[i]
+struct WnSwapOp {
+    static constexpr bool READ_A = true, WRITE_A = true, WRITE_B = true;
+    static __device__ __forceinline__ void apply(float& a, float& b) {
+        const float t = a;
+        a = b;
+        b = t;
+    }
+};
+template <int MODE>
+struct WnAccumOp {
+    static constexpr bool READ_A = MODE != WN_ACCUM_SET, WRITE_A = MODE != WN_ACCUM_FINISH, WRITE_B = MODE == WN_ACCUM_FINISH;
+    static __device__ __forceinline__ void apply(float& a, float& b) {
+        const float s = READ_A ? a + b : b;
+        if (WRITE_B) b = s;
+        else a = s;
+    }
+};
+
+template <class OP>
+static __device__ __forceinline__ void wn_pair_one(float* a, float* b, long i) {
+    float y = b[i], x = OP::READ_A ? a[i] : 0.0f;
+    OP::apply(x, y);
+    if (OP::WRITE_A) a[i] = x;
+    if (OP::WRITE_B) b[i] = y;
+}
+
+template <class OP, int BATCH>
+static __device__ __forceinline__ void wn_pair_sweep(float* a, float* b, long n) {
+    const long stride = (long)gridDim.x * WN_TPB;
+    const long tid = (long)blockIdx.x * WN_TPB + threadIdx.x;
+    if ((reinterpret_cast<uintptr_t>(a) & 15) != (reinterpret_cast<uintptr_t>(b) & 15)) {
+        for (long i = tid; i < n; i += stride) wn_pair_one<OP>(a, b, i);
+        return;
+    }
+    const WnQuadSplit s = wn_quad_split(a, n);
+    float4* a4 = reinterpret_cast<float4*>(a + s.head);
+    float4* b4 = reinterpret_cast<float4*>(b + s.head);
+    for (long j = tid; j < s.n4; j += BATCH * stride) {
+        float4 x[BATCH], y[BATCH];   // x stays unset without READ_A: such an OP's apply() may assign its `a`, never read it
+        WN_UNROLL
+        for (int k = 0; k < BATCH; ++k) {
+            const long jk = j + k * stride;
+            if (jk < s.n4) {
+                y[k] = b4[jk];
+                if (OP::READ_A) x[k] = a4[jk];
+            }
+        }
+        WN_UNROLL
+        for (int k = 0; k < BATCH; ++k) {
+            const long jk = j + k * stride;
+            if (jk < s.n4) {
+                OP::apply(x[k].x, y[k].x);
+                OP::apply(x[k].y, y[k].y);
+                OP::apply(x[k].z, y[k].z);
+                OP::apply(x[k].w, y[k].w);
+                if (OP::WRITE_A) a4[jk] = x[k];
+                if (OP::WRITE_B) b4[jk] = y[k];
+            }
+        }
+    }
+    long i;
+    if (wn_quad_edge(s, n, &i)) wn_pair_one<OP>(a, b, i);
+}
+
+#define WN_SWAP_MAXBLOCKS 512
+#define WN_SWAP_BATCH 2
+__global__ __launch_bounds__(WN_TPB) void k_swap(float* a, float* b, long n) { wn_pair_sweep<WnSwapOp, WN_SWAP_BATCH>(a, b, n); }
+
+int wn_swap(float* a, float* b, long n, wn_stream_t st) {
+    WN_PROF("swap", 0.0, 16.0 * (double)n, st);
+    WN_LAUNCH(k_swap, dim3(wn_quad_blocks(n, WN_SWAP_MAXBLOCKS)), dim3(WN_TPB), 0, st, a, b, n);
+    return 0;
+}
+
+#define WN_ACCUM_MAXBLOCKS 1024
+#define WN_ACCUM_BATCH 2
+template <int MODE>
+__global__ __launch_bounds__(WN_TPB) void k_grad_accumulate(float* __restrict__ acc, float* __restrict__ grad, long n) {
+    wn_pair_sweep<WnAccumOp<MODE>, WN_ACCUM_BATCH>(acc, grad, n);
+}
+
+int wn_grad_accumulate(float* acc, float* grad, long n, int mode, wn_stream_t st) {
+    if (mode != WN_ACCUM_SET && mode != WN_ACCUM_ADD && mode != WN_ACCUM_FINISH) return 1;
+    WN_PROF("grad_accumulate", 0.0, 12.0 * (double)n, st);
+    const dim3 grid(wn_quad_blocks(n, WN_ACCUM_MAXBLOCKS));
+    if (mode == WN_ACCUM_SET) {
+        WN_LAUNCH(k_grad_accumulate<WN_ACCUM_SET>, grid, dim3(WN_TPB), 0, st, acc, grad, n);
+    } else if (mode == WN_ACCUM_ADD) {
+        WN_LAUNCH(k_grad_accumulate<WN_ACCUM_ADD>, grid, dim3(WN_TPB), 0, st, acc, grad, n);
+    } else {
+        WN_LAUNCH(k_grad_accumulate<WN_ACCUM_FINISH>, grid, dim3(WN_TPB), 0, st, acc, grad, n);
+    }
+    return 0;
+}

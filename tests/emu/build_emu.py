@@ -9,12 +9,15 @@ import fcntl
 import hashlib
 import os
 import subprocess
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "pytorchwavenetvocoder_amd", "csrc")
 OUT = os.path.join(HERE, "_build")
-SOURCES = ["wn_gemm.hip", "wn_gemm6.hip", "wn_elem.hip", "wn_fused.hip", "wn_decode.hip", "wn_dlp.hip", "wn_dlpm.hip", "wn_dlpf.hip", "wn_prof.hip", "wn_api.hip"]
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from pytorchwavenetvocoder_amd.csrc.build import SOURCES  # noqa: E402  (the product's own list: same translation units)
 LIB = os.path.join(OUT, "libwavenet_emu.so")
 FLAGS = ["-O2", "-std=c++17", "-fPIC", "-DWN_EMU", "-Wno-psabi", "-mfma", "-ffp-contract=off", "-I", HERE, "-I", CSRC, "-x", "c++"]
 # wn_gemm.hip keeps the 16-byte alignment of its float4 accesses checked (hip_emu.h: WN_EMU_ALIGNED_VEC): a trap, no sanitizer

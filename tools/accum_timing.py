@@ -6,7 +6,8 @@ HIP events around windows of calls, the variants alternating window by window:
 
   launches   ``grad_accumulate`` in each of its three modes at the benchmark model's n = 1 594 897 and the recipe model's
              n = 46 190 161 floats, beside torch's ``acc.add_(g)`` on the same two buffers -- the yardstick.  SET moves 8 n bytes, ADD,
-             FINISH and ``add_`` 12 n (two reads, one write); the TB/s column is that traffic over the median.
+             FINISH and ``add_`` 12 n (two reads, one write); the TB/s column is that traffic over the median.  ``swap``
+             (``wn_op_swap``, the same two-buffer walk in csrc/wn_optim.inl: 16 n bytes) is timed in the same windows.
   cycle      on the benchmark's model: one cycle of A = 4 micro-batches of B = 2 x T = 23040 (``micro_step=(i, 4)``) against four
              plain B = 2 calls (what the cycle costs without its four launches) and against the one B = 8 call (what a device with
              room for it would run instead).  No optimizer step in any of the three.
@@ -64,13 +65,14 @@ def launches(name, calls, windows, dev):
     def op(mode, grad):
         return lambda: lib.check(lib.wn_op_accumulate(acc.data_ptr(), grad.data_ptr(), n, mode, st), "wn_op_accumulate")
     fns = {"set": op(_lib.ACCUM_SET, g), "add": op(_lib.ACCUM_ADD, g), "finish": op(_lib.ACCUM_FINISH, g2),
+           "swap": lambda: lib.check(lib.wn_op_swap(acc.data_ptr(), g.data_ptr(), n, st), "wn_op_swap"),
            "torch_add_": lambda: acc.add_(g)}
     for fn in fns.values():
         for _ in range(5):
             fn()
     torch.cuda.synchronize()
     us = alternate(fns, calls, windows)
-    words = {"set": 8, "add": 12, "finish": 12, "torch_add_": 12}
+    words = {"set": 8, "add": 12, "finish": 12, "swap": 16, "torch_add_": 12}
     return {"part": "launches", "model": name, "n": n, "calls_per_window": calls, "windows": windows, "launch_us": us,
             "tb_per_s": {k: words[k] * n / (1e6 * us[k]["median"]) for k in us},
             "add_minus_torch_us": us["add"]["median"] - us["torch_add_"]["median"],

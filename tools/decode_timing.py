@@ -12,16 +12,18 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXP = os.path.join(ROOT, "tools", "exp")
 SO = os.path.join(EXP, "libwn_timing.so")
+sys.path.insert(0, ROOT)
+from pytorchwavenetvocoder_amd.csrc.build import SOURCES  # noqa: E402
 
 
 def build():
     os.makedirs(EXP, exist_ok=True)
     csrc = os.path.join(ROOT, "pytorchwavenetvocoder_amd", "csrc")
     objs = []
-    for name in ("wn_gemm", "wn_gemm6", "wn_elem", "wn_fused", "wn_decode", "wn_prof", "wn_api"):
-        obj = os.path.join(EXP, name + ".timing.o")
+    for src in SOURCES:
+        obj = os.path.join(EXP, src.replace(".hip", ".timing.o"))
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DWN_TIMING", "-c",
-                               os.path.join(csrc, name + ".hip"), "-o", obj])
+                               os.path.join(csrc, src), "-o", obj])
         objs.append(obj)
     subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SO] + objs)
 
@@ -29,7 +31,6 @@ def build():
 if "--build-only" in sys.argv:
     build()
     sys.exit(0)
-sys.path.insert(0, ROOT)
 os.environ["WN_LIB_PATH"] = SO
 import torch  # noqa: E402
 

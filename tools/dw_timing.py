@@ -18,6 +18,8 @@ EXP = os.path.join(ROOT, "tools", "exp")
 VARIANT = os.environ.get("WN_DWT_VARIANT", "")   # "", NOLOAD, NOSPLIT, NOPUT: what-if builds that drop one part of the k-step (timing only)
 SO = os.path.join(EXP, "libwn_dwtiming%s.so" % VARIANT)
 CSRC = os.path.join(ROOT, "pytorchwavenetvocoder_amd", "csrc")
+sys.path.insert(0, ROOT)
+from pytorchwavenetvocoder_amd.csrc.build import SOURCES  # noqa: E402
 
 
 def build():
@@ -26,8 +28,7 @@ def build():
     subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-DWN_TIMING"] +
                           (["-DWN_DWX_" + VARIANT] if VARIANT else []) +
                           ["-c", os.path.join(CSRC, "wn_gemm6.hip"), "-o", obj])
-    objs = [obj if n == "wn_gemm6" else os.path.join(CSRC, n + ".o")
-            for n in ("wn_gemm", "wn_gemm6", "wn_elem", "wn_fused", "wn_decode", "wn_dlp", "wn_dlpm", "wn_dlpf", "wn_prof", "wn_api")]
+    objs = [obj if s == "wn_gemm6.hip" else os.path.join(CSRC, s.replace(".hip", ".o")) for s in SOURCES]
     subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SO] + objs)
 
 
@@ -35,7 +36,6 @@ if "--build-only" in sys.argv or not os.path.exists(SO):
     build()
     if "--build-only" in sys.argv:
         sys.exit(0)
-sys.path.insert(0, ROOT)
 os.environ["WN_LIB_PATH"] = SO
 import torch  # noqa: E402
 

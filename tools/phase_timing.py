@@ -16,6 +16,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXP = os.path.join(ROOT, "tools", "exp")
 SO = os.path.join(EXP, "libwn_timing.so")
+sys.path.insert(0, ROOT)
+from pytorchwavenetvocoder_amd.csrc.build import SOURCES  # noqa: E402
 
 
 def build():
@@ -23,10 +25,10 @@ def build():
     csrc = os.path.join(ROOT, "pytorchwavenetvocoder_amd", "csrc")
     objs = []
     procs = []
-    for name in ("wn_gemm", "wn_gemm6", "wn_elem", "wn_fused", "wn_decode", "wn_dlp", "wn_dlpm", "wn_dlpf", "wn_prof", "wn_api"):
-        obj = os.path.join(EXP, name + ".timing.o")
+    for src in SOURCES:
+        obj = os.path.join(EXP, src.replace(".hip", ".timing.o"))
         procs.append(subprocess.Popen(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-DWN_TIMING", "-c",
-                                       os.path.join(csrc, name + ".hip"), "-o", obj]))
+                                       os.path.join(csrc, src), "-o", obj]))
         objs.append(obj)
     for pr in procs:
         if pr.wait() != 0:
@@ -38,7 +40,6 @@ if "--build-only" in sys.argv or not os.path.exists(SO):
     build()
     if "--build-only" in sys.argv:
         sys.exit(0)
-sys.path.insert(0, ROOT)
 os.environ["WN_LIB_PATH"] = SO
 import torch  # noqa: E402
 
