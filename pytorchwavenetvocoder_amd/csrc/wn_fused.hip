@@ -498,6 +498,42 @@ static __device__ __forceinline__ void split8(const float (&x)[8], wn_f4 (&bf)[3
     bf[1].x = wn_bits_f32(mq[0]); bf[1].y = wn_bits_f32(mq[1]); bf[1].z = wn_bits_f32(mq[2]); bf[1].w = wn_bits_f32(mq[3]);
     bf[2].x = wn_bits_f32(lq[0]); bf[2].y = wn_bits_f32(lq[1]); bf[2].z = wn_bits_f32(lq[2]); bf[2].w = wn_bits_f32(lq[3]);
 }
+// the six products of two row tiles' weight pieces with the operand's pieces, small terms first (WN_EXP_NPROD: top of the file)
+static __device__ __forceinline__ void products6(const wn_f4 (&af)[2][3], const wn_f4 (&bf)[3], f32x16& c0, f32x16& c1) {
+    constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+    WN_UNROLL
+    for (int t6 = 0; t6 < WN_EXP_NPROD; ++t6) {
+        c0 = mfma_bf16(af[0][PA[t6]], bf[PB[t6]], c0);
+        c1 = mfma_bf16(af[1][PA[t6]], bf[PB[t6]], c1);
+    }
+}
+// The fragments of one 16-k block of a 64-row weight image, [NP pieces][64 rows][16 k], for both row tiles; Wl: the block's
+// address in the LDS plus this lane's wn_frag_off
+template <int NP>
+static __device__ __forceinline__ void lds_frags(const char* Wl, wn_f4 (&af)[2][NP]) {
+    WN_UNROLL
+    for (int q = 0; q < 2; ++q) {
+        WN_UNROLL
+        for (int p = 0; p < NP; ++p) af[q][p] = *reinterpret_cast<const wn_f4*>(Wl + p * 2048 + q * 1024);
+    }
+}
+// ... of block kb of a res-1x1 image: from the LDS at Wr, or (RG: "res from global") from the pre-split image behind Ir, where
+// the blocks start `base` bytes in
+template <bool RG>
+static __device__ __forceinline__ void res_frags(const char* Wr, wn_rsrc_t Ir, unsigned base, int vfrag, int kb, wn_f4 (&af)[2][3]) {
+    if constexpr (RG) {
+        WN_UNROLL
+        for (int q = 0; q < 2; ++q) {
+            WN_UNROLL
+            for (int p = 0; p < 3; ++p) {
+                const float4 f = wn_buf_load4(Ir, vfrag, base + (unsigned)(kb * 6144 + p * 2048 + q * 1024));
+                af[q][p] = wn_f4{f.x, f.y, f.z, f.w};
+            }
+        }
+    } else {
+        lds_frags(Wr + kb * 6144 + vfrag, af);
+    }
+}
 // 8 source values (stride `st` floats) of one (row, block half) -> the three LDS pieces
 static __device__ __forceinline__ void split_to_lds(const float* src, int st, char* dst, int piece_bytes) {
     float x[8];
@@ -626,6 +662,15 @@ static __device__ __forceinline__ void split8h(const float (&x)[8], float s, wn_
     }
     bf[0].x = wn_bits_f32(hq[0]); bf[0].y = wn_bits_f32(hq[1]); bf[0].z = wn_bits_f32(hq[2]); bf[0].w = wn_bits_f32(hq[3]);
     bf[1].x = wn_bits_f32(lq[0]); bf[1].y = wn_bits_f32(lq[1]); bf[1].z = wn_bits_f32(lq[2]); bf[1].w = wn_bits_f32(lq[3]);
+}
+// the three products of the fp16 pair, small terms first: h l, l h, h h
+static __device__ __forceinline__ void products3(const wn_f4 (&af)[2][2], const wn_f4 (&bf)[2], f32x16& c0, f32x16& c1) {
+    constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};
+    WN_UNROLL
+    for (int t3 = 0; t3 < 3; ++t3) {
+        c0 = mfma_f16(af[0][PA[t3]], bf[PB[t3]], c0);
+        c1 = mfma_f16(af[1][PA[t3]], bf[PB[t3]], c1);
+    }
 }
 // power of two s with amax * s in [2^(E-1), 2^E)  (amax == 0 or tiny / huge: clamped, s stays a normal float with a normal inverse)
 static __host__ __device__ __forceinline__ float wn_pow2_scale(float amax, int E) {
@@ -847,15 +892,6 @@ struct FwdBf16x3 {
         __syncthreads();
         return cv;
     }
-    // the six products of two rows' weight pieces with the operand's pieces, small terms first
-    static __device__ __forceinline__ void products(const wn_f4 (&af)[2][3], const wn_f4 (&bf)[3], f32x16& c0, f32x16& c1) {
-        constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-        WN_UNROLL
-        for (int t6 = 0; t6 < WN_EXP_NPROD; ++t6) {
-            c0 = mfma_bf16(af[0][PA[t6]], bf[PB[t6]], c0);
-            c1 = mfma_bf16(af[1][PA[t6]], bf[PB[t6]], c1);
-        }
-    }
     template <int K>
     __device__ __forceinline__ void tap(f32x16 (&acc)[4], const float (&x)[32], bool ok, int tapblk) {
         WN_UNROLL
@@ -874,7 +910,7 @@ struct FwdBf16x3 {
                     WN_UNROLL
                     for (int p = 0; p < 3; ++p) af[q][p] = *reinterpret_cast<const wn_f4*>(Wl + p * (128 * 32) + (qh + q) * 1024);
                 }
-                products(af, bf, acc[qh], acc[qh + 1]);
+                products6(af, bf, acc[qh], acc[qh + 1]);
             }
         }
     }
@@ -886,22 +922,9 @@ struct FwdBf16x3 {
         out[1] = f32x16_zero();
         const wn_rsrc_t Ir = wn_make_buf(wimg, (unsigned)(RG ? fwd_image_bytes(K) : 16));
         const int vfrag = wn_frag_off(li, hi);
-        auto res_frags = [&](int kb, wn_f4 (&af)[2][3]) {
-            WN_UNROLL
-            for (int q = 0; q < 2; ++q) {
-                WN_UNROLL
-                for (int p = 0; p < 3; ++p) {
-                    if (RG) {
-                        const float4 f = wn_buf_load4(Ir, vfrag, (unsigned)(K * 4 * WD_BLK + kb * WR_BLK + p * (64 * 32) + q * 1024));
-                        af[q][p] = wn_f4{f.x, f.y, f.z, f.w};
-                    } else {
-                        af[q][p] = *reinterpret_cast<const wn_f4*>(Wr + kb * WR_BLK + vfrag + p * (64 * 32) + q * 1024);
-                    }
-                }
-            }
-        };
+        constexpr unsigned base = K * 4 * WD_BLK;   // (RG) the res-1x1 blocks lie behind the taps in the image
         wn_f4 afr[2][2][3];   // two sets: with RG the fragments of block kb + 1 are in flight under the MFMAs of block kb
-        res_frags(0, afr[0]);
+        res_frags<RG>(Wr, Ir, base, vfrag, 0, afr[0]);
         WN_UNROLL
         for (int kb = 0; kb < 4; ++kb) {
             float x8[8];
@@ -909,8 +932,8 @@ struct FwdBf16x3 {
             for (int e = 0; e < 8; ++e) x8[e] = z[(8 * kb + e) >> 4][(8 * kb + e) & 15];
             wn_f4 bf[3];
             split8(x8, bf);
-            if (kb + 1 < 4) res_frags(kb + 1, afr[(kb + 1) & 1]);
-            products(afr[kb & 1], bf, out[0], out[1]);
+            if (kb + 1 < 4) res_frags<RG>(Wr, Ir, base, vfrag, kb + 1, afr[(kb + 1) & 1]);
+            products6(afr[kb & 1], bf, out[0], out[1]);
         }
         WN_UNROLL
         for (int q = 0; q < 2; ++q) {
@@ -959,14 +982,6 @@ struct FwdF16x2 {
         inv_wr = tail[1];
         return cv;
     }
-    static __device__ __forceinline__ void products(const wn_f4 (&af)[2][2], const wn_f4 (&bf)[2], f32x16& c0, f32x16& c1) {
-        constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};   // small terms first: h l, l h, h h
-        WN_UNROLL
-        for (int t3 = 0; t3 < 3; ++t3) {
-            c0 = mfma_f16(af[0][PA[t3]], bf[PB[t3]], c0);
-            c1 = mfma_f16(af[1][PA[t3]], bf[PB[t3]], c1);
-        }
-    }
     template <int K>
     __device__ __forceinline__ void tap(f32x16 (&acc)[4], const float (&x)[32], bool ok, int tapblk) {
         // The tile's block scale: the smallest of its taps' scales so far; the accumulators follow it down (exact: powers of two).
@@ -999,7 +1014,7 @@ struct FwdF16x2 {
                     WN_UNROLL
                     for (int p = 0; p < 2; ++p) af[q][p] = *reinterpret_cast<const wn_f4*>(Wl + p * (128 * 32) + (qh + q) * 1024);
                 }
-                products(af, bf, acc[qh], acc[qh + 1]);
+                products3(af, bf, acc[qh], acc[qh + 1]);
             }
         }
         if (tapblk == K - 1) inv = inv_wd / sc;   // (both powers of two)
@@ -1024,7 +1039,7 @@ struct FwdF16x2 {
                 WN_UNROLL
                 for (int p = 0; p < 2; ++p) afr[q][p] = *reinterpret_cast<const wn_f4*>(Wr + kb * WR_BLK + vfrag + p * (64 * 32) + q * 1024);
             }
-            products(afr, bf, out[0], out[1]);
+            products3(afr, bf, out[0], out[1]);
         }
         const float invr = inv_wr * (1.0f / 8192.0f);
         WN_UNROLL
@@ -1172,99 +1187,192 @@ int wn_fused_resblock_fwd(const float* wd_f, const float* wres_f, const float* c
 }
 
 // ---------------------------------------------------------------------------------------------
-// conv64: out[64][t] = sum over segments, channels k:  W_seg[k][0..63] * src_seg[k][t - shift_seg]
+// The backward kernels.  What they share, and what every one of them is built from:
+//   bwd_gate_epilogue   gate' (dP from dZ and the saved gate halves), optionally with the aux-gradient partial sums and the
+//                       per-tile max |dP| -- the ONE place that arithmetic is written
+//   split_chunk         one 32-channel operand chunk on the split arithmetics (six bf16 products / three fp16 products)
+//   conv64_tiles        the tile loop of k_conv64 (exact f32-input MFMA) and k_conv64s (bf16 split): policies ConvF32, ConvBf16x3
+//   k_chain64s          one launch per layer of the data chain
 // ---------------------------------------------------------------------------------------------
-struct ConvSeg {
-    const float* src;  // (B, nch, T)
-    const float* w;    // [nch][64] (global); staged to LDS at float offset woff
-    int nch;           // multiple of 32
-    int shift;
-    int woff;
-};
-struct ConvArgs {
-    ConvSeg seg[3];
-    int nseg;
-    int nchunks;  // sum of nch/32
-    int wfloats;  // total LDS floats
-    int B, T;
-    const float* S;      // MODE 0
-    const float* Gt;     // MODE 0: the saved tanh half -- or, with gz != 0, the saved product z = s * tanh (g = z / s)
-    int gz;
-    const float* resid;  // MODE 1 (nullable)
-    float* out;          // MODE 0: dP (B,128,T) ; MODE 1: dX (B,64,T)
-    int interleave;      // k_conv64s: chunk q -> segment q % nseg (equal-size segments): the taps of one channel group back to back
-    // MODE 2 (gate' + aux-gradient partials, see wn_fused.h)
-    const float* G;      // (B, g_bstride) frame-rate aux projection of this layer, rows [0,128)
+// The accumulator tile of a wave: register r of row tile q, lane (li, hi) = channel 32 q + mfma32_row(r, hi), sample t.  Stores
+// are unconditional: lanes past T carry vst = WN_VOFF_DEAD, which the buffer range check drops (no branch per element).
+struct GateEpi {
+    float* out;          // dP (B, 128, T)
+    int gz;              // e1 is the saved product z = s * tanh instead of the tanh half (g = z / s)
+    // AUX: the partial sums of the aux gradient (wn_fused.h)
+    const float* G;      // (B, g_bstride) frame-rate aux projection of the layer, rows [0,128)
     long g_bstride;
     const float* upw;    // [U]
     int U, F;
     float* dGp;          // (B, 128, T/16)
     float* qp;           // (B, T)
+    float* amaxPm;       // TRACK_AMAX: (B, tiles) max |dP| of every 32-sample tile (nullable)
 };
 
-template <int MODE>
-__global__ __launch_bounds__(WN_LB) void k_conv64(ConvArgs a) {
-    WN_DYN_SMEM(smem_raw);
-    float* W = reinterpret_cast<float*>(smem_raw);
-    for (int sg = 0; sg < a.nseg; ++sg) stage_copy(W + a.seg[sg].woff, a.seg[sg].w, a.seg[sg].nch * 64);
-    __syncthreads();
-    // De-phase the two waves that share a SIMD (waves w and w+4): started together they would run
-    // their MFMA phases and their gate/store phases in lock step and leave the matrix pipe idle
-    // during the latter; half a tile of head start makes one wave's VALU/VMEM phase coincide with
-    // the other's MFMA phase.
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+// gate backward (wavenet.py:529-532 reversed): dP = [dZ g s (1-s) ; dZ s (1-g^2)] of tile tb of sequence b, from dz and the saved
+// halves e0 = s, e1 = tanh (or z).  AUX adds the partial sums of the aux gradient: every lane takes part in the cross-lane sums,
+// so lanes past T carry dP = 0 there -- as they do with TRACK_AMAX (the tile's max |dP| for the fp16 pair chain that reads it);
+// without either, what those lanes compute only feeds stores that are dropped.  HALF_BARRIER: one 32-row half at a time (the
+// chain's register budget).
+template <bool AUX, bool TRACK_AMAX, bool HALF_BARRIER>
+static __device__ __forceinline__ void bwd_gate_epilogue(const GateEpi& p, const f32x16 (&dz)[2], const float (&e0)[2][16],
+                                                         const float (&e1)[2][16], int T, int tiles_per_b, int b, int tb, int t,
+                                                         bool inb, int vst) {
+    const int lane = threadIdx.x & 63;
     const int li = lane & 31, hi = lane >> 5;
-    const int T = a.T;
     const int T4 = T * 4;
-    const int tiles_per_b = (T + 31) >> 5;
-    const int ntiles = a.B * tiles_per_b;
-    const TileWalk walk = tile_walk(ntiles, threadIdx.x >> 6);
-    const int step = walk.step, tile_end = walk.end;
-    const int NCH = a.nchunks;
-
-    // Operand chunks (32 channels = 16 k-steps) are double buffered in registers: chunk q+2 is in
-    // flight while the 32 MFMAs of chunks q and q+1 run.
-    float xa[16], xb[16];
-    bool oka = false, okb = false;
-    auto locate = [&](int q, int& sg, int& c0) {
-        sg = 0;
-        c0 = q * 32;
-        while (sg + 1 < a.nseg && c0 >= a.seg[sg].nch) {
-            c0 -= a.seg[sg].nch;
-            ++sg;
-        }
+    const wn_rsrc_t Or = wn_make_buf(p.out + (long)b * 128 * T, (unsigned)(128 * T4));
+    float pmax = 0.0f;
+    (void)pmax; (void)li; (void)hi;
+    // element (q, r): both halves of dP computed and stored
+    auto element = [&](int q, int r, float& dpa, float& dpg) {
+        const int so = (32 * q + mfma32_row(r, 0)) * T4;
+        const float s = e0[q][r], g = p.gz ? e1[q][r] * wn_rcp(e0[q][r]) : e1[q][r];
+        const float dzv = (AUX || TRACK_AMAX) ? (inb ? dz[q][r] : 0.0f) : dz[q][r];
+        dpa = dzv * g * (s * (1.0f - s));
+        dpg = dzv * s * (1.0f - g * g);
+        wn_buf_store(Or, dpa, vst, so);
+        wn_buf_store(Or, dpg, vst, so + 64 * T4);
+        if (TRACK_AMAX) pmax = fmaxf(pmax, fmaxf(fabsf(dpa), fabsf(dpg)));
     };
-    auto issue = [&](int tl_v, int q, float (&xr)[16], bool& okr) {
-        const int tl = WN_UNIFORM(tl_v);
-        const int b = tl / tiles_per_b;
-        const int t = (tl - b * tiles_per_b) * 32 + li;
-        int sg, c0;
-        locate(q, sg, c0);
-        const ConvSeg& g = a.seg[sg];
-        const int ts = t - g.shift;
-        const bool ok = (t < T) && ts >= 0 && ts < T;
-        okr = ok;
-        const wn_rsrc_t Sr = wn_make_buf(g.src + (long)b * g.nch * T, (unsigned)(g.nch * T4));
-        const int vt = ok ? (hi * T + ts) * 4 : 0;
+    if constexpr (AUX) {
+        const int tc = inb ? t : 0;
+        const int fr = tc / p.U;
+        const float wj = inb ? p.upw[tc - fr * p.U] : 0.0f;
+        const int F4 = p.F * 4;
+        const int H = T >> 4;  // 16-sample groups per channel row
+        const wn_rsrc_t Gr = wn_make_buf(p.G + (long)b * p.g_bstride, (unsigned)(128 * F4));
+        const wn_rsrc_t Dr = wn_make_buf(p.dGp + (long)b * 128 * H, (unsigned)(128 * H * 4));
+        const int vg = (4 * hi * p.F + fr) * 4;
+        const int l16 = li & 15;
+        const int h16 = ((tb * 32) >> 4) + (li >> 4);
+        float qsum = 0.0f;
         WN_UNROLL
-        for (int s = 0; s < 16; ++s) xr[s] = wn_buf_load(Sr, vt, (c0 + 2 * s) * T4);
-    };
-    f32x16 acc[2];
-    auto consume = [&](int q, const float (&xr)[16], bool okr) {
-        int sg, c0;
-        locate(q, sg, c0);
-        const float* Wl = W + a.seg[sg].woff + (c0 + hi) * 64 + li;
+        for (int q = 0; q < 2; ++q) {
+            float ga[16], gg[16];
+            WN_UNROLL
+            for (int r = 0; r < 16; ++r) {
+                ga[r] = wn_buf_load(Gr, vg, (32 * q + mfma32_row(r, 0)) * F4);
+                gg[r] = wn_buf_load(Gr, vg, (64 + 32 * q + mfma32_row(r, 0)) * F4);
+            }
+            float keep_a = 0.0f, keep_g = 0.0f;
+            WN_UNROLL
+            for (int r = 0; r < 16; ++r) {
+                float dpa, dpg;
+                element(q, r, dpa, dpg);
+                qsum += dpa * ga[r] + dpg * gg[r];
+                const float ra = wn_row16_sum(wj * dpa), rg = wn_row16_sum(wj * dpg);
+                keep_a = (l16 == r) ? ra : keep_a;
+                keep_g = (l16 == r) ? rg : keep_g;
+            }
+            // lane l16 of each 16-lane group keeps the sums of channel row 32q + mfma32_row(l16, hi)
+            const int row = 32 * q + mfma32_row(l16, hi);
+            const int doff = (h16 < H) ? (row * H + h16) * 4 : 0x7ffffff0;
+            wn_buf_store(Dr, keep_a, doff, 0);
+            wn_buf_store(Dr, keep_g, doff, (h16 < H) ? 64 * H * 4 : 0);
+            if (HALF_BARRIER) WN_SCHED_BARRIER();
+        }
+        qsum += __shfl_xor(qsum, 32, 64);  // the two lane halves hold complementary channel rows
+        if (hi == 0 && inb) p.qp[(long)b * T + t] = qsum;
+    } else {
+        WN_UNROLL
+        for (int q = 0; q < 2; ++q) {
+            WN_UNROLL
+            for (int r = 0; r < 16; ++r) {
+                float dpa, dpg;
+                element(q, r, dpa, dpg);
+            }
+        }
+    }
+    if (TRACK_AMAX && p.amaxPm != nullptr) {
+        pmax = wave_reduce_max(pmax);
+        if (lane == 0) p.amaxPm[(long)b * tiles_per_b + tb] = pmax;
+    }
+}
+
+// One 32-channel operand chunk (two 16-k blocks of NP pieces, [piece][64 rows][16 k], at Wl for this lane) into the 64-row
+// accumulators: xr[8 blk + e] is the lane's share of block blk, zero where !ok.  H16: the fp16 pair of xr * sc, three products;
+// otherwise the three bf16 pieces, six products.
+template <bool H16>
+static __device__ __forceinline__ void split_chunk(const char* Wl, const float (&xr)[16], bool ok, float sc, f32x16 (&acc)[2]) {
+    constexpr int NP = H16 ? 2 : 3;
+    WN_UNROLL
+    for (int blk = 0; blk < 2; ++blk) {
+        float x8[8];
+        WN_UNROLL
+        for (int e = 0; e < 8; ++e) x8[e] = ok ? xr[8 * blk + e] : 0.0f;
+        wn_f4 bf[NP], af[2][NP];
+        if constexpr (H16) split8h(x8, sc, bf);
+        else split8(x8, bf);
+        lds_frags(Wl + blk * (NP * 2048), af);
+        if constexpr (H16) products3(af, bf, acc[0], acc[1]);
+        else products6(af, bf, acc[0], acc[1]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// conv64: out[64][t] = sum over segments, channels k:  W_seg[k][0..63] * src_seg[k][t - shift_seg]
+// MODE 0: the gate' epilogue (dP from the sum = dZ); MODE 1: the sum (+ resid) is dX; MODE 2: gate' with the aux-gradient
+// partial sums (wn_fused.h; split arithmetic only).
+// ---------------------------------------------------------------------------------------------
+struct ConvSeg {
+    const float* src = nullptr;  // (B, nch, T)
+    const float* w = nullptr;    // [nch][64] (global); ConvF32 stages it to the LDS at float offset woff
+    int nch = 0;                 // multiple of 32
+    int shift = 0;
+    int woff = 0;
+};
+struct ConvArgs {
+    ConvSeg seg[3];
+    int nseg = 0;
+    int nchunks = 0;  // sum of nch/32
+    int wfloats = 0;  // total LDS floats
+    int B = 0, T = 0;
+    const float* S = nullptr;      // MODE 0, 2
+    const float* Gt = nullptr;     // MODE 0, 2: the saved tanh half -- or, with gz != 0, the saved product z = s * tanh (g = z / s)
+    int gz = 0;
+    const float* resid = nullptr;  // MODE 1 (nullable)
+    float* out = nullptr;          // MODE 0, 2: dP (B,128,T) ; MODE 1: dX (B,64,T)
+    int interleave = 0;            // ConvBf16x3: chunk q -> segment q % nseg (equal-size segments): the taps of one channel group back to back
+    // MODE 2 (see GateEpi)
+    const float* G = nullptr;
+    long g_bstride = 0;
+    const float* upw = nullptr;
+    int U = 0, F = 0;
+    float* dGp = nullptr;
+    float* qp = nullptr;
+};
+
+// The arithmetics of conv64_tiles.  Each one owns its LDS weights and what depends on their layout:
+//   INTERLEAVES       whether it takes ConvArgs::interleave (its LDS order is the chunk order) or keeps [segment][channel] order
+//   HALF_ROWS         lane half hi starts HALF_ROWS channel rows further into a chunk
+//   chan(s)           channel, within the chunk and before the lane half's rows, of operand load s (16 per chunk and lane)
+//   stage(smem, a)    fills the LDS (the kernel's barrier follows)
+//   consume(...)      chunk q (= channels [c0, c0 + 32) of segment sg) of this lane's operands xr, zero where !ok, into acc
+// Exact f32-input MFMA (an fp32 fma chain): weights as stage_copy leaves them, [k][64 rows] per segment; k-step s of a chunk is
+// channel c0 + 2 s + hi.
+struct ConvF32 {
+    static constexpr bool INTERLEAVES = false;
+    static constexpr int HALF_ROWS = 1;
+    static __device__ __forceinline__ int chan(int s) { return 2 * s; }
+    static __device__ __forceinline__ void stage(char* smem, const ConvArgs& a) {
+        float* W = reinterpret_cast<float*>(smem);
+        for (int sg = 0; sg < a.nseg; ++sg) stage_copy(W + a.seg[sg].woff, a.seg[sg].w, a.seg[sg].nch * 64);
+    }
+    static __device__ __forceinline__ void consume(const char* smem, const ConvArgs& a, int q, int sg, int c0, const float (&xr)[16],
+                                                   bool okr, f32x16 (&acc)[2]) {
+        const int li = threadIdx.x & 31, hi = (threadIdx.x & 63) >> 5;
+        const float* Wl = reinterpret_cast<const float*>(smem) + a.seg[sg].woff + (c0 + hi) * 64 + li;
         // stage = two k-steps (4 LDS operands, 4 MFMAs); ping-pong operand sets: the reads of the next
         // stage are in flight during the MFMAs of the current one
         float a0[4], a1[4];
         WN_UNROLL
-        for (int q = 0; q < 4; ++q) a0[q] = Wl[(2 * (q >> 1)) * 64 + 32 * (q & 1)];
+        for (int i = 0; i < 4; ++i) a0[i] = Wl[(2 * (i >> 1)) * 64 + 32 * (i & 1)];
         WN_SGB_DS(2);
         WN_UNROLL
         for (int s = 0; s < 16; s += 4) {
             WN_UNROLL
-            for (int q = 0; q < 4; ++q) a1[q] = Wl[(2 * (s + 2 + (q >> 1))) * 64 + 32 * (q & 1)];
+            for (int i = 0; i < 4; ++i) a1[i] = Wl[(2 * (s + 2 + (i >> 1))) * 64 + 32 * (i & 1)];
             {
                 const float xv0 = okr ? xr[s] : 0.0f, xv1 = okr ? xr[s + 1] : 0.0f;
                 acc[0] = mfma32(a0[0], xv0, acc[0]);
@@ -1276,7 +1384,7 @@ __global__ __launch_bounds__(WN_LB) void k_conv64(ConvArgs a) {
             WN_SGB_MFMA(4);
             if (s + 4 < 16) {
                 WN_UNROLL
-                for (int q = 0; q < 4; ++q) a0[q] = Wl[(2 * (s + 4 + (q >> 1))) * 64 + 32 * (q & 1)];
+                for (int i = 0; i < 4; ++i) a0[i] = Wl[(2 * (s + 4 + (i >> 1))) * 64 + 32 * (i & 1)];
             }
             {
                 const float xv0 = okr ? xr[s + 2] : 0.0f, xv1 = okr ? xr[s + 3] : 0.0f;
@@ -1288,137 +1396,55 @@ __global__ __launch_bounds__(WN_LB) void k_conv64(ConvArgs a) {
             WN_SGB_DS(2);
             WN_SGB_MFMA(4);
         }
-    };
-
-    int tile_v = walk.first;
-    if (tile_v < tile_end) {
-        issue(tile_v, 0, xa, oka);
-        if (NCH > 1) issue(tile_v, 1, xb, okb);
     }
-    while (tile_v < tile_end) {
-        const int tile = WN_UNIFORM(tile_v);
-        const int b = tile / tiles_per_b;
-        const int t = (tile - b * tiles_per_b) * 32 + li;
-        const bool inb = t < T;
-        const int vcur = inb ? (4 * hi * T + t) * 4 : 0;
-        const int vst = inb ? vcur : WN_VOFF_DEAD;   // stores of lanes past T are dropped by the range check
-        const int next_v = tile_v + step;
-
-        // epilogue inputs: issued now, consumed after all MFMAs of the tile
-        float e0[2][16], e1[2][16];
-        if (MODE == 0) {
-            const wn_rsrc_t Sr = wn_make_buf(a.S + (long)b * 64 * T, (unsigned)(64 * T4));
-            const wn_rsrc_t Gr = wn_make_buf(a.Gt + (long)b * 64 * T, (unsigned)(64 * T4));
-            WN_UNROLL
-            for (int q = 0; q < 2; ++q) {
-                WN_UNROLL
-                for (int r = 0; r < 16; ++r) {
-                    const int so = (32 * q + mfma32_row(r, 0)) * T4;
-                    e0[q][r] = wn_buf_load(Sr, vcur, so);
-                    e1[q][r] = wn_buf_load(Gr, vcur, so);
-                }
-            }
-        } else if (a.resid != nullptr) {
-            const wn_rsrc_t Rr = wn_make_buf(a.resid + (long)b * 64 * T, (unsigned)(64 * T4));
-            WN_UNROLL
-            for (int q = 0; q < 2; ++q) {
-                WN_UNROLL
-                for (int r = 0; r < 16; ++r) e0[q][r] = wn_buf_load(Rr, vcur, (32 * q + mfma32_row(r, 0)) * T4);
-            }
-        }
-        WN_SCHED_BARRIER();
-        acc[0] = f32x16_zero();
-        acc[1] = f32x16_zero();
-        for (int q = 0; q < NCH; q += 2) {
-            consume(q, xa, oka);
-            if (q + 2 < NCH) issue(tile_v, q + 2, xa, oka);
-            else if (next_v < tile_end) issue(next_v, 0, xa, oka);
-            WN_SCHED_BARRIER();
-            if (q + 1 < NCH) {
-                consume(q + 1, xb, okb);
-                if (q + 3 < NCH) issue(tile_v, q + 3, xb, okb);
-                else if (next_v < tile_end && NCH > 1) issue(next_v, 1, xb, okb);
-                WN_SCHED_BARRIER();
-            }
-        }
-        {
-            if (MODE == 0) {
-                // gate backward: dP = [dZ*g*s*(1-s) ; dZ*s*(1-g^2)]
-                const wn_rsrc_t Or = wn_make_buf(a.out + (long)b * 128 * T, (unsigned)(128 * T4));
-                WN_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    WN_UNROLL
-                    for (int r = 0; r < 16; ++r) {
-                        const int so = (32 * q + mfma32_row(r, 0)) * T4;
-                        const float s = e0[q][r], g = a.gz ? e1[q][r] * wn_rcp(e0[q][r]) : e1[q][r], dz = acc[q][r];
-                        wn_buf_store(Or, dz * g * (s * (1.0f - s)), vst, so);
-                        wn_buf_store(Or, dz * s * (1.0f - g * g), vst, so + 64 * T4);
-                    }
-                }
+};
+// The bf16 matrix cores: every fp32 operand is split into three bf16 pieces and the six significant cross products are
+// accumulated in fp32 (see wn_gemm6.hip for the error analysis).  Weights are split once per launch into the LDS in fragment
+// layout, chunk after chunk in the order they are consumed: [16-k block][piece][64 rows][16 k], 6 KB per block; the activation
+// chunk of a lane (2 x 8 consecutive channels of its time step: lane half hi owns channels 8 hi .. 8 hi + 7 of each block) is
+// split in registers.  24 bf16 MFMAs (768 cycles) replace the 32 f32 MFMAs (2048 cycles) of a 32-channel chunk.
+struct ConvBf16x3 {
+    static constexpr bool INTERLEAVES = true;
+    static constexpr int HALF_ROWS = 8;
+    static __device__ __forceinline__ int chan(int s) { return 16 * (s >> 3) + (s & 7); }
+    static __device__ __forceinline__ void stage(char* W, const ConvArgs& a) {
+        for (int idx = threadIdx.x; idx < a.nchunks * 2 * 128; idx += WN_FT) {
+            const int o = idx & 63, h = (idx >> 6) & 1, kbg = idx >> 7;
+            int sg = 0, c = kbg * 16 + 8 * h;
+            if (a.interleave) {
+                const int q = kbg >> 1;
+                sg = q % a.nseg;
+                c = (q / a.nseg) * 32 + (kbg & 1) * 16 + 8 * h;
             } else {
-                const wn_rsrc_t Or = wn_make_buf(a.out + (long)b * 64 * T, (unsigned)(64 * T4));
-                WN_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    WN_UNROLL
-                    for (int r = 0; r < 16; ++r) {
-                        float v = acc[q][r];
-                        if (a.resid != nullptr) v += e0[q][r];
-                        wn_buf_store(Or, v, vst, (32 * q + mfma32_row(r, 0)) * T4);
-                    }
+                while (sg + 1 < a.nseg && c >= a.seg[sg].nch) {
+                    c -= a.seg[sg].nch;
+                    ++sg;
                 }
             }
+            const float* src = a.seg[sg].w + (long)c * 64 + o;
+            float x[8];
+            WN_UNROLL
+            for (int e = 0; e < 8; ++e) x[e] = src[e * 64];
+            wn_f4 bf[3];
+            split8(x, bf);
+            WN_UNROLL
+            for (int p = 0; p < 3; ++p) *reinterpret_cast<wn_f4*>(W + kbg * 6144 + p * 2048 + wn_frag_off(o, h)) = bf[p];
         }
-        tile_v = next_v;
     }
-}
+    static __device__ __forceinline__ void consume(const char* W, const ConvArgs&, int q, int, int, const float (&xr)[16], bool okr,
+                                                   f32x16 (&acc)[2]) {
+        const int li = threadIdx.x & 31, hi = (threadIdx.x & 63) >> 5;
+        split_chunk<false>(W + 2 * q * 6144 + wn_frag_off(li, hi), xr, okr, 1.0f, acc);
+    }
+};
 
-// Same tile loop on the bf16 matrix cores: every fp32 operand is split into three bf16 pieces and the
-// six significant cross products are accumulated in fp32 (see wn_gemm6.hip for the error analysis).
-// Weights are split once per launch into LDS in fragment layout [16-k block][piece][64 rows][16 k];
-// the activation chunk of a lane (2 x 8 consecutive channels of its time step) is split in registers.
-// 24 bf16 MFMAs (768 cycles) replace the 32 f32 MFMAs (2048 cycles) of a 32-channel chunk.
-template <int MODE>
-__global__ __launch_bounds__(WN_LB) void k_conv64s(ConvArgs a) {
+template <int MODE, class Arith>
+static __device__ __forceinline__ void conv64_tiles(const ConvArgs& a) {
     WN_DYN_SMEM(smem_raw);
-    char* W = smem_raw;  // 6 KB per 16-k block: [piece][row][16 k] bf16
-    for (int idx = threadIdx.x; idx < a.nchunks * 2 * 128; idx += WN_FT) {
-        const int o = idx & 63, h = (idx >> 6) & 1, kbg = idx >> 7;
-        int sg = 0, c = kbg * 16 + 8 * h;
-        if (a.interleave) {
-            const int q = kbg >> 1;
-            sg = q % a.nseg;
-            c = (q / a.nseg) * 32 + (kbg & 1) * 16 + 8 * h;
-        } else {
-            while (sg + 1 < a.nseg && c >= a.seg[sg].nch) {
-                c -= a.seg[sg].nch;
-                ++sg;
-            }
-        }
-        const float* src = a.seg[sg].w + (long)c * 64 + o;
-        unsigned hq[4], mq[4], lq[4];
-        WN_UNROLL
-        for (int q = 0; q < 4; ++q) {
-            const float x0 = src[(2 * q) * 64], x1 = src[(2 * q + 1) * 64];
-            hq[q] = wn_pk_bf16(x0, x1);
-            const float r0 = x0 - wn_bits_f32(hq[q] << 16), r1 = x1 - wn_bits_f32(hq[q] & 0xffff0000u);
-            mq[q] = wn_pk_bf16(r0, r1);
-            lq[q] = wn_pk_bf16(r0 - wn_bits_f32(mq[q] << 16), r1 - wn_bits_f32(mq[q] & 0xffff0000u));
-        }
-        unsigned* d = reinterpret_cast<unsigned*>(W + kbg * 6144 + wn_frag_off(o, h));
-        WN_UNROLL
-        for (int q = 0; q < 4; ++q) {
-            d[q] = hq[q];
-            d[512 + q] = mq[q];
-            d[1024 + q] = lq[q];
-        }
-    }
+    Arith::stage(smem_raw, a);
     __syncthreads();
-    // De-phase the two waves that share a SIMD (waves w and w+4): started together they would run
-    // their MFMA phases and their gate/store phases in lock step and leave the matrix pipe idle
-    // during the latter; half a tile of head start makes one wave's VALU/VMEM phase coincide with
-    // the other's MFMA phase.
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int li = lane & 31, hi = lane >> 5;
     const int T = a.T;
     const int T4 = T * 4;
@@ -1429,11 +1455,11 @@ __global__ __launch_bounds__(WN_LB) void k_conv64s(ConvArgs a) {
     const int NCH = a.nchunks;
 
     // Operand chunks (32 channels = 16 k-steps) are double buffered in registers: chunk q+2 is in
-    // flight while the 32 MFMAs of chunks q and q+1 run.
+    // flight while the MFMAs of chunks q and q+1 run.
     float xa[16], xb[16];
     bool oka = false, okb = false;
     auto locate = [&](int q, int& sg, int& c0) {
-        if (a.interleave) {
+        if (Arith::INTERLEAVES && a.interleave) {
             sg = q % a.nseg;
             c0 = (q / a.nseg) * 32;
             return;
@@ -1456,41 +1482,15 @@ __global__ __launch_bounds__(WN_LB) void k_conv64s(ConvArgs a) {
         const bool ok = (t < T) && ts >= 0 && ts < T;
         okr = ok;
         const wn_rsrc_t Sr = wn_make_buf(g.src + (long)b * g.nch * T, (unsigned)(g.nch * T4));
-        const int vt = ok ? (8 * hi * T + ts) * 4 : 0;  // lane half hi owns channels 8*hi .. 8*hi+7 of each 16-k block
+        const int vt = ok ? (Arith::HALF_ROWS * hi * T + ts) * 4 : 0;
         WN_UNROLL
-        for (int s = 0; s < 16; ++s) xr[s] = wn_buf_load(Sr, vt, (c0 + 16 * (s >> 3) + (s & 7)) * T4);
+        for (int s = 0; s < 16; ++s) xr[s] = wn_buf_load(Sr, vt, (c0 + Arith::chan(s)) * T4);
     };
     f32x16 acc[2];
     auto consume = [&](int q, const float (&xr)[16], bool okr) {
-        WN_UNROLL
-        for (int blk = 0; blk < 2; ++blk) {
-            unsigned hq[4], mq[4], lq[4];
-            WN_UNROLL
-            for (int e = 0; e < 4; ++e) {
-                const float x0 = okr ? xr[8 * blk + 2 * e] : 0.0f, x1 = okr ? xr[8 * blk + 2 * e + 1] : 0.0f;
-                hq[e] = wn_pk_bf16(x0, x1);
-                const float r0 = x0 - wn_bits_f32(hq[e] << 16), r1 = x1 - wn_bits_f32(hq[e] & 0xffff0000u);
-                mq[e] = wn_pk_bf16(r0, r1);
-                lq[e] = wn_pk_bf16(r0 - wn_bits_f32(mq[e] << 16), r1 - wn_bits_f32(mq[e] & 0xffff0000u));
-            }
-            wn_f4 bf[3];
-            bf[0].x = wn_bits_f32(hq[0]); bf[0].y = wn_bits_f32(hq[1]); bf[0].z = wn_bits_f32(hq[2]); bf[0].w = wn_bits_f32(hq[3]);
-            bf[1].x = wn_bits_f32(mq[0]); bf[1].y = wn_bits_f32(mq[1]); bf[1].z = wn_bits_f32(mq[2]); bf[1].w = wn_bits_f32(mq[3]);
-            bf[2].x = wn_bits_f32(lq[0]); bf[2].y = wn_bits_f32(lq[1]); bf[2].z = wn_bits_f32(lq[2]); bf[2].w = wn_bits_f32(lq[3]);
-            const char* Wl = W + (2 * q + blk) * 6144 + wn_frag_off(li, hi);
-            wn_f4 af[2][3];
-            WN_UNROLL
-            for (int rt = 0; rt < 2; ++rt) {
-                WN_UNROLL
-                for (int p = 0; p < 3; ++p) af[rt][p] = *reinterpret_cast<const wn_f4*>(Wl + p * 2048 + rt * 1024);
-            }
-            constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};  // small terms first
-            WN_UNROLL
-            for (int t = 0; t < 6; ++t) {
-                acc[0] = mfma_bf16(af[0][PA[t]], bf[PB[t]], acc[0]);
-                acc[1] = mfma_bf16(af[1][PA[t]], bf[PB[t]], acc[1]);
-            }
-        }
+        int sg, c0;
+        locate(q, sg, c0);
+        Arith::consume(smem_raw, a, q, sg, c0, xr, okr, acc);
     };
 
     int tile_v = walk.first;
@@ -1544,80 +1544,29 @@ __global__ __launch_bounds__(WN_LB) void k_conv64s(ConvArgs a) {
                 WN_SCHED_BARRIER();
             }
         }
-        if (MODE == 2) {
-            // gate backward + the partial sums of the aux gradient (wn_fused.h): every lane takes part in the
-            // cross-lane sums, lanes past T carry dP = 0 (their operands were zero).
-            const int tc = inb ? t : 0;
-            const int fr = tc / a.U;
-            const float wj = inb ? a.upw[tc - fr * a.U] : 0.0f;
-            const int F4 = a.F * 4;
-            const int H = T >> 4;  // 16-sample groups per channel row
-            const wn_rsrc_t Or = wn_make_buf(a.out + (long)b * 128 * T, (unsigned)(128 * T4));
-            const wn_rsrc_t Gr = wn_make_buf(a.G + (long)b * a.g_bstride, (unsigned)(128 * F4));
-            const wn_rsrc_t Dr = wn_make_buf(a.dGp + (long)b * 128 * H, (unsigned)(128 * H * 4));
-            const int vg = (4 * hi * a.F + fr) * 4;
-            const int l16 = li & 15;
-            const int h16 = (((tile - b * tiles_per_b) * 32) >> 4) + (li >> 4);
-            float qsum = 0.0f;
+        if constexpr (MODE != 1) {
+            const GateEpi ge = {a.out, a.gz, a.G, a.g_bstride, a.upw, a.U, a.F, a.dGp, a.qp, nullptr};
+            bwd_gate_epilogue<MODE == 2, false, false>(ge, acc, e0, e1, T, tiles_per_b, b, tile - b * tiles_per_b, t, inb, vst);
+        } else {
+            const wn_rsrc_t Or = wn_make_buf(a.out + (long)b * 64 * T, (unsigned)(64 * T4));
             WN_UNROLL
             for (int q = 0; q < 2; ++q) {
-                float ga[16], gg[16];
                 WN_UNROLL
                 for (int r = 0; r < 16; ++r) {
-                    ga[r] = wn_buf_load(Gr, vg, (32 * q + mfma32_row(r, 0)) * F4);
-                    gg[r] = wn_buf_load(Gr, vg, (64 + 32 * q + mfma32_row(r, 0)) * F4);
-                }
-                float keep_a = 0.0f, keep_g = 0.0f;
-                WN_UNROLL
-                for (int r = 0; r < 16; ++r) {
-                    const int so = (32 * q + mfma32_row(r, 0)) * T4;
-                    const float s = e0[q][r], g = a.gz ? e1[q][r] * wn_rcp(e0[q][r]) : e1[q][r], dz = inb ? acc[q][r] : 0.0f;
-                    const float dpa = dz * g * (s * (1.0f - s)), dpg = dz * s * (1.0f - g * g);
-                    wn_buf_store(Or, dpa, vst, so);   // lanes past T: out-of-range offset, dropped (no branch per element)
-                    wn_buf_store(Or, dpg, vst, so + 64 * T4);
-                    qsum += dpa * ga[r] + dpg * gg[r];
-                    const float ra = wn_row16_sum(wj * dpa), rg = wn_row16_sum(wj * dpg);
-                    keep_a = (l16 == r) ? ra : keep_a;
-                    keep_g = (l16 == r) ? rg : keep_g;
-                }
-                // lane l16 of each 16-lane group keeps the sums of channel row 32q + mfma32_row(l16, hi)
-                const int row = 32 * q + mfma32_row(l16, hi);
-                const int doff = (h16 < H) ? (row * H + h16) * 4 : 0x7ffffff0;
-                wn_buf_store(Dr, keep_a, doff, 0);
-                wn_buf_store(Dr, keep_g, doff, (h16 < H) ? 64 * H * 4 : 0);
-            }
-            qsum += __shfl_xor(qsum, 32, 64);  // the two lane halves hold complementary channel rows
-            if (hi == 0 && inb) a.qp[(long)b * T + t] = qsum;
-        } else {
-            if (MODE == 0) {
-                // gate backward: dP = [dZ*g*s*(1-s) ; dZ*s*(1-g^2)]
-                const wn_rsrc_t Or = wn_make_buf(a.out + (long)b * 128 * T, (unsigned)(128 * T4));
-                WN_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    WN_UNROLL
-                    for (int r = 0; r < 16; ++r) {
-                        const int so = (32 * q + mfma32_row(r, 0)) * T4;
-                        const float s = e0[q][r], g = a.gz ? e1[q][r] * wn_rcp(e0[q][r]) : e1[q][r], dz = acc[q][r];
-                        wn_buf_store(Or, dz * g * (s * (1.0f - s)), vst, so);
-                        wn_buf_store(Or, dz * s * (1.0f - g * g), vst, so + 64 * T4);
-                    }
-                }
-            } else {
-                const wn_rsrc_t Or = wn_make_buf(a.out + (long)b * 64 * T, (unsigned)(64 * T4));
-                WN_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    WN_UNROLL
-                    for (int r = 0; r < 16; ++r) {
-                        float v = acc[q][r];
-                        if (a.resid != nullptr) v += e0[q][r];
-                        wn_buf_store(Or, v, vst, (32 * q + mfma32_row(r, 0)) * T4);
-                    }
+                    float v = acc[q][r];
+                    if (a.resid != nullptr) v += e0[q][r];
+                    wn_buf_store(Or, v, vst, (32 * q + mfma32_row(r, 0)) * T4);
                 }
             }
         }
         tile_v = next_v;
     }
 }
+
+template <int MODE>
+__global__ __launch_bounds__(WN_LB) void k_conv64(ConvArgs a) { conv64_tiles<MODE, ConvF32>(a); }
+template <int MODE>
+__global__ __launch_bounds__(WN_LB) void k_conv64s(ConvArgs a) { conv64_tiles<MODE, ConvBf16x3>(a); }
 
 template <int MODE>
 static int launch_conv64(const ConvArgs& a, int split, wn_stream_t st) {
@@ -1629,7 +1578,7 @@ static int launch_conv64(const ConvArgs& a, int split, wn_stream_t st) {
         WN_LAUNCH((k_conv64s<MODE>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
         return 0;
     }
-    if constexpr (MODE != 2) {  // the aux-partial epilogue exists in the split kernel only
+    if constexpr (MODE != 2) {  // the aux-partial epilogue is built on the split arithmetic only
         const size_t lds = (size_t)a.wfloats * sizeof(float);
         if (wn_dyn_lds<k_conv64<MODE>>(lds)) return 1;
         WN_LAUNCH((k_conv64<MODE>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
@@ -1642,25 +1591,32 @@ int wn_fused_gate_split_supported(int Sch) {
     return Sch % 32 == 0 && (size_t)(Sch / 32 + 2) * 2 * 6144 <= 160 * 1024;   // launch_conv64's split LDS, with the res segment
 }
 
-int wn_fused_bwd_gate(const float* wskip, const float* wres, const float* dSk, const float* dXn, const float* S, const float* Gt,
-                      int gt_is_z, float* dP, int B, int T, int Sch, int split, wn_stream_t st) {
-    WN_PROF("fused_bwd_gate", 2.0 * (double)B * T * 64.0 * (Sch + (dXn ? 64.0 : 0.0)),
-            4.0 * (double)B * T * (Sch + (dXn ? 64.0 : 0.0) + 4.0 * 64.0), st);  // dSk (, dXn), S, Gt in; dP out
+// what the aux-gradient partial sums need: whole 16-sample groups inside one frame, frames that tile T
+static bool aux_shape_ok(int U, int F, int T) { return U >= 16 && !(U & 15) && !(T & 15) && (long)U * F == T; }
+
+// the skip (and, with dXn, res) contraction in front of gate'
+static ConvArgs gate_conv_args(const float* wskip, const float* wres, const float* dSk, const float* dXn, const float* S,
+                               const float* Gt, int gt_is_z, float* dP, int B, int T, int Sch) {
     ConvArgs a;
     a.nseg = 1;
-    a.seg[0].src = dSk; a.seg[0].w = wskip; a.seg[0].nch = Sch; a.seg[0].shift = 0; a.seg[0].woff = 0;
+    a.seg[0].src = dSk; a.seg[0].w = wskip; a.seg[0].nch = Sch;
     a.wfloats = Sch * 64;
     a.nchunks = Sch / 32;
     if (dXn) {
-        a.seg[1].src = dXn; a.seg[1].w = wres; a.seg[1].nch = 64; a.seg[1].shift = 0; a.seg[1].woff = Sch * 64;
+        a.seg[1].src = dXn; a.seg[1].w = wres; a.seg[1].nch = 64; a.seg[1].woff = Sch * 64;
         a.nseg = 2;
         a.wfloats += 64 * 64;
         a.nchunks += 2;
     }
-    a.B = B; a.T = T; a.S = S; a.Gt = Gt; a.gz = gt_is_z; a.resid = nullptr; a.out = dP;
-    a.interleave = 0;
-    a.G = nullptr; a.g_bstride = 0; a.upw = nullptr; a.U = 0; a.F = 0; a.dGp = nullptr; a.qp = nullptr;
-    return launch_conv64<0>(a, split, st);
+    a.B = B; a.T = T; a.S = S; a.Gt = Gt; a.gz = gt_is_z; a.out = dP;
+    return a;
+}
+
+int wn_fused_bwd_gate(const float* wskip, const float* wres, const float* dSk, const float* dXn, const float* S, const float* Gt,
+                      int gt_is_z, float* dP, int B, int T, int Sch, int split, wn_stream_t st) {
+    WN_PROF("fused_bwd_gate", 2.0 * (double)B * T * 64.0 * (Sch + (dXn ? 64.0 : 0.0)),
+            4.0 * (double)B * T * (Sch + (dXn ? 64.0 : 0.0) + 4.0 * 64.0), st);  // dSk (, dXn), S, Gt in; dP out
+    return launch_conv64<0>(gate_conv_args(wskip, wres, dSk, dXn, S, Gt, gt_is_z, dP, B, T, Sch), split, st);
 }
 
 int wn_fused_bwd_gate_aux(const float* wskip, const float* wres, const float* dSk, const float* dXn, const float* S,
@@ -1668,20 +1624,8 @@ int wn_fused_bwd_gate_aux(const float* wskip, const float* wres, const float* dS
                           float* dGp, float* qp, int B, int T, int Sch, wn_stream_t st) {
     WN_PROF("fused_bwd_gate", 2.0 * (double)B * T * 64.0 * (Sch + (dXn ? 64.0 : 0.0)),
             4.0 * (double)B * T * (Sch + (dXn ? 64.0 : 0.0) + 4.0 * 64.0 + 9.0), st);  // + dGp (8/timestep) and qp (1) out
-    if (U < 16 || (U & 15) || (T & 15) || (long)U * F != T) return 1;
-    ConvArgs a;
-    a.nseg = 1;
-    a.seg[0].src = dSk; a.seg[0].w = wskip; a.seg[0].nch = Sch; a.seg[0].shift = 0; a.seg[0].woff = 0;
-    a.wfloats = Sch * 64;
-    a.nchunks = Sch / 32;
-    if (dXn) {
-        a.seg[1].src = dXn; a.seg[1].w = wres; a.seg[1].nch = 64; a.seg[1].shift = 0; a.seg[1].woff = Sch * 64;
-        a.nseg = 2;
-        a.wfloats += 64 * 64;
-        a.nchunks += 2;
-    }
-    a.B = B; a.T = T; a.S = S; a.Gt = Gt; a.gz = gt_is_z; a.resid = nullptr; a.out = dP;
-    a.interleave = 0;
+    if (!aux_shape_ok(U, F, T)) return 1;
+    ConvArgs a = gate_conv_args(wskip, wres, dSk, dXn, S, Gt, gt_is_z, dP, B, T, Sch);
     a.G = G; a.g_bstride = g_bstride; a.upw = upw; a.U = U; a.F = F; a.dGp = dGp; a.qp = qp;
     return launch_conv64<2>(a, 1, st);
 }
@@ -1702,19 +1646,18 @@ int wn_fused_bwd_dx(const float* wd_b, const float* dP, const float* dXn, float*
     }
     a.wfloats = K * 128 * 64;
     a.nchunks = K * 4;
-    a.B = B; a.T = T; a.S = nullptr; a.Gt = nullptr; a.gz = 0; a.resid = dXn; a.out = dX;
+    a.B = B; a.T = T; a.resid = dXn; a.out = dX;
     // The taps of one 32-channel group are consumed back to back: position p is read as tap K-1 by the wave of its
     // own tile and as an earlier tap by the wave d samples away, and with [tap][channel] order those two reads of the
     // same lines were half a tile period apart -- longer than a line survives in the XCD's 4 MB L2 under the
     // kernel's write stream, so the second tap came over the fabric again (PMC: 253 MB per launch for 189 compulsory).
     // measured: 56.3 -> 53.0 us per launch (profiles/r01/tap_probe.txt)
     a.interleave = (K > 1) ? 1 : 0;
-    a.G = nullptr; a.g_bstride = 0; a.upw = nullptr; a.U = 0; a.F = 0; a.dGp = nullptr; a.qp = nullptr;
     return launch_conv64<1>(a, split, st);
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_chain64s -- one launch per layer of the backward data chain (split arithmetic, K <= 2):
+// k_chain64s -- one launch per layer of the backward data chain (split arithmetic):
 //     dX_l[t]     = dX_{l+1}[t] + sum_tap Wd_tap^T dP_l[t + (K-1-tap) d]                    (wavenet.py:527-528 reversed)
 //     dZ_{l-1}[t] = dZs_{l-1}[t] + Wres_{l-1}^T dX_l[t]                                      (wavenet.py:533-535 reversed)
 //     dP_{l-1}[t] = [dZ g s (1-s) ; dZ s (1-g^2)]                                            (wavenet.py:529-532 reversed)
@@ -1725,43 +1668,35 @@ int wn_fused_bwd_dx(const float* wd_b, const float* dP, const float* dXn, float*
 // split form is that the skip part of dZ arrives pre-contracted: dZs = Wskip_l^T dSkip for ALL layers is one matrix-bound
 // contraction per step (wn_api.hip), so this kernel reads 64 channels of it instead of the 256 of dSkip and needs no
 // Wskip: taps K x 128 x 64 + Wres^T 64 x 64 = 120 KB of bf16 fragments for K = 2.
-// AUX = 1 adds the aux-gradient partial sums of wn_fused_bwd_gate_aux to the gate epilogue (same arithmetic, same order).
+// AUX = 1 adds the aux-gradient partial sums of wn_fused_bwd_gate_aux to the gate epilogue (bwd_gate_epilogue).
 // ---------------------------------------------------------------------------------------------
 struct ChainArgs {
-    const float* img_taps;  // pre-built LDS images of the tap weights (layer l) and of Wres^T (layer l-1), or NULL
-    const float* img_res;
-    const float* wd_b;   // [tap][128][64]: W_tap^T, row = dP channel, col = dX channel   (layer l)
-    const float* dP;     // (B, 128, T) of layer l
-    const float* dXn;    // (B, 64, T) dX_{l+1}; NULL for the last layer (its residual output is dead)
-    float* dX;           // (B, 64, T) out
-    const float* wres;   // natural res_1x1 weight of layer l-1: [o][i] = [k][row]
-    const float* dZs;    // skip part of dZ_{l-1}: rows [0, 64) at dZs + b * zs_bstride, row stride T
-    long zs_bstride;
-    int zs_t0;           // dZs is zero (and was never written) in front of this position: the loss window of wn_backward_window
-    const float* S;      // (B, 64, T) sigmoid / tanh halves of layer l-1 (saved by the forward)
-    const float* Gt;     // with gz != 0: the saved product z = s * tanh instead of the tanh half (g = z / s)
-    int gz;
-    float* dPm;          // (B, 128, T) out: dP_{l-1}
-    int B, T, K, dil;
-    // AUX
-    const float* G;      // (B, g_bstride) frame-rate aux projection of layer l-1, rows [0,128)
-    long g_bstride;
-    const float* upw;    // [U]
-    int U, F;
-    float* dGp;          // (B, 128, T/16)
-    float* qp;           // (B, T)
+    const float* img_taps = nullptr;  // pre-built LDS images of the tap weights (layer l) and of Wres^T (layer l-1), or NULL
+    const float* img_res = nullptr;
+    const float* wd_b = nullptr;   // [tap][128][64]: W_tap^T, row = dP channel, col = dX channel   (layer l)
+    const float* dP = nullptr;     // (B, 128, T) of layer l
+    const float* dXn = nullptr;    // (B, 64, T) dX_{l+1}; NULL for the last layer (its residual output is dead)
+    float* dX = nullptr;           // (B, 64, T) out
+    const float* wres = nullptr;   // natural res_1x1 weight of layer l-1: [o][i] = [k][row]
+    const float* dZs = nullptr;    // skip part of dZ_{l-1}: rows [0, 64) at dZs + b * zs_bstride, row stride T
+    long zs_bstride = 0;
+    int zs_t0 = 0;                 // dZs is zero (and was never written) in front of this position: the loss window of wn_backward_window
+    const float* S = nullptr;      // (B, 64, T) sigmoid / tanh halves of layer l-1 (saved by the forward)
+    const float* Gt = nullptr;     // with gz != 0: the saved product z = s * tanh instead of the tanh half (g = z / s)
+    int gz = 0;
+    float* dPm = nullptr;          // (B, 128, T) out: dP_{l-1}
+    int B = 0, T = 0, K = 1, dil = 1;
+    // AUX (see GateEpi)
+    const float* G = nullptr;
+    long g_bstride = 0;
+    const float* upw = nullptr;
+    int U = 0, F = 0;
+    float* dGp = nullptr;
+    float* qp = nullptr;
     // H16 (fp16 pair split, block-scaled): img_taps / img_res are the two-piece images of wn_fused_pack_images16
-    const float* amaxP;  // (B, tiles) max |dP_l| of every 32-sample tile, written by the launch that produced dP_l
-    float* amaxPm;       // (B, tiles) out: max |dP_{l-1}| per tile (nullable)
+    const float* amaxP = nullptr;  // (B, tiles) max |dP_l| of every 32-sample tile, written by the launch that produced dP_l
+    float* amaxPm = nullptr;       // (B, tiles) out: max |dP_{l-1}| per tile (nullable)
 };
-
-// 8 fp32 values -> the three bf16 pieces of the lane's share of a 16-k block
-static __device__ __forceinline__ void split8v(const float (&x)[8], bool ok, wn_f4 (&bf)[3]) {
-    float y[8];
-    WN_UNROLL
-    for (int e = 0; e < 8; ++e) y[e] = ok ? x[e] : 0.0f;
-    split8(y, bf);
-}
 
 // HEAD = true: the top of the chain.  The last layer's residual output is dead (wavenet.py:231-238), so dP_{L-1} is the gate'
 // epilogue alone on dZs_{L-1} (which bwd_dz_skip_all now produces for ALL layers): no taps, no Wres^T, no dX -- its own
@@ -1775,16 +1710,15 @@ static __device__ __forceinline__ void split8v(const float (&x)[8], bool ok, wn_
 template <int AUX, int K, bool HEAD = false, bool H16 = false>
 __global__ __launch_bounds__(WN_LB) void k_chain64s(ChainArgs a) {
     WN_DYN_SMEM(smem_raw);
-    char* W = smem_raw;                      // tap blocks: chunk q (32 channels) = tap q % K, channel group q / K; 2 blocks of 6 KB each
+    char* W = smem_raw;                      // tap blocks: chunk q (32 channels) = tap q % K, channel group q / K; 2 blocks each
     constexpr int NCH = K * 4;               // chunks of the dX part
-    constexpr int BLKB = H16 ? 4096 : 6144;  // bytes of one [piece][64 rows][16 k] block
-    constexpr int PCB = 2048;                // ... of one piece of it
+    constexpr int BLKB = H16 ? 4096 : 6144;  // bytes of one [piece][64 rows][16 k] block (pieces of 2 KB)
     char* Wr = W + NCH * 2 * BLKB;           // Wres^T: 4 blocks [piece][64 rows][16 k], k order = accumulator register order
     // K = 3: the taps alone fill the LDS (144 KB); the Wres^T fragments (24 KB, L2 resident) are read from the pre-split image
     // in global memory, one 16-k block ahead of their MFMAs (the launcher only takes K = 3 with images)
     constexpr bool RG = (K >= 3) && !H16;
     float inv_wd = 1.0f, inv_wr = 1.0f;
-    (void)inv_wd; (void)inv_wr; (void)PCB;
+    (void)inv_wd; (void)inv_wr;
     if (HEAD) {
         // no weights
     } else if (H16) {
@@ -1813,6 +1747,7 @@ __global__ __launch_bounds__(WN_LB) void k_chain64s(ChainArgs a) {
     const int ntiles = a.B * tiles_per_b;
     const TileWalk walk = tile_walk(ntiles, threadIdx.x >> 6);
     const int step = walk.step, tile_end = walk.end;
+    const int vfrag = wn_frag_off(li, hi);
 
     float xa[16], xb[16];
     bool oka = false, okb = false;
@@ -1831,46 +1766,7 @@ __global__ __launch_bounds__(WN_LB) void k_chain64s(ChainArgs a) {
     };
     f32x16 acc[2];
     float s_dp = 1.0f;   // H16: block scale of this tile's dP operand
-    auto consume = [&](int q, const float (&xr)[16], bool okr) {
-        WN_UNROLL
-        for (int blk = 0; blk < 2; ++blk) {
-            float x8[8];
-            WN_UNROLL
-            for (int e = 0; e < 8; ++e) x8[e] = H16 ? (okr ? xr[8 * blk + e] : 0.0f) : xr[8 * blk + e];
-            const char* Wl = W + (2 * q + blk) * BLKB + wn_frag_off(li, hi);
-            if constexpr (H16) {
-                wn_f4 bf[2];
-                split8h(x8, s_dp, bf);
-                wn_f4 af[2][2];
-                WN_UNROLL
-                for (int rt = 0; rt < 2; ++rt) {
-                    WN_UNROLL
-                    for (int p = 0; p < 2; ++p) af[rt][p] = *reinterpret_cast<const wn_f4*>(Wl + p * PCB + rt * 1024);
-                }
-                constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};   // small terms first: h l, l h, h h
-                WN_UNROLL
-                for (int t3 = 0; t3 < 3; ++t3) {
-                    acc[0] = mfma_f16(af[0][PA[t3]], bf[PB[t3]], acc[0]);
-                    acc[1] = mfma_f16(af[1][PA[t3]], bf[PB[t3]], acc[1]);
-                }
-            } else {
-                wn_f4 bf[3];
-                split8v(x8, okr, bf);
-                wn_f4 af[2][3];
-                WN_UNROLL
-                for (int rt = 0; rt < 2; ++rt) {
-                    WN_UNROLL
-                    for (int p = 0; p < 3; ++p) af[rt][p] = *reinterpret_cast<const wn_f4*>(Wl + p * 2048 + rt * 1024);
-                }
-                constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};  // small terms first
-                WN_UNROLL
-                for (int t6 = 0; t6 < WN_EXP_NPROD; ++t6) {
-                    acc[0] = mfma_bf16(af[0][PA[t6]], bf[PB[t6]], acc[0]);
-                    acc[1] = mfma_bf16(af[1][PA[t6]], bf[PB[t6]], acc[1]);
-                }
-            }
-        }
-    };
+    auto consume = [&](int q, const float (&xr)[16], bool okr) { split_chunk<H16>(W + 2 * q * BLKB + vfrag, xr, okr, s_dp, acc); };
 
     // H16: block scale of a tile's dP operand = the largest |dP_l| over the producer tiles its taps read (shift (K - 1 - tap) d
     // ahead: at most two tiles each), as the launch that wrote dP_l recorded them.  Looked up together with the tile's first
@@ -1910,9 +1806,8 @@ __global__ __launch_bounds__(WN_LB) void k_chain64s(ChainArgs a) {
         const int vzs = (t >= a.zs_t0) ? vst : WN_VOFF_DEAD;
         const int next_v = tile_v + step;
 
-        // The residual input dX_{l+1} is the INITIAL VALUE of the tap accumulators (loaded straight into them), and the
-        // pre-contracted skip part of dZ that of the second accumulator pair (requested in the middle of the taps).
-        // Lanes past T read a valid dummy address; their columns never leave the wave.
+        // dz: the pre-contracted skip part of dZ (requested in the middle of the taps), to which the res-1x1 transpose of dX
+        // is added.  Lanes past T read a valid dummy address; their columns never leave the wave.
         f32x16 dz[2];
         const wn_rsrc_t Ssr = wn_make_buf(a.S + (long)b * 64 * T, (unsigned)(64 * T4));
         const wn_rsrc_t Gsr = wn_make_buf(a.Gt + (long)b * 64 * T, (unsigned)(64 * T4));
@@ -2002,22 +1897,6 @@ __global__ __launch_bounds__(WN_LB) void k_chain64s(ChainArgs a) {
             // dX_l of this tile is finished in the accumulator layout: register r of lane (li, hi) = channel 32q + row(r, hi)
             WN_SCHED_BARRIER();
             // dZ += Wres^T dX: k-step e of block kb takes accumulator register 8 (kb & 1) + e of row tile kb >> 1
-            const wn_rsrc_t Ir = wn_make_buf(a.img_res, (unsigned)(RG ? WN_RES_T_BYTES : 16));
-            const int vfrag = wn_frag_off(li, hi);
-            auto res_frags = [&](int kb, wn_f4 (&af)[2][3]) {
-                WN_UNROLL
-                for (int rt = 0; rt < 2; ++rt) {
-                    WN_UNROLL
-                    for (int p = 0; p < 3; ++p) {
-                        if (RG) {
-                            const float4 f = wn_buf_load4(Ir, vfrag, (unsigned)(kb * 6144 + p * 2048 + rt * 1024));
-                            af[rt][p] = wn_f4{f.x, f.y, f.z, f.w};
-                        } else {
-                            af[rt][p] = *reinterpret_cast<const wn_f4*>(Wr + kb * 6144 + vfrag + p * 2048 + rt * 1024);
-                        }
-                    }
-                }
-            };
             if constexpr (H16) {
                 // dX operand: its own wave-wide maximum decides the block scale; the skip part dZs (true scale, loaded into dz) is
                 // added by the fma that scales the products back
@@ -2032,7 +1911,6 @@ __global__ __launch_bounds__(WN_LB) void k_chain64s(ChainArgs a) {
                 f32x16 dzm[2];
                 dzm[0] = f32x16_zero();
                 dzm[1] = f32x16_zero();
-                constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};
                 WN_UNROLL
                 for (int kb = 0; kb < 4; ++kb) {
                     float x8[8];
@@ -2041,16 +1919,8 @@ __global__ __launch_bounds__(WN_LB) void k_chain64s(ChainArgs a) {
                     wn_f4 bf[2];
                     split8h(x8, s_dx, bf);
                     wn_f4 af[2][2];
-                    WN_UNROLL
-                    for (int rt = 0; rt < 2; ++rt) {
-                        WN_UNROLL
-                        for (int p = 0; p < 2; ++p) af[rt][p] = *reinterpret_cast<const wn_f4*>(Wr + kb * BLKB + vfrag + p * PCB + rt * 1024);
-                    }
-                    WN_UNROLL
-                    for (int t3 = 0; t3 < 3; ++t3) {
-                        dzm[0] = mfma_f16(af[0][PA[t3]], bf[PB[t3]], dzm[0]);
-                        dzm[1] = mfma_f16(af[1][PA[t3]], bf[PB[t3]], dzm[1]);
-                    }
+                    lds_frags(Wr + kb * BLKB + vfrag, af);
+                    products3(af, bf, dzm[0], dzm[1]);
                 }
                 const float invz = inv_wr / s_dx;
                 WN_UNROLL
@@ -2059,23 +1929,19 @@ __global__ __launch_bounds__(WN_LB) void k_chain64s(ChainArgs a) {
                     for (int r = 0; r < 16; ++r) dz[qq][r] = fmaf(dzm[qq][r], invz, dz[qq][r]);
                 }
             } else {
-            wn_f4 afr[2][2][3];
-            res_frags(0, afr[0]);
-            WN_UNROLL
-            for (int kb = 0; kb < 4; ++kb) {
-                float x8[8];
+                const wn_rsrc_t Ir = wn_make_buf(a.img_res, (unsigned)(RG ? WN_RES_T_BYTES : 16));
+                wn_f4 afr[2][2][3];   // two sets: with RG the fragments of block kb + 1 are in flight under the MFMAs of block kb
+                res_frags<RG>(Wr, Ir, 0u, vfrag, 0, afr[0]);
                 WN_UNROLL
-                for (int e = 0; e < 8; ++e) x8[e] = acc[kb >> 1][8 * (kb & 1) + e];
-                wn_f4 bf[3];
-                split8(x8, bf);
-                if (kb + 1 < 4) res_frags(kb + 1, afr[(kb + 1) & 1]);
-                constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-                WN_UNROLL
-                for (int t6 = 0; t6 < WN_EXP_NPROD; ++t6) {
-                    dz[0] = mfma_bf16(afr[kb & 1][0][PA[t6]], bf[PB[t6]], dz[0]);
-                    dz[1] = mfma_bf16(afr[kb & 1][1][PA[t6]], bf[PB[t6]], dz[1]);
+                for (int kb = 0; kb < 4; ++kb) {
+                    float x8[8];
+                    WN_UNROLL
+                    for (int e = 0; e < 8; ++e) x8[e] = acc[kb >> 1][8 * (kb & 1) + e];
+                    wn_f4 bf[3];
+                    split8(x8, bf);
+                    if (kb + 1 < 4) res_frags<RG>(Wr, Ir, 0u, vfrag, kb + 1, afr[(kb + 1) & 1]);
+                    products6(afr[kb & 1], bf, dz[0], dz[1]);
                 }
-            }
             }
             WN_SCHED_BARRIER();
             // the next tile's first operand chunks go out before this tile's stores (vmcnt counts loads and stores in order)
@@ -2095,83 +1961,39 @@ __global__ __launch_bounds__(WN_LB) void k_chain64s(ChainArgs a) {
         }
         WN_SCHED_BARRIER();  // the dX registers are free from here on
         WN_PRIO(WN_PRIO_GATE);
-        const wn_rsrc_t Or = wn_make_buf(a.dPm + (long)b * 128 * T, (unsigned)(128 * T4));
-        if (AUX) {
-            // gate backward + the partial sums of the aux gradient (as k_conv64s<2>): every lane takes part in the
-            // cross-lane sums, lanes past T carry dP = 0
-            const int tc = inb ? t : 0;
-            const int fr = tc / a.U;
-            const float wj = inb ? a.upw[tc - fr * a.U] : 0.0f;
-            const int F4 = a.F * 4;
-            const int H = T >> 4;  // 16-sample groups per channel row
-            const wn_rsrc_t Gr = wn_make_buf(a.G + (long)b * a.g_bstride, (unsigned)(128 * F4));
-            const wn_rsrc_t Dr = wn_make_buf(a.dGp + (long)b * 128 * H, (unsigned)(128 * H * 4));
-            const int vg = (4 * hi * a.F + fr) * 4;
-            const int l16 = li & 15;
-            const int h16 = (((tile - b * tiles_per_b) * 32) >> 4) + (li >> 4);
-            float qsum = 0.0f;
-            float pmax = 0.0f;
-            (void)pmax;
-            WN_UNROLL
-            for (int q = 0; q < 2; ++q) {
-                float ga[16], gg[16];
-                WN_UNROLL
-                for (int r = 0; r < 16; ++r) {
-                    ga[r] = wn_buf_load(Gr, vg, (32 * q + mfma32_row(r, 0)) * F4);
-                    gg[r] = wn_buf_load(Gr, vg, (64 + 32 * q + mfma32_row(r, 0)) * F4);
-                }
-                float keep_a = 0.0f, keep_g = 0.0f;
-                WN_UNROLL
-                for (int r = 0; r < 16; ++r) {
-                    const int so = (32 * q + mfma32_row(r, 0)) * T4;
-                    const float s = e0[q][r], g = a.gz ? e1[q][r] * wn_rcp(e0[q][r]) : e1[q][r], dzv = inb ? dz[q][r] : 0.0f;
-                    const float dpa = dzv * g * (s * (1.0f - s)), dpg = dzv * s * (1.0f - g * g);
-                    wn_buf_store(Or, dpa, vst, so);   // lanes past T: out-of-range offset, dropped (no branch per element)
-                    wn_buf_store(Or, dpg, vst, so + 64 * T4);
-                    if (H16) pmax = fmaxf(pmax, fmaxf(fabsf(dpa), fabsf(dpg)));
-                    qsum += dpa * ga[r] + dpg * gg[r];
-                    const float ra = wn_row16_sum(wj * dpa), rg = wn_row16_sum(wj * dpg);
-                    keep_a = (l16 == r) ? ra : keep_a;
-                    keep_g = (l16 == r) ? rg : keep_g;
-                }
-                const int row = 32 * q + mfma32_row(l16, hi);
-                const int doff = (h16 < H) ? (row * H + h16) * 4 : 0x7ffffff0;
-                wn_buf_store(Dr, keep_a, doff, 0);
-                wn_buf_store(Dr, keep_g, doff, (h16 < H) ? 64 * H * 4 : 0);
-                WN_SCHED_BARRIER();  // one 32-row half at a time (register budget)
-            }
-            qsum += __shfl_xor(qsum, 32, 64);
-            if (hi == 0 && inb) a.qp[(long)b * T + t] = qsum;
-            if (H16 && a.amaxPm != nullptr) {
-                pmax = wave_reduce_max(pmax);
-                if (lane == 0) a.amaxPm[(long)b * tiles_per_b + (tile - b * tiles_per_b)] = pmax;
-            }
-        } else {
-            float pmax = 0.0f;
-            (void)pmax;
-            WN_UNROLL
-            for (int q = 0; q < 2; ++q) {
-                WN_UNROLL
-                for (int r = 0; r < 16; ++r) {
-                    const int so = (32 * q + mfma32_row(r, 0)) * T4;
-                    const float s = e0[q][r], g = a.gz ? e1[q][r] * wn_rcp(e0[q][r]) : e1[q][r], dzv = H16 ? (inb ? dz[q][r] : 0.0f) : dz[q][r];
-                    const float dpa = dzv * g * (s * (1.0f - s)), dpg = dzv * s * (1.0f - g * g);
-                    wn_buf_store(Or, dpa, vst, so);
-                    wn_buf_store(Or, dpg, vst, so + 64 * T4);
-                    if (H16) pmax = fmaxf(pmax, fmaxf(fabsf(dpa), fabsf(dpg)));
-                }
-            }
-            if (H16 && a.amaxPm != nullptr) {
-                pmax = wave_reduce_max(pmax);
-                if (lane == 0) a.amaxPm[(long)b * tiles_per_b + (tile - b * tiles_per_b)] = pmax;
-            }
-        }
+        const GateEpi ge = {a.dPm, a.gz, a.G, a.g_bstride, a.upw, a.U, a.F, a.dGp, a.qp, a.amaxPm};
+        bwd_gate_epilogue<AUX != 0, H16, true>(ge, dz, e0, e1, T, tiles_per_b, b, tile - b * tiles_per_b, t, inb, vst);
         tile_v = next_v;
     }
 }
 
 int wn_fused_chain_supported(int R, int K, int S) {
     return wn_fused_supported(R, K, S) && K >= 1 && K <= 3 && (size_t)(K * 8 + (K >= 3 ? 0 : 4)) * 6144 <= 160 * 1024;
+}
+
+template <int AUX, int K, bool HEAD, bool H16>
+static int launch_chain(const ChainArgs& a, long nblk, size_t lds, wn_stream_t st) {
+    if constexpr (!HEAD) {
+        if (wn_dyn_lds<k_chain64s<AUX, K, HEAD, H16>>(lds)) return 1;
+    }
+    WN_LAUNCH((k_chain64s<AUX, K, HEAD, H16>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);
+    return 0;
+}
+// the one dispatch on (aux, K, fp16 pair); the head has its K = 1 instantiations only
+template <bool HEAD, int AUX, bool H16>
+static int launch_chain_k(const ChainArgs& a, long nblk, size_t lds, wn_stream_t st) {
+    if constexpr (HEAD) return launch_chain<AUX, 1, true, H16>(a, nblk, lds, st);
+    else switch (a.K) {
+        case 1: return launch_chain<AUX, 1, false, H16>(a, nblk, lds, st);
+        case 2: return launch_chain<AUX, 2, false, H16>(a, nblk, lds, st);
+        case 3: return launch_chain<AUX, 3, false, H16>(a, nblk, lds, st);
+        default: return 1;
+    }
+}
+template <bool HEAD>
+static int dispatch_chain(const ChainArgs& a, bool aux, bool h16, long nblk, size_t lds, wn_stream_t st) {
+    if (aux) return h16 ? launch_chain_k<HEAD, 1, true>(a, nblk, lds, st) : launch_chain_k<HEAD, 1, false>(a, nblk, lds, st);
+    return h16 ? launch_chain_k<HEAD, 0, true>(a, nblk, lds, st) : launch_chain_k<HEAD, 0, false>(a, nblk, lds, st);
 }
 
 int wn_fused_bwd_chain(const float* wd_b, const float* dP, const float* dXn, float* dX, const float* wres_prev, const float* dZs,
@@ -2183,8 +2005,10 @@ int wn_fused_bwd_chain(const float* wd_b, const float* dP, const float* dXn, flo
     WN_PROF("fused_bwd_chain", 2.0 * (double)B * T * 64.0 * (K * 128.0 + 64.0),
             4.0 * (double)B * T * (128.0 + (dXn ? 64.0 : 0.0) + 64.0 + 128.0 + 64.0 + 128.0 + (aux ? 9.0 : 0.0)), st);
     if (K < 1 || K > 3) return 1;
-    if (aux && (U < 16 || (U & 15) || (T & 15) || (long)U * F != T)) return 1;
+    if (aux && !aux_shape_ok(U, F, T)) return 1;
     if (K == 3 && !(img_taps && img_res)) return 1;   // K = 3 reads the Wres^T fragments from the image
+    const bool h16 = amaxP != nullptr;   // fp16 pair split: img_taps / img_res are the two-piece images (wn_fused_pack_images16)
+    if (h16 && (!img_taps || !img_res)) return 1;
     ChainArgs a;
     a.img_taps = (img_taps && img_res) ? img_taps : nullptr; a.img_res = img_res;
     a.wd_b = wd_b; a.dP = dP; a.dXn = dXn; a.dX = dX;
@@ -2192,72 +2016,27 @@ int wn_fused_bwd_chain(const float* wd_b, const float* dP, const float* dXn, flo
     a.B = B; a.T = T; a.K = K; a.dil = dilation;
     a.G = G; a.g_bstride = g_bstride; a.upw = upw; a.U = U; a.F = F; a.dGp = dGp; a.qp = qp;
     a.amaxP = amaxP; a.amaxPm = amaxPm;
-    const long ntiles = (long)B * ((T + 31) / 32);
-    const long nblk = balanced_blocks(ntiles);
-    if (amaxP != nullptr) {   // fp16 pair split: img_taps / img_res are the two-piece images (wn_fused_pack_images16)
-        if (!img_taps || !img_res) return 1;
-        const size_t lds16 = (size_t)(K * 8 + 4) * 4096;
-#define WN_CHAIN_LAUNCH16(AUXV, KV)                                                                               \
-    do {                                                                                                          \
-        if (wn_dyn_lds<k_chain64s<AUXV, KV, false, true>>(lds16)) return 1;                                       \
-        WN_LAUNCH((k_chain64s<AUXV, KV, false, true>), dim3((unsigned)nblk), dim3(WN_FT), lds16, st, a);          \
-    } while (0)
-        if (aux) {
-            if (K == 1) WN_CHAIN_LAUNCH16(1, 1);
-            else if (K == 2) WN_CHAIN_LAUNCH16(1, 2);
-            else WN_CHAIN_LAUNCH16(1, 3);
-        } else {
-            if (K == 1) WN_CHAIN_LAUNCH16(0, 1);
-            else if (K == 2) WN_CHAIN_LAUNCH16(0, 2);
-            else WN_CHAIN_LAUNCH16(0, 3);
-        }
-#undef WN_CHAIN_LAUNCH16
-        return 0;
-    }
-    const size_t lds = (size_t)(K * 8 + (K >= 3 ? 0 : 4)) * 6144;
-#define WN_CHAIN_LAUNCH(AUXV, KV)                                                                       \
-    do {                                                                                                \
-        if (wn_dyn_lds<k_chain64s<AUXV, KV>>(lds)) return 1;                                            \
-        WN_LAUNCH((k_chain64s<AUXV, KV>), dim3((unsigned)nblk), dim3(WN_FT), lds, st, a);               \
-    } while (0)
-    if (aux) {
-        if (K == 1) WN_CHAIN_LAUNCH(1, 1);
-        else if (K == 2) WN_CHAIN_LAUNCH(1, 2);
-        else WN_CHAIN_LAUNCH(1, 3);
-    } else {
-        if (K == 1) WN_CHAIN_LAUNCH(0, 1);
-        else if (K == 2) WN_CHAIN_LAUNCH(0, 2);
-        else WN_CHAIN_LAUNCH(0, 3);
-    }
-#undef WN_CHAIN_LAUNCH
-    return 0;
+    const long nblk = balanced_blocks((long)B * ((T + 31) / 32));
+    const size_t lds = h16 ? (size_t)(K * 8 + 4) * 4096 : (size_t)(K * 8 + (K >= 3 ? 0 : 4)) * 6144;
+    return dispatch_chain<false>(a, aux, h16, nblk, lds, st);
 }
 
-// Top of the chain: dP_{L-1} = gate'(dZs_{L-1}) (k_chain64s<AUX, K, true>: no weights, no LDS, the epilogue only)
+// Top of the chain: dP_{L-1} = gate'(dZs_{L-1}) (k_chain64s<AUX, 1, true>: no weights, no LDS, the epilogue only)
 int wn_fused_bwd_chain_head(const float* dZs, long zs_bstride, const float* S, const float* Gt, int gt_is_z, float* dP_prev,
                             const float* G, long g_bstride, const float* upw, int U, int F, float* dGp, float* qp, int B, int T,
                             int zs_t0, float* amaxPm, wn_stream_t st) {
     const bool aux = dGp != nullptr;
     WN_PROF("fused_bwd_gate", 0.0, 4.0 * (double)B * T * (64.0 + 128.0 + 128.0 + (aux ? 9.0 : 0.0)), st);
-    if (aux && (U < 16 || (U & 15) || (T & 15) || (long)U * F != T)) return 1;
+    if (aux && !aux_shape_ok(U, F, T)) return 1;
     ChainArgs a;
-    a.img_taps = nullptr; a.img_res = nullptr; a.wd_b = nullptr; a.dP = nullptr; a.dXn = nullptr; a.dX = nullptr; a.wres = nullptr;
     a.dZs = dZs; a.zs_bstride = zs_bstride; a.zs_t0 = zs_t0; a.S = S; a.Gt = Gt; a.gz = gt_is_z; a.dPm = dP_prev;
-    a.B = B; a.T = T; a.K = 1; a.dil = 1;
+    a.B = B; a.T = T;
     a.G = G; a.g_bstride = g_bstride; a.upw = upw; a.U = U; a.F = F; a.dGp = dGp; a.qp = qp;
-    a.amaxP = nullptr; a.amaxPm = amaxPm;
+    a.amaxPm = amaxPm;
     const long ntiles = (long)B * ((T + 31) / 32);
     long nblk = (ntiles + WN_FW - 1) / WN_FW;   // one tile per wave up to 1024 workgroups (HBM-bound, nothing to amortise)
     if (nblk > 1024) nblk = 1024;
     if (nblk >= 8) nblk &= ~7L;                 // whole XCD rounds for the tile walk
-    if (amaxPm != nullptr) {   // the fp16 pair chain follows: also record max |dP| per tile
-        if (aux)
-            WN_LAUNCH((k_chain64s<1, 1, true, true>), dim3((unsigned)nblk), dim3(WN_FT), 0, st, a);
-        else
-            WN_LAUNCH((k_chain64s<0, 1, true, true>), dim3((unsigned)nblk), dim3(WN_FT), 0, st, a);
-    } else if (aux)
-        WN_LAUNCH((k_chain64s<1, 1, true>), dim3((unsigned)nblk), dim3(WN_FT), 0, st, a);
-    else
-        WN_LAUNCH((k_chain64s<0, 1, true>), dim3((unsigned)nblk), dim3(WN_FT), 0, st, a);
-    return 0;
+    // with amaxPm the fp16 pair chain follows: the H16 instantiation also records max |dP| per tile
+    return dispatch_chain<true>(a, aux, amaxPm != nullptr, nblk, 0, st);
 }

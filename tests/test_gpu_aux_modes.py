@@ -52,12 +52,18 @@ def test_aux_gradient_modes_agree_and_match_the_oracle():
 
 def test_chain_kernel_ragged_shapes():
     """The one-launch-per-layer backward chain on shapes the big cases do not have: a half-full last tile (T % 32 == 16),
-    three sequences, kernel_size 1, a single layer (head + tail only), no upsampling layer (aux partials fall back)."""
+    three sequences, kernel_size 1, a single layer (head + tail only), no upsampling layer (aux partials fall back).  The
+    rows behind the first six reach the instantiations of the chain kernel no other GPU test launches: kernel_size 1 without
+    the aux partial sums, kernel_size 1 on the fp16 pair split (WN_FLAG_CHAIN_F16PAIR) with and without them, and the fp16
+    pair split without them at kernel_size 2 and 3 (its head launch included)."""
     from pytorchwavenetvocoder_amd import _lib as L
-    A = L.FLAG_AUX_FUSED
-    for cfg_t, B, T, seed, flags in [((64, 6, 64, 32, 2, 2, 2, 16), 3, 80, 42, A), ((64, 6, 64, 32, 3, 1, 1, 16), 2, 48, 41, A),
+    A, C = L.FLAG_AUX_FUSED, L.FLAG_CHAIN_F16PAIR
+    K1, K2, K3 = (64, 6, 64, 32, 3, 1, 1, 16), (64, 6, 64, 32, 2, 2, 2, 16), (64, 6, 64, 32, 3, 1, 3, 16)
+    for cfg_t, B, T, seed, flags in [(K2, 3, 80, 42, A), (K1, 2, 48, 41, A),
                                      ((64, 6, 64, 32, 1, 1, 2, 16), 1, 32, 44, A), ((64, 6, 64, 64, 3, 2, 2, 0), 1, 70, 43, A),
-                                     ((64, 6, 64, 32, 2, 2, 2, 16), 3, 80, 42, 0), ((256, 8, 64, 128, 5, 2, 2, 16), 2, 304, 45, A)]:
+                                     (K2, 3, 80, 42, 0), ((256, 8, 64, 128, 5, 2, 2, 16), 2, 304, 45, A),
+                                     (K1, 2, 48, 41, 0), (K1, 2, 48, 41, A | C), (K1, 2, 48, 41, C), (K2, 3, 80, 42, C),
+                                     (K3, 3, 80, 46, C)]:
         e, g = PC.run_oracle_vs_engine(cfg_t, B, T, seed, _lib(), DEV, flags=flags, scale=0.2 if cfg_t[3] < 128 else 0.1)
         print("chain ragged", cfg_t, B, T, "logits %.3g grads %.3g" % (e, g))
 
