@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 15
+#define WN_ABI_VERSION 16
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -359,6 +359,30 @@ int wn_backward_dh(const WnConfig* cfg, int B, int T, const float* params, const
                    const float* dlogits, int t_first, float* grads, float* dh, void* ws, size_t ws_bytes, void* const* events,
                    int n_events, int layers_per_bucket, int flags, void* stream);
 
+/* wn_backward_dh for a model with frozen parameters (since ABI v16): the pass stops where no trainable parameter needs it.
+ *   first_layer   the lowest layer l whose own tensors (dil_*, aux_1x1_*, skip_1x1.l, res_1x1.l) include a trainable one; L when
+ *                 no layer tensor trains.  It must be 0 when dh != NULL, or when the front conv or the upsampling layer trains
+ *                 (both need every layer's data gradient) -- an error otherwise.
+ *   needs         WN_NEED_POST | WN_NEED_FRONT | WN_NEED_UP: the post-net, the front conv, the upsampling layer train.
+ * What is left out: the post-net weight gradients without WN_NEED_POST (and the two data contractions in front of them when
+ * first_layer == L as well); the data chain below first_layer, including the launch that would produce dX_{first_layer}
+ * (kept for first_layer == 0 with WN_NEED_FRONT); the weight-gradient groups below first_layer -- groups are counted from the top
+ * as in the full pass, so a group wholly at or above first_layer issues the full pass's launches with its split-K plan, and the
+ * lowest one is cut at first_layer; the front-conv gradient and the upsampling reductions without their bits.  The two
+ * all-layers contractions (the skip part of dZ, and skip_1x1 where it is one launch) keep all L layers while any layer is
+ * computed and fall away with first_layer == L: their plans follow the row / column count, and the computed layers keep the
+ * full pass's bits this way.  Nothing is left out inside a computed layer.  Every bucket event is still
+ * recorded, in order (a bucket whose layers were all left out: where the walk would have reached it).
+ * The gradient buffer: ranges of tensors outside what was asked for hold UNSPECIFIED values (written or not).
+ * first_layer = 0 with WN_NEED_ALL is wn_backward_dh, launch for launch. */
+#define WN_NEED_POST 1
+#define WN_NEED_FRONT 2
+#define WN_NEED_UP 4
+#define WN_NEED_ALL 7
+int wn_backward_needs(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                      const float* dlogits, int t_first, float* grads, float* dh, void* ws, size_t ws_bytes, void* const* events,
+                      int n_events, int layers_per_bucket, int flags, void* stream, int first_layer, int needs);
+
 /* torch.optim.Adam step over the flat buffers (reference train.py:457-460,539): L2-in-gradient
  * weight decay, bias correction with `step` (1-based); [skip_lo, skip_hi) is left untouched. */
 int wn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step,
@@ -427,6 +451,39 @@ int wn_adam_step_ema(float* params, const float* grads, float* exp_avg, float* e
 int wn_adam_step_guarded_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float eps,
                              float weight_decay, int64_t skip_lo, int64_t skip_hi, const WnOptState* state, double ema_decay,
                              int ema_warmup, void* stream);
+
+/* ---- training with frozen parameters: the norm and the Adam step over LIVE RANGES (since ABI v16; additions only) ----
+ * A model with frozen parameters updates some ranges of its flat buffers and must leave the rest alone -- weights, both moments
+ * and the moving average bit for bit, with no weight decay -- whatever the gradient buffer holds there (it may hold anything: a
+ * backward pass need not write the gradient of a frozen tensor).  The entry points below are wn_grad_norm, wn_adam_step(_ema) and
+ * wn_adam_step_guarded(_ema) with a table of live ranges in the place of the one skip range; the calls above stay as they are.
+ *
+ * wn_live_table (host only, no launch): `ranges` holds n_ranges pairs lo, hi -- non-empty ranges [lo, hi) inside [0, n), sorted
+ * and disjoint (touching ranges are allowed).  It writes the 3 * n_ranges int64 words of the table to `table` (host memory):
+ * lo[n_ranges], hi[n_ranges], before[n_ranges] = the number of live elements in front of each range, and returns n_live, the
+ * number of live elements; -1 on an error (wn_last_error: NULL, an empty table, an empty range, ranges that are not sorted and
+ * disjoint, a range outside [0, n)).  The caller copies the words to device memory (8-byte aligned) once per freeze set; the
+ * launching calls take that device copy with n_ranges and n_live, and trust it to be what wn_live_table wrote.
+ *
+ * The kernels walk the compacted index space [0, n_live) with the grid the whole-buffer kernel would use for n_live elements and
+ * map an index to its buffer element through the table (staged in LDS up to 1024 ranges, read from global memory beyond; a
+ * thread bisects once and then moves forward).  An element outside every range is neither read nor written in any buffer.
+ *   wn_grad_norm_live          wn_grad_norm over the live elements: the same finalize launch, the same state block, the same
+ *                              promises (grid a function of n_live alone, fixed order at every level, exact products in double:
+ *                              non-finite exactly when a LIVE element is).  scratch: wn_grad_norm_scratch_floats(n) floats.
+ *   wn_adam_step_live          wn_adam_step (ema == NULL) / wn_adam_step_ema: a live element's params, exp_avg, exp_avg_sq and
+ *                              ema get the bits the whole-buffer call gives them on the same inputs and scalars.
+ *   wn_adam_step_guarded_live  wn_adam_step_guarded (ema == NULL) / wn_adam_step_guarded_ema, likewise.
+ * Errors (wn_last_error): a NULL buffer or table, n_ranges <= 0, n_live outside [n_ranges, n], and those of the calls above. */
+int64_t wn_live_table(const int64_t* ranges, int n_ranges, int64_t n, int64_t* table);
+int wn_grad_norm_live(const float* grads, int64_t n, const int64_t* table, int n_ranges, int64_t n_live, float max_norm, int guard,
+                      float lr, float beta1, float beta2, float* scratch, WnOptState* state, void* stream);
+int wn_adam_step_live(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                      const int64_t* table, int n_ranges, int64_t n_live, int64_t step, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, double ema_decay, int ema_warmup, void* stream);
+int wn_adam_step_guarded_live(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                              const int64_t* table, int n_ranges, int64_t n_live, float eps, float weight_decay,
+                              const WnOptState* state, double ema_decay, int ema_warmup, void* stream);
 
 /* ---- op-level entry points (used by the composite calls above; exported for parity tests) ---- */
 

@@ -115,6 +115,8 @@ NARROW_FLAGS = FLAG_DW_3PRODUCT | FLAG_DW_F16PAIR | FLAG_MM_F16PAIR | FLAG_FUSED
 FLAG_REPACK = 1 << 17  # wn_backward: rebuild the packed / pre-split weight sets from the params given to that call
 # wn_op_accumulate modes (include/wavenet_hip.h WN_ACCUM_*): acc = grad, acc = acc + grad, grad = acc + grad
 ACCUM_SET, ACCUM_ADD, ACCUM_FINISH = range(3)
+# wn_backward_needs (include/wavenet_hip.h WN_NEED_*): which of the post-net, the front conv and the upsampling layer train
+NEED_POST, NEED_FRONT, NEED_UP, NEED_ALL = 1, 2, 4, 7
 
 
 def flag_dw_flush(n):
@@ -122,7 +124,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -138,6 +140,7 @@ EXPORTS = [
     "wn_forward_nll", "wn_softmax_nll_rows", "wn_mol_nll_rows", "wn_op_row_sums",
     "wn_adam_step_ema", "wn_adam_step_guarded_ema", "wn_op_swap",
     "wn_op_accumulate",
+    "wn_backward_needs", "wn_live_table", "wn_grad_norm_live", "wn_adam_step_live", "wn_adam_step_guarded_live",
 ]
 
 
@@ -190,6 +193,8 @@ class WnLibrary(object):
         L.wn_backward.argtypes = [cfgp, i, i, vp, vp, vp, vp, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
         L.wn_backward_window.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
         L.wn_backward_dh.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp]
+        # wn_backward_dh + (first_layer, needs): the pass of a model with frozen parameters (ABI v16)
+        L.wn_backward_needs.argtypes = [cfgp, i, i, vp, vp, vp, vp, i, vp, vp, vp, sz, ctypes.POINTER(vp), i, i, i, vp, i, i]
         L.wn_adam_step.argtypes = [vp, vp, vp, vp, i64, i64, f, f, f, f, f, i64, i64, vp]
         L.wn_grad_norm_scratch_floats.argtypes = [i64]
         L.wn_grad_norm_scratch_floats.restype = i64
@@ -200,6 +205,12 @@ class WnLibrary(object):
         L.wn_adam_step_guarded_ema.argtypes = [vp, vp, vp, vp, vp, i64, f, f, i64, i64, vp, d, i, vp]
         L.wn_op_swap.argtypes = [vp, vp, i64, vp]
         L.wn_op_accumulate.argtypes = [vp, vp, i64, i, vp]
+        # live ranges (ABI v16): (host ranges, n_ranges, n, host table) -> n_live; then (.., n, device table, n_ranges, n_live, ..)
+        L.wn_live_table.argtypes = [vp, i, i64, vp]
+        L.wn_live_table.restype = i64
+        L.wn_grad_norm_live.argtypes = [vp, i64, vp, i, i64, f, i, f, f, f, vp, vp, vp]
+        L.wn_adam_step_live.argtypes = [vp, vp, vp, vp, vp, i64, vp, i, i64, i64, f, f, f, f, f, d, i, vp]
+        L.wn_adam_step_guarded_live.argtypes = [vp, vp, vp, vp, vp, i64, vp, i, i64, f, f, vp, d, i, vp]
         L.wn_op_front.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.wn_op_causal_conv.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.wn_op_causal_conv_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]

@@ -605,6 +605,13 @@ def get_parser():
                              "minibatches.  The step is the mean over all their loss positions; one-utterance batches (whose "
                              "lengths the other ranks do not know) are weighted equally, 1 / (ranks * accum_steps)")
     parser.add_argument("--resume", default=None, nargs="?", type=str, help="checkpoint to continue from")
+    # extension (not reference flags): fine-tuning part of a model (WaveNet.freeze / train_only)
+    parser.add_argument("--pretrained", default=None, type=str,
+                        help="checkpoint whose model weights start iteration 0 (fresh optimizer); not together with --resume")
+    parser.add_argument("--freeze", default=None, type=str,
+                        help="regular expression (re.search on the parameter names): the matching tensors are frozen")
+    parser.add_argument("--train_only", default=None, type=str,
+                        help="regular expression: only the matching tensors train, every other one is frozen; not together with --freeze")
     return parser
 
 
@@ -733,6 +740,19 @@ def _worker(rank, world, args, port):
                           max_grad_norm=max_grad_norm if max_grad_norm > 0.0 else None,
                           skip_nonfinite=bool(getattr(args, "skip_nonfinite_steps", False)),
                           ema_decay=ema_decay if ema_decay > 0.0 else None, ema_warmup=bool(getattr(args, "ema_warmup", True)))
+    pretrained, freeze, train_only = (getattr(args, k, None) or None for k in ("pretrained", "freeze", "train_only"))
+    if pretrained:   # (main() has refused --pretrained beside --resume and --freeze beside --train_only)
+        model.load_state_dict(torch.load(pretrained, map_location=lambda storage, loc: storage, weights_only=False)["model"])
+        logging.info("model weights from %s (iteration 0, fresh optimizer)." % pretrained)
+    if freeze or train_only:
+        if freeze:
+            model.freeze(freeze)
+        else:
+            model.train_only(train_only)
+        tensors = list(model.parameters())
+        frozen = [p for p in tensors if not p.requires_grad]
+        logging.info("trainable parameters = %d of %d (%d of %d tensors frozen)" % (
+            sum(p.numel() for p in tensors) - sum(p.numel() for p in frozen), sum(p.numel() for p in tensors), len(frozen), len(tensors)))
     if args.resume is not None and len(args.resume) != 0:
         checkpoint = torch.load(args.resume, map_location=lambda storage, loc: storage, weights_only=False)
         iterations = checkpoint["iterations"]
@@ -877,6 +897,12 @@ def main(argv=None):
     if n_ranks > 1 and (args.batch_length is not None or args.utterance_batch) and args.batch_size < n_ranks:
         # every rank must own at least one window of each minibatch (the reference scatters the same way)
         logging.error("--batch_size (%d) must be >= the number of GPUs (%d)." % (args.batch_size, n_ranks))
+        sys.exit(1)
+    if args.freeze and args.train_only:
+        logging.error("--freeze and --train_only exclude each other.")
+        sys.exit(1)
+    if args.pretrained and args.resume:
+        logging.error("--pretrained starts iteration 0 from a checkpoint's weights, --resume continues a run: give one of them.")
         sys.exit(1)
     if world_env > 1:  # launched by torch.distributed.run: one process per GPU already
         _worker(int(os.environ.get("LOCAL_RANK", os.environ.get("RANK", "0"))), world_env, args,

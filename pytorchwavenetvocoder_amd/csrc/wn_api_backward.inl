@@ -95,15 +95,33 @@ extern "C" int wn_backward(const WnConfig* cfg, int B, int T, const float* param
 // grads == NULL (wn_backward_dh only): the data gradients and dh alone -- no weight-gradient launch, no reduction of one, and no
 // scale of the fp16 pair weight gradients (the data contractions of WN_FLAG_MM_F16PAIR still take theirs).  dh != NULL: dL/dh
 // (wn_auxdh.inl) after the last flush group, on its stream; the flush groups then keep dG of every layer (at its own offset).
+//
+// Frozen parameters (wn_backward_needs, ABI v16): `first_layer` is the lowest layer whose own tensors hold a
+// trainable one (L: none) and `needs` says which of the post-net, the front conv and the upsampling layer train.  The pass then
+// stops where nothing below needs it: the chain runs from L - 1 down to first_layer and the launch that would produce
+// dX_{first_layer} is left out (unless first_layer == 0 and the front conv trains); flush groups and buckets are counted from the
+// top as always, so a group wholly at or above first_layer is the full pass's group, launch for launch, and the lowest one is cut
+// at first_layer; a bucket whose layers were all left out still gets its event where the walk reaches it.  Nothing is left out
+// inside a computed layer.  The other three entry points pass first_layer = 0 and WN_NEED_ALL: the launches of before.
 static int backward_impl(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
                          const float* dlogits, int t_first, float* grads, float* dh, void* wsp, size_t ws_bytes,
-                         void* const* events, int n_events, int lpb, int flags, void* stream) {
+                         void* const* events, int n_events, int lpb, int flags, void* stream, int first_layer = 0,
+                         int needs = WN_NEED_ALL) {
     Ctx c;
     WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, flags, stream));
     if (!params || !x || !h || !dlogits || (!grads && !dh)) return fail(1, "NULL argument");
     c.params = params;
     if (t_first < 0 || t_first >= T) return fail(1, "t_first=%d outside [0,%d)", t_first, T);
     const bool wgrad = grads != nullptr;
+    const int fl = first_layer;
+    if (fl < 0 || fl > c.d.L) return fail(1, "first_layer=%d outside [0,%d]", fl, c.d.L);
+    if (needs & ~WN_NEED_ALL) return fail(1, "needs=%d holds unknown bits", needs);
+    if (fl > 0 && (dh || !wgrad)) return fail(1, "first_layer=%d with dh: dL/dh needs every layer (first_layer = 0)", fl);
+    if (fl > 0 && (needs & (WN_NEED_FRONT | WN_NEED_UP)))
+        return fail(1, "first_layer=%d with the front conv or the upsampling layer trainable: both need every layer (first_layer = 0)", fl);
+    const bool need_post = wgrad && (needs & WN_NEED_POST), need_front = (needs & WN_NEED_FRONT) != 0,
+               need_up = (needs & WN_NEED_UP) != 0;
+    const bool any_below_logits = fl < c.d.L || need_post;   // false: nothing at all reads dO2 / dSkip
     if (c.dw_f16_mode && (wgrad || c.r.mm_f16)) {   // before the side stream forks: overflow word := 0, a_mul := the scale of this call's gradient (wn_elem.h)
         const int tw0 = (t_first / 128) * 128;
         float* words = c.ws + c.w.dw_ovf;
@@ -146,7 +164,7 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
     int bucket = 0;
 
     // ---- post-net backward (wavenet.py:518-523 reversed) ----
-    {   // dO2 = W2^T dlogits, masked by relu'(O2)
+    if (any_below_logits) {   // dO2 = W2^T dlogits, masked by relu'(O2)
         WnGemmArgs g = wn_gemm_default();
         g.M = d.S; g.N = Tw; g.K = d.Qo;
         g.A = params + y.post2_w; g.lda = d.S;
@@ -156,7 +174,7 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
         g.nbatch = B; g.tag = "bwd_post2_dx";
         WN_TRY(fw_gemm(c, g, nullptr, nullptr, t0, true));
     }
-    {   // dSkip = W1^T dO2, masked by relu'(skip-sum)
+    if (any_below_logits) {   // dSkip = W1^T dO2, masked by relu'(skip-sum)
         WnGemmArgs g = wn_gemm_default();
         g.M = d.S; g.N = Tw; g.K = d.S;
         g.A = params + y.post1_w; g.lda = d.S;
@@ -168,14 +186,14 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
         if (t0 > 0) WN_TRY(wn_fill_cols(ws + w.dSk, (long)B * d.S, T, t0, c.st));
     }
     WN_TRY(side_link(side.rt, c.st, cs.st));  // fork: dO2, dSkip (and everything before this call) are ready
-    if (wgrad) {   // d conv_post_2.{weight,bias}
+    if (need_post) {   // d conv_post_2.{weight,bias}
         WnGemmArgs g = wn_gemm_default();
         g.M = d.Qo; g.N = d.S; g.K = Tw;
         g.A = dlogits + t0; g.lda = T; g.a_zstride = (long)d.Qo * T;
         g.B = ws + w.O2 + t0; g.ldb = T; g.b_zstride = (long)d.S * T; g.b_clen = Tw; g.tag = "dw_post2";
         WN_TRY(dw_gemm(cs, g, dw_out_plain(grads + y.post2_w, d.S, grads + y.post2_b)));
     }
-    if (wgrad) {   // d conv_post_1.{weight,bias}
+    if (need_post) {   // d conv_post_1.{weight,bias}
         WnGemmArgs g = wn_gemm_default();
         g.M = d.S; g.N = d.S; g.K = Tw;
         g.A = ws + w.dO2 + t0; g.lda = T; g.a_zstride = (long)d.S * T;
@@ -193,9 +211,12 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
     // 8..15 override the group size.  (The split-K plan, hence the rounding, depends on the group size.)
     int fmax = (flags >> 8) & 0xff;
     if (fmax == 0) fmax = (side.rt && !(flags & WN_FLAG_BWD_OVERLAP_HEAD)) ? WN_DW_FLUSH_DEFAULT : d.L;
-    const bool skipres = c.r.split_bf16 && c.dw_f16_mul != 0.0f && d.L > 1 && lpb >= d.L && fmax >= 2 &&
+    // (first_layer == L - 1 cuts the top group down to the last layer alone: the same exclusion)
+    const bool skipres = c.r.split_bf16 && c.dw_f16_mul != 0.0f && d.L > 1 && lpb >= d.L && fmax >= 2 && fl < d.L - 1 &&
                          wn_dw_skipres_supported(d.S, d.R, d.L, d.L - 1);
-    if (wgrad && !skipres) {   // d skip_1x1.l.weight for all layers in one contraction; bias = rowsum(dSkip) for every layer
+    // (over all L layers whenever a layer is computed: the split-K plan, the tile shape and the row sums behind the biases follow
+    // the column count, so a contraction over [first_layer, L) alone would not give the computed layers the full pass's bits)
+    if (wgrad && !skipres && fl < d.L) {   // d skip_1x1.l.weight for all layers in one contraction; bias = rowsum(dSkip) for every layer
         WnGemmArgs g = wn_gemm_default();
         g.M = d.S; g.N = d.L * d.R; g.K = Tw;
         g.A = ws + w.dSk + t0; g.lda = T; g.a_zstride = (long)d.S * T;
@@ -213,7 +234,9 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
     // (layer = outermost z dimension of the dW contraction), then reduced in a fixed order.
     const float* upw = d.U > 0 ? params + y.up_w : ws + w.one;
     const bool aux_fused = c.r.aux_fused, chain = c.r.chain;
-    if (chain) {
+    // (all L * R rows whatever first_layer is: the pre-split image of wskipT_f is one [k][rows] block and the kernel variant
+    // follows the row count, so a launch over fewer rows would not give the computed layers the full pass's bits)
+    if (chain && fl < d.L) {
         WnGemmArgs g = wn_gemm_default();
         g.M = d.L * d.R; g.N = Tw; g.K = d.S;
         g.A = ws + w.wskipT_f; g.lda = (long)d.L * d.R;
@@ -331,6 +354,8 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
 
     int bucket_hi = d.L;  // layers [l, bucket_hi) have been walked but not flushed yet
     for (int l = d.L - 1; l >= 0; --l) {
+        const bool computed = l >= fl;                        // below first_layer: only the bucket bookkeeping
+        const bool want_dx = l > fl || (l == 0 && need_front);   // dX_l feeds layer l - 1 (or the front conv): not below the cut
         const int dil = dilation_of(cfg, l);
         const float* Sl = c.Sg(l);
         const float* Gtl = c.Gt(l);   // any-size path only: the fused forward saves s and z = s * tanh
@@ -341,20 +366,21 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
         float* dXl = c.dX(l);
         const float* wskip = params + c.p_skip(l);
         const float* wres = params + c.p_layer(l) + y.o_res_w;
-        if (chain) {
+        if (!computed) {
+        } else if (chain) {
             if (l == d.L - 1) {   // head of the chain: gate' of the last layer on its rows of dZs (no dX input)
                 WN_TRY(wn_fused_bwd_chain_head(c.dZs(l), c.dZs_B(), Sl, Zl, gz, dP, c.G(l), c.G_B(), upw, Ue, F,
                                                aux_fused ? c.dGp(l) : nullptr, aux_fused ? c.qp(l) : nullptr, B, T, t0,
                                                c.r.chain_f16 ? c.amaxP(l) : nullptr, c.st));
             }
-            if (l > 0) {  // dX_l from dP_l, and gate' of layer l-1 from it
+            if (l > fl) {  // dX_l from dP_l, and gate' of layer l-1 from it
                 const int lp = l - 1;
                 WN_TRY(wn_fused_bwd_chain(c.wd_b(l), dP, dXn, dXl, params + c.p_layer(lp) + y.o_res_w, c.dZs(lp), c.dZs_B(),
                                           c.Sg(lp), c.Z(lp), gz, c.P(lp), c.G(lp), c.G_B(), upw, Ue, F,
                                           aux_fused ? c.dGp(lp) : nullptr, aux_fused ? c.qp(lp) : nullptr, B, T, d.K, dil,
                                           c.img(1, l, c.r.chain_f16), c.img(2, lp, c.r.chain_f16), t0,
                                           c.r.chain_f16 ? c.amaxP(l) : nullptr, c.r.chain_f16 ? c.amaxP(lp) : nullptr, c.st));
-            } else {      // tail: dX_0
+            } else if (want_dx) {      // tail: dX_0
                 WN_TRY(wn_fused_bwd_dx(c.wd_b(0), dP, dXn, dXl, B, T, d.K, dil, 1, c.st));
             }
         } else if (c.r.fused) {
@@ -364,7 +390,7 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
                                              c.qp(l), B, T, d.S, c.st));
             else
                 WN_TRY(wn_fused_bwd_gate(wskip, wres, ws + w.dSk, dXn, Sl, Zl, gz, dP, B, T, d.S, c.r.split_bf16 ? 1 : 0, c.st));
-            WN_TRY(wn_fused_bwd_dx(c.wd_b(l), dP, dXn, dXl, B, T, d.K, dil, c.r.split_bf16 ? 1 : 0, c.st));
+            if (want_dx) WN_TRY(wn_fused_bwd_dx(c.wd_b(l), dP, dXn, dXl, B, T, d.K, dil, c.r.split_bf16 ? 1 : 0, c.st));
         } else {
             // dZ = Wskip_l^T dSkip (+ Wres_l^T dX_{l+1}) -> gate' -> dP.  Wide models on the split kernels: gate' is the
             // epilogue of the LAST of the two contractions (dZ never leaves the chip for it).
@@ -397,7 +423,7 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
                 if (dXn) WN_TRY(fw_gemm(c, gr, nullptr, nullptr, 0, true));
                 WN_TRY(wn_gate_bwd(ws + w.dZ, Sl, Gtl, dP, B, T, d.R, c.st));
             }
-            {   // dX_l = dX_{l+1} + sum_tap W_tap^T dP[t + (K-1-tap) d]
+            if (want_dx) {   // dX_l = dX_{l+1} + sum_tap W_tap^T dP[t + (K-1-tap) d]
                 WnGemmArgs g = wn_gemm_default();
                 g.M = d.R; g.N = T; g.K = d.K * 2 * d.R;
                 g.A = c.wd_b(l); g.lda = d.R;
@@ -411,11 +437,13 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
         }
         const int done = d.L - l;  // layers walked
         const bool bucket_end = (done % lpb == 0 || l == 0);
-        if (bucket_end || bucket_hi - l >= fmax) {
-            WN_TRY(side_link(side.rt, c.st, cl.st));  // dP, dX of layers [l, bucket_hi) are enqueued
-            if (flags & WN_FLAG_BWD_OVERLAP_HEAD)       // the split-K partial buffers are shared with the head's launches
-                WN_TRY(side_link(side.rt, cs.st, c.st));
-            WN_TRY(flush_bucket(l, bucket_hi));
+        if (bucket_end || bucket_hi - l >= fmax || l == fl) {   // (l == first_layer: the lowest group is cut here)
+            if (computed) {
+                WN_TRY(side_link(side.rt, c.st, cl.st));  // dP, dX of layers [l, bucket_hi) are enqueued
+                if (flags & WN_FLAG_BWD_OVERLAP_HEAD)       // the split-K partial buffers are shared with the head's launches
+                    WN_TRY(side_link(side.rt, cs.st, c.st));
+                WN_TRY(flush_bucket(l, bucket_hi));
+            }
             bucket_hi = l;
             if (bucket_end) {
                 if (events) rt_event_record(events[bucket], cl.st);
@@ -438,8 +466,9 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
     }
     const float* dXn = c.dX(0);  // dL/dx_0
     // ---- front conv: scatter over the token indices, or (large tables) the one-hot contraction ----
-    if (wn_front_dw_supported(d.R, d.K, d.Q) &&
-        wn_front_dw_partial_floats(B, T, d.R, d.K, d.Q) <= w.front_partial_floats) {
+    if (!need_front) {
+    } else if (wn_front_dw_supported(d.R, d.K, d.Q) &&
+               wn_front_dw_partial_floats(B, T, d.R, d.K, d.Q) <= w.front_partial_floats) {
         WN_TRY(wn_front_dw(dXn, x, ws + w.front_partial, grads + y.causal_w, grads + y.causal_b, B, T, d.R, d.K, d.Q, cl.st));
     } else {
         WnGemmArgs g = wn_gemm_default();
@@ -452,7 +481,7 @@ static int backward_impl(const WnConfig* cfg, int B, int T, const float* params,
         WN_TRY(dw_gemm(cl, g, o));
     }
     // ---- upsampling layer parameters ----
-    if (d.U > 0) {
+    if (d.U > 0 && need_up) {
         WnReduceArgs r = reduce_plain(ws + w.dw_partial, d.L * B * 2 * d.R, 1, d.U, grads + y.up_w, 0, 1);
         r.scratch = ws + w.red_scratch; r.scratch_floats = w.red_scratch_floats;
         WN_TRY(wn_reduce(&r, cl.st));
@@ -479,6 +508,16 @@ extern "C" int wn_backward_dh(const WnConfig* cfg, int B, int T, const float* pa
     if (!grads && !dh) return fail(1, "wn_backward_dh: grads and dh are both NULL");
     if (!grads && (events || n_events)) return fail(1, "wn_backward_dh: bucket events need grads (no weight gradients are produced)");
     return backward_impl(cfg, B, T, params, x, h, dlogits, t_first, grads, dh, wsp, ws_bytes, events, n_events, lpb, flags, stream);
+}
+
+extern "C" int wn_backward_needs(const WnConfig* cfg, int B, int T, const float* params, const int64_t* x, const float* h,
+                                 const float* dlogits, int t_first, float* grads, float* dh, void* wsp, size_t ws_bytes,
+                                 void* const* events, int n_events, int lpb, int flags, void* stream, int first_layer, int needs) {
+    api_enter();
+    if (!grads && !dh) return fail(1, "wn_backward_needs: grads and dh are both NULL");
+    if (!grads && (events || n_events)) return fail(1, "wn_backward_needs: bucket events need grads (no weight gradients are produced)");
+    return backward_impl(cfg, B, T, params, x, h, dlogits, t_first, grads, dh, wsp, ws_bytes, events, n_events, lpb, flags, stream,
+                         first_layer, needs);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -574,4 +613,78 @@ extern "C" int wn_adam_step_guarded_ema(float* params, const float* grads, float
     WN_TRY(wn_adam_guarded_ema(params, grads, exp_avg, exp_avg_sq, ema, (long)n, eps, weight_decay, (long)skip_lo, (long)skip_hi,
                                state, ema_decay, ema_warmup, (wn_stream_t)stream));
     return rt_check("wn_adam_step_guarded_ema");
+}
+
+// ------------------------------------------------------------------------------------------
+// Training with frozen parameters (ABI v16): the norm and the Adam step over live ranges of the flat buffers.  wn_live_table is
+// the one place a list of ranges is checked and turned into the table the kernels read; the launching entry points take the
+// device copy of what it wrote, with its two host-side facts (n_ranges, n_live).
+extern "C" int64_t wn_live_table(const int64_t* ranges, int n_ranges, int64_t n, int64_t* table) {
+    g_err[0] = 0;   // pure host code: no runtime call to clear
+    if (!ranges || !table) return fail(1, "wn_live_table: NULL argument"), -1;
+    if (n_ranges <= 0) return fail(1, "wn_live_table: an empty table (n_ranges = %d)", n_ranges), -1;
+    if (n <= 0) return fail(1, "wn_live_table: n <= 0"), -1;
+    int64_t before = 0, prev_hi = 0;
+    for (int r = 0; r < n_ranges; ++r) {
+        const int64_t lo = ranges[2 * r], hi = ranges[2 * r + 1];
+        if (lo < 0 || hi > n) return fail(1, "wn_live_table: range %d = [%lld, %lld) outside [0, %lld)", r, (long long)lo, (long long)hi, (long long)n), -1;
+        if (hi <= lo) return fail(1, "wn_live_table: range %d = [%lld, %lld) is empty", r, (long long)lo, (long long)hi), -1;
+        if (r > 0 && lo < prev_hi) return fail(1, "wn_live_table: range %d = [%lld, %lld) is not behind range %d (the ranges must be sorted and disjoint)", r, (long long)lo, (long long)hi, r - 1), -1;
+        table[r] = lo;
+        table[n_ranges + r] = hi;
+        table[2 * (int64_t)n_ranges + r] = before;
+        before += hi - lo;
+        prev_hi = hi;
+    }
+    return before;
+}
+
+static const char* live_argument_error(const int64_t* table, int n_ranges, int64_t n_live, int64_t n) {
+    if (!table) return "table is NULL";
+    if (n_ranges <= 0) return "an empty table";
+    if (n_live < n_ranges || n_live > n) return "n_live is not what wn_live_table returned for this table";
+    if (reinterpret_cast<uintptr_t>(table) & 7) return "table needs 8-byte alignment";
+    return nullptr;
+}
+
+extern "C" int wn_grad_norm_live(const float* grads, int64_t n, const int64_t* table, int n_ranges, int64_t n_live, float max_norm,
+                                 int guard, float lr, float beta1, float beta2, float* scratch, WnOptState* state, void* stream) {
+    api_enter();
+    if (!grads || !scratch || !state || n <= 0) return fail(1, "bad wn_grad_norm_live argument");
+    if (const char* why = live_argument_error(table, n_ranges, n_live, n)) return fail(1, "wn_grad_norm_live: %s", why);
+    if ((reinterpret_cast<uintptr_t>(grads) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 7) || (reinterpret_cast<uintptr_t>(state) & 7))
+        return fail(1, "wn_grad_norm_live: grads needs 4-byte, scratch and state 8-byte alignment");
+    double* partial = reinterpret_cast<double*>(scratch);
+    WN_TRY(wn_grad_sumsq_live(grads, reinterpret_cast<const long*>(table), n_ranges, (long)n_live, partial, (wn_stream_t)stream));
+    WN_TRY(wn_grad_norm_finalize(partial, wn_grad_sumsq_blocks((long)n_live), max_norm, guard != 0, lr, beta1, beta2, state,
+                                 (wn_stream_t)stream));
+    return rt_check("wn_grad_norm_live");
+}
+
+extern "C" int wn_adam_step_live(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                 const int64_t* table, int n_ranges, int64_t n_live, int64_t step, float lr, float beta1, float beta2,
+                                 float eps, float weight_decay, double ema_decay, int ema_warmup, void* stream) {
+    api_enter();
+    if (!adam_buffers_ok(params, grads, exp_avg, exp_avg_sq, n) || step < 1) return fail(1, "bad wn_adam_step_live argument");
+    if (const char* why = live_argument_error(table, n_ranges, n_live, n)) return fail(1, "wn_adam_step_live: %s", why);
+    if (ema)
+        if (const char* why = ema_argument_error(params, ema, n, ema_decay)) return fail(1, "wn_adam_step_live: %s", why);
+    const AdamBias b = adam_bias(lr, beta1, beta2, step);
+    WN_TRY(wn_adam_live(params, grads, exp_avg, exp_avg_sq, ema, reinterpret_cast<const long*>(table), n_ranges, (long)n_live,
+                        b.lr_over_bc1, b.sqrt_bc2, beta1, beta2, eps, weight_decay,
+                        ema ? wn_ema_weight(ema_decay, ema_warmup, step) : 0.0f, (wn_stream_t)stream));
+    return rt_check("wn_adam_step_live");
+}
+
+extern "C" int wn_adam_step_guarded_live(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                         const int64_t* table, int n_ranges, int64_t n_live, float eps, float weight_decay,
+                                         const WnOptState* state, double ema_decay, int ema_warmup, void* stream) {
+    api_enter();
+    if (!adam_buffers_ok(params, grads, exp_avg, exp_avg_sq, n) || !state) return fail(1, "bad wn_adam_step_guarded_live argument");
+    if (const char* why = live_argument_error(table, n_ranges, n_live, n)) return fail(1, "wn_adam_step_guarded_live: %s", why);
+    if (ema)
+        if (const char* why = ema_argument_error(params, ema, n, ema_decay)) return fail(1, "wn_adam_step_guarded_live: %s", why);
+    WN_TRY(wn_adam_guarded_live(params, grads, exp_avg, exp_avg_sq, ema, reinterpret_cast<const long*>(table), n_ranges, (long)n_live,
+                                eps, weight_decay, state, ema_decay, ema_warmup, (wn_stream_t)stream));
+    return rt_check("wn_adam_step_guarded_live");
 }

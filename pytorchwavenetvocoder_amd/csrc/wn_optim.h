@@ -39,6 +39,16 @@ int wn_adam_ema(float* p, const float* g, float* m, float* v, float* e, long n, 
                 float beta2, float eps, float weight_decay, long skip_lo, long skip_hi, float w, wn_stream_t st);
 int wn_adam_guarded_ema(float* p, const float* g, float* m, float* v, float* e, long n, float eps, float weight_decay, long skip_lo,
                         long skip_hi, const struct WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st);
+// The same over LIVE RANGES of the buffers (training with frozen parameters; include/wavenet_hip.h, ABI v16).  `table` is the
+// device table wn_live_table wrote (lo[nr], hi[nr], before[nr]), n_live its number of live elements.  The kernels walk the
+// compacted index space [0, n_live) with the grid of the whole-buffer launch for n_live elements and address nothing outside the
+// ranges; a live element gets the bits the whole-buffer launch gives it.  e == NULL: no moving average.
+int wn_adam_live(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live, float lr_over_bc1,
+                 float sqrt_bc2, float beta1, float beta2, float eps, float weight_decay, float w, wn_stream_t st);
+int wn_adam_guarded_live(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live, float eps,
+                         float weight_decay, const struct WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st);
+// wn_grad_sumsq_blocks(n_live) partials for wn_grad_norm_finalize
+int wn_grad_sumsq_live(const float* g, const long* table, int nr, long n_live, double* partial, wn_stream_t st);
 // a[i] <-> b[i], i < n: two non-overlapping fp32 buffers of 4-byte alignment, exchanged in place
 int wn_swap(float* a, float* b, long n, wn_stream_t st);
 // gradient accumulation over micro-batches (include/wavenet_hip.h WN_ACCUM_*, ABI v15): SET acc = grad, ADD acc = acc + grad,

@@ -40,8 +40,30 @@ static unsigned wn_quad_blocks(long n, long cap) {
 //            e == p_new as its exact fixed point; d e + (1 - d) p_new has not (the two fp32 coefficients of d = 0.9999 do not sum
 //            to 1).  9 words per element move instead of 7.
 // Both are compile-time: a plain kernel carries no multiply by a coefficient and no access to e.  p, m and v get the same bits
-// from all four kernels because there is one expression for them, which no flag changes: GUARDED only puts a separately rounded
-// product in place of g[i], and the EMA only reads pn.
+// from all four kernels because there is one expression for them (wn_adam_element), which no flag changes: GUARDED only puts a
+// separately rounded product in place of g[i], and the EMA only reads pn.  The kernels over live ranges (below) call the same one.
+template <bool GUARDED, bool EMA>
+static __device__ __forceinline__ void wn_adam_element(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, float* __restrict__ e, long i, float lr_over_bc1,
+                                                       float sqrt_bc2, float coef, float beta1, float beta2, float eps, float wd,
+                                                       float w) {
+    const float pv = p[i];
+    float ev = 0.0f;
+    if (EMA) ev = e[i];
+    // never contracted into the decay term's fma: coef == 1 leaves the unguarded arithmetic
+    float gv = GUARDED ? wn_fmul_rn(coef, g[i]) : g[i];
+    if (wd != 0.0f) gv += wd * pv;
+    const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
+    const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
+    m[i] = mv;
+    v[i] = vv;
+    const float denom = sqrtf(vv) / sqrt_bc2 + eps;
+    const float pn = pv - lr_over_bc1 * (mv / denom);
+    p[i] = pn;
+    if (EMA) e[i] = fmaf(w, pn - ev, ev);
+}
+
+// the whole buffer without [skip_lo, skip_hi): one element per thread and trip
 template <bool GUARDED, bool EMA>
 static __device__ __forceinline__ void wn_adam_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                      float* __restrict__ v, float* __restrict__ e, long n, float lr_over_bc1,
@@ -50,20 +72,7 @@ static __device__ __forceinline__ void wn_adam_sweep(float* __restrict__ p, cons
     const long stride = (long)gridDim.x * WN_TPB;
     for (long i = (long)blockIdx.x * WN_TPB + threadIdx.x; i < n; i += stride) {
         if (i >= skip_lo && i < skip_hi) continue;
-        const float pv = p[i];
-        float ev = 0.0f;
-        if (EMA) ev = e[i];
-        // never contracted into the decay term's fma: coef == 1 leaves the unguarded arithmetic
-        float gv = GUARDED ? wn_fmul_rn(coef, g[i]) : g[i];
-        if (wd != 0.0f) gv += wd * pv;
-        const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
-        const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
-        m[i] = mv;
-        v[i] = vv;
-        const float denom = sqrtf(vv) / sqrt_bc2 + eps;
-        const float pn = pv - lr_over_bc1 * (mv / denom);
-        p[i] = pn;
-        if (EMA) e[i] = fmaf(w, pn - ev, ev);
+        wn_adam_element<GUARDED, EMA>(p, g, m, v, e, i, lr_over_bc1, sqrt_bc2, coef, beta1, beta2, eps, wd, w);
     }
 }
 
@@ -252,6 +261,164 @@ int wn_grad_norm_finalize(const double* partial, int nb, float max_norm, int gua
                           WnOptState* state, wn_stream_t st) {
     WN_PROF("grad_norm_finalize", 0.0, 8.0 * (double)nb, st);
     WN_LAUNCH(k_grad_norm_finalize, dim3(1), dim3(WN_TPB), 0, st, partial, nb, max_norm, guard, lr, beta1, beta2, state);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adam and the sum of squares over LIVE RANGES of the flat buffers (training with frozen parameters; ABI v16).
+// The table (device memory, int64, wn_live_table writes it): lo[nr], hi[nr], before[nr] -- nr sorted, disjoint, non-empty ranges
+// [lo, hi) and the number of live elements in front of each.  A kernel walks the COMPACTED index space [0, n_live) with the grid
+// its whole-buffer twin would use for n_live elements; compacted index c of range r is buffer element lo[r] + (c - before[r]).
+// A thread finds the range of its first index by bisection, then only moves forward: while c stays inside the range it holds
+// (two registers: the range's end and the offset to add) no table word is read.  Tables of up to WN_LIVE_LDS_RANGES ranges are
+// staged in LDS (16 KiB) by every block; a longer one is read where it lies.  Elements outside every range are never addressed.
+#define WN_LIVE_LDS_RANGES 1024
+struct WnLiveTable {
+    const long* lo;
+    const long* before;
+    int nr;
+    long n_live;
+};
+struct WnLiveCursor {
+    int r;      // the range the thread is in
+    long end;   // compacted end of that range
+    long off;   // buffer index = compacted index + off
+};
+// every thread of the block calls it (one barrier when the table is staged: nr is uniform)
+static __device__ __forceinline__ WnLiveTable wn_live_stage(const long* __restrict__ table, int nr, long n_live, long* s_lo,
+                                                            long* s_before) {
+    if (nr > WN_LIVE_LDS_RANGES) return {table, table + 2 * (long)nr, nr, n_live};
+    for (int i = threadIdx.x; i < nr; i += WN_TPB) {
+        s_lo[i] = table[i];
+        s_before[i] = table[2 * (long)nr + i];
+    }
+    __syncthreads();
+    return {s_lo, s_before, nr, n_live};
+}
+static __device__ __forceinline__ void wn_live_enter(const WnLiveTable& t, int r, WnLiveCursor* k) {
+    const long first = t.before[r];
+    k->r = r;
+    k->end = r + 1 < t.nr ? t.before[r + 1] : t.n_live;
+    k->off = t.lo[r] - first;
+}
+// the last range in [r0, nr) that begins at or in front of c (c < n_live, before[r0] <= c)
+static __device__ __forceinline__ void wn_live_seek(const WnLiveTable& t, long c, int r0, WnLiveCursor* k) {
+    int a = r0, b = t.nr - 1;
+    while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if (t.before[mid] <= c) a = mid;
+        else b = mid - 1;
+    }
+    wn_live_enter(t, a, k);
+}
+// buffer index of compacted index c, which is not in front of the cursor: the next range first (the common step), bisection over
+// the ranges behind it otherwise (a stride that jumps many short ranges)
+static __device__ __forceinline__ long wn_live_index(const WnLiveTable& t, long c, WnLiveCursor* k) {
+    if (c >= k->end) {
+        wn_live_enter(t, k->r + 1, k);
+        if (c >= k->end) wn_live_seek(t, c, k->r + 1, k);
+    }
+    return c + k->off;
+}
+
+// One kernel for the four variants: the unguarded ones take their scalars as arguments, the guarded ones from the state block
+// (and return before anything else when the step does not apply), exactly as k_adam* above.
+template <bool GUARDED, bool EMA>
+__global__ __launch_bounds__(WN_TPB) void k_adam_live(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, float* __restrict__ e, const long* __restrict__ table,
+                                                      int nr, long n_live, float lr_over_bc1, float sqrt_bc2, float beta1,
+                                                      float beta2, float eps, float wd, float w,
+                                                      const WnOptState* __restrict__ state, double ema_decay, int ema_warmup) {
+    __shared__ long s_lo[WN_LIVE_LDS_RANGES], s_before[WN_LIVE_LDS_RANGES];
+    float coef = 1.0f;
+    if (GUARDED) {
+        if (!state->apply) return;
+        lr_over_bc1 = state->lr_over_bc1;
+        sqrt_bc2 = state->sqrt_bc2;
+        coef = state->clip_coef;
+        beta1 = state->beta1;
+        beta2 = state->beta2;
+        if (EMA) w = wn_ema_weight(ema_decay, ema_warmup, state->steps_applied);
+    }
+    const WnLiveTable t = wn_live_stage(table, nr, n_live, s_lo, s_before);
+    const long stride = (long)gridDim.x * WN_TPB;
+    long c = (long)blockIdx.x * WN_TPB + threadIdx.x;
+    if (c >= n_live) return;
+    WnLiveCursor k;
+    wn_live_seek(t, c, 0, &k);
+    for (; c < n_live; c += stride)
+        wn_adam_element<GUARDED, EMA>(p, g, m, v, e, wn_live_index(t, c, &k), lr_over_bc1, sqrt_bc2, coef, beta1, beta2, eps, wd, w);
+}
+
+template <bool GUARDED, bool EMA>
+static void wn_adam_live_launch(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live,
+                                float lr_over_bc1, float sqrt_bc2, float beta1, float beta2, float eps, float wd, float w,
+                                const WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st) {
+    auto kernel = k_adam_live<GUARDED, EMA>;
+    WN_LAUNCH(kernel, dim3(wn_adam_blocks(n_live)), dim3(WN_TPB), 0, st, p, g, m, v, e, table, nr, n_live, lr_over_bc1, sqrt_bc2,
+              beta1, beta2, eps, wd, w, state, ema_decay, ema_warmup);
+}
+
+int wn_adam_live(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live, float lr_over_bc1,
+                 float sqrt_bc2, float beta1, float beta2, float eps, float weight_decay, float w, wn_stream_t st) {
+    WN_PROF(e ? "adam_ema_live" : "adam_live", 0.0, (e ? 36.0 : 28.0) * (double)n_live, st);
+    if (e) wn_adam_live_launch<false, true>(p, g, m, v, e, table, nr, n_live, lr_over_bc1, sqrt_bc2, beta1, beta2, eps, weight_decay, w, nullptr, 0.0, 0, st);
+    else wn_adam_live_launch<false, false>(p, g, m, v, e, table, nr, n_live, lr_over_bc1, sqrt_bc2, beta1, beta2, eps, weight_decay, w, nullptr, 0.0, 0, st);
+    return 0;
+}
+
+int wn_adam_guarded_live(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live, float eps,
+                         float weight_decay, const WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st) {
+    WN_PROF(e ? "adam_guarded_ema_live" : "adam_guarded_live", 0.0, (e ? 36.0 : 28.0) * (double)n_live, st);
+    if (e) wn_adam_live_launch<true, true>(p, g, m, v, e, table, nr, n_live, 0.0f, 0.0f, 0.0f, 0.0f, eps, weight_decay, 0.0f, state, ema_decay, ema_warmup, st);
+    else wn_adam_live_launch<true, false>(p, g, m, v, e, table, nr, n_live, 0.0f, 0.0f, 0.0f, 0.0f, eps, weight_decay, 0.0f, state, ema_decay, ema_warmup, st);
+    return 0;
+}
+
+// k_grad_sumsq over the live ranges: one double per block of the grid k_grad_sumsq would use for n_live elements
+// (wn_grad_sumsq_blocks(n_live): a function of n_live alone), scalar loads (a range begins at any element), WN_GN_BATCH of them in
+// flight per thread.  The order is fixed at every level as there -- a thread adds its elements c, c + stride, ... front to back
+// -- and the products are exact in double, so the partials feed k_grad_norm_finalize unchanged and the sum is non-finite exactly
+// when a live element is.
+__global__ __launch_bounds__(WN_TPB) void k_grad_sumsq_live(const float* __restrict__ g, const long* __restrict__ table, int nr,
+                                                            long n_live, double* __restrict__ partial) {
+    __shared__ double red[WN_TPB >> 6];
+    __shared__ long s_lo[WN_LIVE_LDS_RANGES], s_before[WN_LIVE_LDS_RANGES];
+    const WnLiveTable t = wn_live_stage(table, nr, n_live, s_lo, s_before);
+    const long stride = (long)gridDim.x * WN_TPB;
+    double acc = 0.0;
+    long c = (long)blockIdx.x * WN_TPB + threadIdx.x;
+    if (c < n_live) {
+        WnLiveCursor k;
+        wn_live_seek(t, c, 0, &k);
+        for (; c < n_live; c += WN_GN_BATCH * stride) {
+            long idx[WN_GN_BATCH];
+            float x[WN_GN_BATCH];
+            WN_UNROLL
+            for (int j = 0; j < WN_GN_BATCH; ++j) {
+                const long cj = c + j * stride;
+                idx[j] = cj < n_live ? wn_live_index(t, cj, &k) : -1;
+            }
+            WN_UNROLL
+            for (int j = 0; j < WN_GN_BATCH; ++j) x[j] = idx[j] >= 0 ? g[idx[j]] : 0.0f;
+            WN_UNROLL
+            for (int j = 0; j < WN_GN_BATCH; ++j) acc += (double)x[j] * (double)x[j];
+        }
+    }
+    acc = wn_wave_sum_f64(acc);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = red[0];
+        for (int i = 1; i < (WN_TPB >> 6); ++i) s += red[i];
+        partial[blockIdx.x] = s;
+    }
+}
+
+int wn_grad_sumsq_live(const float* g, const long* table, int nr, long n_live, double* partial, wn_stream_t st) {
+    WN_PROF("grad_sumsq_live", 2.0 * (double)n_live, 4.0 * (double)n_live, st);
+    WN_LAUNCH(k_grad_sumsq_live, dim3((unsigned)wn_grad_sumsq_blocks(n_live)), dim3(WN_TPB), 0, st, g, table, nr, n_live, partial);
     return 0;
 }
 

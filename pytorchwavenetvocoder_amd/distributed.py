@@ -36,7 +36,11 @@ class GradientReducer(object):
     (``optimizer.grad_norm``) and the finiteness it judges are therefore the global gradient's, on every rank.  The ranks agree
     on the clip coefficient to the last bit without exchanging it: the all-reduce leaves the same bits in every rank's buffer,
     and the norm's reduction is device-independent (its grid depends on the buffer's length alone and every partial sum has a
-    fixed order, include/wavenet_hip.h), so identical buffers give identical coefficients and the weights cannot drift apart."""
+    fixed order, include/wavenet_hip.h), so identical buffers give identical coefficients and the weights cannot drift apart.
+
+    Frozen parameters change nothing in what is exchanged: whole buckets, in which the ranges of frozen tensors
+    travel as unspecified values nobody reads.  EVERY RANK MUST FREEZE THE SAME SET (nothing checks it): the optimizer of each
+    rank updates the ranges its own model calls live."""
 
     def __init__(self, model, process_group=None, layers_per_bucket=None, exchange_when_alone=False):
         """``layers_per_bucket``: residual layers per gradient bucket = per weight-gradient launch group of wn_backward.

@@ -64,6 +64,27 @@ def _stream_handle(device):
     return None
 
 
+class LiveTable(object):
+    """The live ranges of a flat buffer for the ``*_live`` calls (include/wavenet_hip.h, ABI v16): ``ranges`` the sorted, disjoint
+    ``(lo, hi)`` pairs, ``n_live`` their number of elements, ``table`` the int64 device tensor the kernels read (``lo``, ``hi``
+    and the live elements in front of each range, as ``wn_live_table`` wrote them).  Built by ``WaveNetEngine.live_table``."""
+    __slots__ = ("ranges", "n_ranges", "n_live", "n", "table")
+
+    def __init__(self, ranges, n_live, n, table):
+        self.ranges, self.n_ranges, self.n_live, self.n, self.table = ranges, len(ranges), int(n_live), int(n), table
+
+
+def coalesce_ranges(ranges):
+    """Sorted ``(lo, hi)`` pairs with empty ones dropped and touching or overlapping neighbours merged into maximal runs."""
+    out = []
+    for lo, hi in sorted((int(a), int(b)) for a, b in ranges if int(b) > int(a)):
+        if out and lo <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], hi))
+        else:
+            out.append((lo, hi))
+    return out
+
+
 class WaveNetEngine(object):
     """Owns the flat buffers of one model replica.
 
@@ -126,6 +147,27 @@ class WaveNetEngine(object):
                                                     ctypes.byref(hi)), "wn_bucket_range")
             out.append((lo.value, hi.value))
         return out
+
+    def live_table(self, ranges, n=None, device=None):
+        """``LiveTable`` of the given ``(lo, hi)`` ranges of a buffer of ``n`` elements (default: the flat buffers) on ``device``
+        (default: the engine's).  The ranges are taken as given -- non-empty, sorted, disjoint, inside ``[0, n)``;
+        ``wn_live_table`` checks that and raises through ``wn_last_error`` (``coalesce_ranges`` tidies a list first).  One small
+        host-to-device copy: build it once per freeze set, not per step."""
+        n = self.n_params if n is None else int(n)
+        ranges = [(int(a), int(b)) for a, b in ranges]
+        nr = len(ranges)
+        flat = (ctypes.c_int64 * max(2 * nr, 1))(*[x for r in ranges for x in r])
+        host = torch.zeros(max(3 * nr, 1), dtype=torch.int64)
+        n_live = self.lib.wn_live_table(ctypes.cast(flat, ctypes.c_void_p), nr, n, ctypes.c_void_p(host.data_ptr()))
+        if n_live < 0:
+            raise _lib.WnError("wn_live_table failed: %s" % self.lib.wn_last_error().decode())
+        return LiveTable(ranges, n_live, n, host.to(self.device if device is None else device))
+
+    def _live_args(self, live):
+        self._check_device(live.table)
+        if live.n != self.n_params:
+            raise ValueError("the live table was built for a buffer of %d elements, the flat buffers hold %d" % (live.n, self.n_params))
+        return _ptr(live.table), live.n_ranges, live.n_live
 
     # ---- device management ----------------------------------------------------------------
     def to(self, device):
@@ -557,7 +599,7 @@ class WaveNetEngine(object):
         return row_nll, counts
 
     def backward(self, dlogits, events=None, layers_per_bucket=0, t_first=None, repack=False, dlogits_bound=None, dh=None,
-                 param_grads=True):
+                 param_grads=True, first_layer=0, needs=_lib.NEED_ALL):
         """Backward of the last ``forward`` / ``forward_loss`` call; fills ``self.grads()`` completely.  ``t_first``: the
         caller guarantees ``dlogits[:, :, :t_first] == 0`` (the training loss covers ``[:, receptive_field:]``,
         train.py:534-536): the post-net / skip part of the backward pass then runs over the loss window only
@@ -576,7 +618,13 @@ class WaveNetEngine(object):
 
         ``dh``: a contiguous fp32 tensor shaped like the forward call's ``h`` (B, n_aux, T / upsampling_factor or T) on the
         model's device; it receives dL/dh (``wn_backward_dh``).  ``param_grads=False`` (with ``dh``): no weight gradient is
-        computed (a frozen model), ``self.grads()`` is left as it is and the call returns None."""
+        computed (a frozen model), ``self.grads()`` is left as it is and the call returns None.
+
+        ``first_layer`` / ``needs`` (``wn_backward_needs``; ``WaveNet`` derives them from ``requires_grad``): the lowest layer
+        with a trainable tensor of its own (``n_layers``: none) and ``_lib.NEED_POST | NEED_FRONT | NEED_UP`` for the post-net,
+        the front conv and the upsampling layer.  The pass stops below ``first_layer`` and leaves out the launches only frozen
+        tensors need; the ranges of those tensors in ``self.grads()`` then hold unspecified values.  ``first_layer`` must be 0
+        with ``dh``, ``NEED_FRONT`` or ``NEED_UP``.  The defaults are the full pass, through the entry points of before."""
         if self._last_shape is None:
             raise _lib.WnError("backward() without a preceding forward()")
         if t_first is None:
@@ -621,6 +669,13 @@ class WaveNetEngine(object):
             n_ev = len(events)
         else:
             arr, n_ev = None, 0
+        if int(first_layer) != 0 or int(needs) != _lib.NEED_ALL:
+            rc = self.lib.wn_backward_needs(ctypes.byref(self.cfg), B, T, _ptr(self.flat_params), _ptr(x), _ptr(h), _ptr(dlogits),
+                                            int(t_first), _ptr(g), _ptr(dh), _ptr(ws), ws.numel() * 4, arr, n_ev,
+                                            int(layers_per_bucket), flags, _stream_handle(self.device), int(first_layer),
+                                            int(needs))
+            self.lib.check(rc, "wn_backward_needs")
+            return g
         if dh is not None or not param_grads:
             rc = self.lib.wn_backward_dh(ctypes.byref(self.cfg), B, T, _ptr(self.flat_params), _ptr(x), _ptr(h), _ptr(dlogits),
                                          int(t_first), _ptr(g), _ptr(dh), _ptr(ws), ws.numel() * 4, arr, n_ev,
@@ -633,8 +688,13 @@ class WaveNetEngine(object):
         self.lib.check(rc, "wn_backward_window")
         return g
 
-    def adam_step(self, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def adam_step(self, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, live=None):
+        """One Adam step over the flat buffers without the dead range.  ``live`` (a ``LiveTable``; here and in the three variants
+        below, ``ema`` None or the average): over those ranges only -- everything outside keeps its bits in every buffer,
+        whatever the gradient buffer holds there (``wn_adam_step_live`` / ``wn_adam_step_guarded_live``)."""
         self._check_device(exp_avg, exp_avg_sq)
+        if live is not None:
+            return self._adam_step_live(exp_avg, exp_avg_sq, None, live, step, lr, betas, eps, weight_decay, 0.0, False)
         rc = self.lib.wn_adam_step(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq),
                                    self.n_params, int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
                                    float(weight_decay), self.dead_range[0], self.dead_range[1],
@@ -661,11 +721,38 @@ class WaveNetEngine(object):
         n = self.n_params if n is None else int(n)
         return torch.empty(int(self.lib.wn_grad_norm_scratch_floats(n)), dtype=torch.float32, device=self.device)
 
-    def grad_norm(self, state, scratch, max_norm=0.0, guard=False, lr=1e-3, betas=(0.9, 0.999), grads=None, skip=None):
+    def _adam_step_live(self, exp_avg, exp_avg_sq, ema, live, step, lr, betas, eps, weight_decay, ema_decay, ema_warmup):
+        table, nr, n_live = self._live_args(live)
+        rc = self.lib.wn_adam_step_live(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(ema),
+                                        self.n_params, table, nr, n_live, int(step), float(lr), float(betas[0]), float(betas[1]),
+                                        float(eps), float(weight_decay), float(ema_decay), int(bool(ema_warmup)),
+                                        _stream_handle(self.device))
+        self.lib.check(rc, "wn_adam_step_live")
+        self._params_epoch += 1
+
+    def _adam_step_guarded_live(self, exp_avg, exp_avg_sq, ema, live, state, eps, weight_decay, ema_decay, ema_warmup):
+        table, nr, n_live = self._live_args(live)
+        rc = self.lib.wn_adam_step_guarded_live(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                                _ptr(ema), self.n_params, table, nr, n_live, float(eps), float(weight_decay),
+                                                _ptr(state), float(ema_decay), int(bool(ema_warmup)), _stream_handle(self.device))
+        self.lib.check(rc, "wn_adam_step_guarded_live")
+        self._params_epoch += 1
+
+    def grad_norm(self, state, scratch, max_norm=0.0, guard=False, lr=1e-3, betas=(0.9, 0.999), grads=None, skip=None, live=None):
         """Global L2 norm of the flat gradient (without the dead range) into ``state``, together with everything the guarded
-        Adam launch reads: two launches, no host synchronisation.  ``max_norm`` None / <= 0 / inf: measure only."""
+        Adam launch reads: two launches, no host synchronisation.  ``max_norm`` None / <= 0 / inf: measure only.  ``live`` (a
+        ``LiveTable``): the norm over those ranges of the flat gradient only (``wn_grad_norm_live``)."""
         g = self.grads() if grads is None else grads
         self._check_device(g, scratch, state)
+        if live is not None:
+            if grads is not None or skip is not None:
+                raise ValueError("grad_norm: live ranges belong to the engine's flat gradient (no grads=, no skip=)")
+            table, nr, n_live = self._live_args(live)
+            rc = self.lib.wn_grad_norm_live(_ptr(g), g.numel(), table, nr, n_live, float(max_norm) if max_norm else 0.0,
+                                            int(bool(guard)), float(lr), float(betas[0]), float(betas[1]), _ptr(scratch),
+                                            _ptr(state), _stream_handle(self.device))
+            self.lib.check(rc, "wn_grad_norm_live")
+            return
         lo, hi = self.dead_range if skip is None else skip
         if grads is not None and skip is None:
             lo = hi = 0
@@ -674,10 +761,12 @@ class WaveNetEngine(object):
                                    _stream_handle(self.device))
         self.lib.check(rc, "wn_grad_norm")
 
-    def adam_step_guarded(self, exp_avg, exp_avg_sq, state, eps=1e-8, weight_decay=0.0):
+    def adam_step_guarded(self, exp_avg, exp_avg_sq, state, eps=1e-8, weight_decay=0.0, live=None):
         """``adam_step`` with its scalars (lr / bc1, sqrt(bc2), clip coefficient, apply flag) read from ``state`` as the
         preceding ``grad_norm`` on the same stream left them.  The gradient buffer keeps its unclipped values."""
         self._check_device(exp_avg, exp_avg_sq, state)
+        if live is not None:
+            return self._adam_step_guarded_live(exp_avg, exp_avg_sq, None, live, state, eps, weight_decay, 0.0, False)
         rc = self.lib.wn_adam_step_guarded(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq),
                                            self.n_params, float(eps), float(weight_decay), self.dead_range[0],
                                            self.dead_range[1], _ptr(state), _stream_handle(self.device))
@@ -686,10 +775,12 @@ class WaveNetEngine(object):
 
     # ---- exponential moving average of the weights (include/wavenet_hip.h, ABI v14) -----------------
     def adam_step_ema(self, exp_avg, exp_avg_sq, ema, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.999,
-                      ema_warmup=True):
+                      ema_warmup=True, live=None):
         """``adam_step`` that also moves the flat buffer ``ema`` towards the new weights in the same launch:
         ``ema += (1 - d_t) (p_new - ema)``, ``d_t = min(ema_decay, (1 + step) / (10 + step))`` with the warm-up."""
         self._check_device(exp_avg, exp_avg_sq, ema)
+        if live is not None:
+            return self._adam_step_live(exp_avg, exp_avg_sq, ema, live, step, lr, betas, eps, weight_decay, ema_decay, ema_warmup)
         rc = self.lib.wn_adam_step_ema(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(ema),
                                        self.n_params, int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
                                        float(weight_decay), self.dead_range[0], self.dead_range[1], float(ema_decay),
@@ -698,10 +789,12 @@ class WaveNetEngine(object):
         self._params_epoch += 1
 
     def adam_step_guarded_ema(self, exp_avg, exp_avg_sq, ema, state, eps=1e-8, weight_decay=0.0, ema_decay=0.999,
-                              ema_warmup=True):
+                              ema_warmup=True, live=None):
         """``adam_step_guarded`` with the moving average: the warm-up index is the device's count of applied steps, and a step
         that does not apply leaves ``ema`` alone like everything else."""
         self._check_device(exp_avg, exp_avg_sq, ema, state)
+        if live is not None:
+            return self._adam_step_guarded_live(exp_avg, exp_avg_sq, ema, live, state, eps, weight_decay, ema_decay, ema_warmup)
         rc = self.lib.wn_adam_step_guarded_ema(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq),
                                                _ptr(ema), self.n_params, float(eps), float(weight_decay), self.dead_range[0],
                                                self.dead_range[1], _ptr(state), float(ema_decay), int(bool(ema_warmup)),

@@ -13,6 +13,7 @@ buffer that the kernels, the fused Adam and the RCCL all-reduce operate on.
 There is no CPU path: calling the model with CPU tensors raises.
 """
 import logging
+import re
 import sys
 import time
 
@@ -22,7 +23,46 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import _lib
-from ..engine import WaveNetEngine, _stream_handle, key_to_kind
+from ..engine import WaveNetEngine, _stream_handle, coalesce_ranges, key_to_kind
+
+
+class TrainableSet(object):
+    """What a tuple of per-parameter flags means for the flat buffers (``WaveNet.trainable``)."""
+    __slots__ = ("mask", "ranges", "n_live", "full", "empty", "first_layer", "needs", "_engine", "_table")
+
+    def __init__(self, model, mask):
+        slices = model._param_slices
+        self.mask = mask
+        # what the backward pass has to reach: the lowest layer with a trainable tensor of its own (n_layers: none), pulled down
+        # to 0 by a trainable front conv or upsampling layer (both sit below every layer), and one bit per non-layer part
+        self.first_layer, self.needs = model._engine.n_layers, 0
+        for on, (key, _) in zip(mask, model.named_parameters()):
+            if not on:
+                continue
+            kind, layer = key_to_kind(key)
+            if kind in (_lib.P_POST1_W, _lib.P_POST1_B, _lib.P_POST2_W, _lib.P_POST2_B):
+                self.needs |= _lib.NEED_POST
+            elif kind in (_lib.P_CAUSAL_W, _lib.P_CAUSAL_B):
+                self.needs |= _lib.NEED_FRONT
+            elif kind in (_lib.P_UP_W, _lib.P_UP_B):
+                self.needs |= _lib.NEED_UP
+            else:
+                self.first_layer = min(self.first_layer, layer)
+        if self.needs & (_lib.NEED_FRONT | _lib.NEED_UP):
+            self.first_layer = 0
+        self.ranges = coalesce_ranges((off, off + n) for on, (off, n, shape, dead) in zip(mask, slices) if on and not dead)
+        self.n_live = sum(hi - lo for lo, hi in self.ranges)
+        self.full = all(on or dead for on, (off, n, shape, dead) in zip(mask, slices))
+        self.empty = not self.ranges
+        self._engine, self._table = model._engine, None
+
+    @property
+    def table(self):
+        """The device ``LiveTable`` of the ranges (None when full or empty), built at its first use: the optimizer needs it,
+        the backward pass and the autograd route do not."""
+        if self._table is None and not (self.full or self.empty):
+            self._table = self._engine.live_table(self.ranges)
+        return self._table
 
 
 def encode_mu_law(x, mu=256):
@@ -261,10 +301,13 @@ class _WaveNetFunction(torch.autograd.Function):
         if not any(ctx.needs_input_grad[3:]):   # a frozen model: dh alone
             eng.backward(dl, dh=dh, param_grads=False)
             return (None, None, dh.to(ctx.h_dtype)) + (None,) * len(model._param_slices)
-        flat = eng.backward(dl, dh=dh).clone()
+        # the same needs loss_and_backward derives from requires_grad, here from what autograd asks for
+        ts = model.trainable(ctx.needs_input_grad[3:])
+        needs = {} if ts.full else {"first_layer": 0 if dh is not None else ts.first_layer, "needs": ts.needs}
+        flat = eng.backward(dl, dh=dh, **needs).clone()
         grads = []
-        for (off, n, shape, dead) in model._param_slices:
-            grads.append(None if dead else flat[off:off + n].view(shape))
+        for on, (off, n, shape, dead) in zip(ts.mask, model._param_slices):
+            grads.append(flat[off:off + n].view(shape) if on else None)
         return (None, None, None if dh is None else dh.to(ctx.h_dtype)) + tuple(grads)
 
 
@@ -338,6 +381,7 @@ class WaveNet(nn.Module):
         assert self._engine.receptive_field == self.receptive_field
         self._fwd_serial = 0
         self._param_slices = []
+        self._trainable_cache = {}   # trainable(): flags as given -> TrainableSet
         self._flatten()
 
     # ---- flat storage -------------------------------------------------------------------------
@@ -405,7 +449,10 @@ class WaveNet(nn.Module):
         (reference train.py:533-538) without an autograd graph.
 
         Leaves the gradients in the flat buffer (``p.grad`` of every parameter is a view of it;
-        ``None`` for the dead last ``res_1x1``) and returns the mean loss as a 1-element device
+        ``None`` for the dead last ``res_1x1`` and for every frozen parameter, ``requires_grad`` False:
+        its range of the buffer holds unspecified values that neither ``FusedAdam`` nor its norm reads;
+        with nothing trainable and no ``aux_grad`` the call is forward and loss, no backward launch)
+        and returns the mean loss as a 1-element device
         tensor (no host sync).  ``grad_scale`` multiplies the gradients (1/world_size for DP).
         ``aux_grad=True``: returns ``(loss, dh)`` with dh = d(loss)/dh (scaled by ``grad_scale`` as well).
 
@@ -434,14 +481,95 @@ class WaveNet(nn.Module):
         # forward + loss in one call: the cross-entropy is the epilogue of conv_post_2 where the model allows it (the logits
         # never reach memory), and the backward pass runs its post-net part over the loss window only
         ragged = {} if lengths is None else {"lengths": lengths}
-        loss, dlogits = eng.forward_loss(x, h, t, t_start=t_start, grad_scale=grad_scale, **ragged)
+        ts = self.trainable()
+        nothing = ts.empty and not aux_grad   # forward and loss only: no backward launch
+        loss, dlogits = eng.forward_loss(x, h, t, t_start=t_start, grad_scale=grad_scale, want_grad=not nothing, **ragged)
         self._fwd_serial += 1
+        if nothing:
+            return self._nothing_to_train(loss, events, micro_step, mode)
         dh = self._aux_grad_buffer(h) if aux_grad else None
-        flat = eng.backward(dlogits, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh)
+        flat = eng.backward(dlogits, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh,
+                            **self._backward_needs(ts, aux_grad, events))
         self._finish_micro_step(micro_step, mode, _accumulate)
-        for p, (off, n, shape, dead) in zip(self.parameters(), self._param_slices):
-            p.grad = None if dead else flat[off:off + n].view(shape)
+        self._point_grads(flat)
         return (loss, dh) if aux_grad else loss
+
+    def _backward_needs(self, ts, aux_grad, events=None):
+        """What ``engine.backward`` has to compute for the model's trainable set: nothing extra when every parameter trains (the
+        full pass through the entry points of before), ``first_layer`` / ``needs`` otherwise -- ``first_layer`` 0 with ``dh``,
+        which needs every layer -- and ``param_grads=False`` for ``dh`` alone."""
+        if ts.full:
+            return {}
+        if ts.empty:
+            if events:
+                raise ValueError("bucket events with nothing trainable: there is no gradient to reduce")
+            return {"param_grads": False}
+        return {"first_layer": 0 if aux_grad else ts.first_layer, "needs": ts.needs}
+
+    def _point_grads(self, flat):
+        """``p.grad`` of every trainable parameter = its view of the flat gradient; None for the dead last ``res_1x1`` and for
+        frozen parameters (``requires_grad`` False), whose ranges of the buffer hold unspecified values nobody reads."""
+        for p, (off, n, shape, dead) in zip(self.parameters(), self._param_slices):
+            p.grad = None if (dead or flat is None or not p.requires_grad) else flat[off:off + n].view(shape)
+
+    def _nothing_to_train(self, loss, events, micro_step, mode):
+        """Every parameter frozen and no ``dh`` asked for: the call was forward and loss.  An accumulation cycle still advances
+        and every ``p.grad`` is None.  Bucket events cannot be served (no backward call records them): an error."""
+        if events:
+            raise ValueError("bucket events with nothing trainable: no backward pass runs, so there is no gradient to reduce")
+        if mode is not None:
+            self._engine.end_micro_step(micro_step)
+        for p in self.parameters():
+            p.grad = None
+        return loss
+
+    # ---- frozen parameters (DESIGN.md 3.11) ---------------------------------------------------------------------------------
+    def trainable(self, mask=None):
+        """The trainable set derived from ``mask`` -- one bool per parameter in ``parameters()`` order; default: the
+        parameters' own ``requires_grad``, THE interface for freezing (it may change between steps).  Returns a
+        ``TrainableSet``: ``mask``, ``ranges`` (live ranges of the flat buffers: trainable and not the dead last ``res_1x1``,
+        coalesced into maximal sorted ``[lo, hi)`` runs), ``n_live``, ``full`` (every non-dead parameter: the whole-buffer
+        launches of a model without frozen parameters apply, nothing else is built), ``empty``, and ``table`` (the device
+        ``LiveTable`` of the ranges; None when full or empty).  Rebuilt only when the tuple of flags (or the flat buffer) changes."""
+        # this runs in front of the first launch of every training call, so a hit costs the parameter tuple the engine keeps (no
+        # walk over the module tree) and one dictionary lookup by the flags as given; the rest runs once per tuple of flags
+        raw = tuple(p.requires_grad for p in self._engine._version_sources) if mask is None else tuple(bool(on) for on in mask)
+        key = (raw, self._engine.flat_params.data_ptr(), str(self._engine.device))
+        ts = self._trainable_cache.get(key)
+        if ts is None:
+            if len(raw) != len(self._param_slices):
+                raise ValueError("the mask has %d entries, the model %d parameters" % (len(raw), len(self._param_slices)))
+            if len(self._trainable_cache) >= 8:   # of sets that came and went the oldest goes
+                self._trainable_cache.pop(next(iter(self._trainable_cache)))
+            # (the dead tensors never count: the flags and an optimizer's "has a gradient" then describe the same set)
+            ts = TrainableSet(self, tuple(on and not dead for on, (off, n, shape, dead) in zip(raw, self._param_slices)))
+            self._trainable_cache[key] = ts
+        return ts
+
+    def _set_requires_grad(self, pattern, matched_value, others_value):
+        rx = re.compile(pattern)
+        named = list(self.named_parameters())
+        hits = [rx.search(k) is not None for k, _ in named]
+        if not any(hits):
+            raise ValueError("pattern %r matches no parameter of the model (keys look like %r)" % (pattern, named[0][0]))
+        changed = 0
+        for (k, p), hit in zip(named, hits):
+            want = matched_value if hit else others_value
+            if want is not None and p.requires_grad != want:
+                p.requires_grad_(want)
+                changed += 1
+        return changed
+
+    def freeze(self, pattern):
+        """Freeze (``requires_grad_(False)``) every parameter whose ``named_parameters()`` key ``re.search`` es ``pattern``; the
+        others stay as they are.  Returns the number of tensors changed; ValueError when the pattern matches nothing.  A frozen
+        parameter gets no gradient (``p.grad`` None) and ``FusedAdam`` leaves its weights, moments and average bit for bit."""
+        return self._set_requires_grad(pattern, False, None)
+
+    def train_only(self, pattern):
+        """Train exactly the parameters whose key matches ``pattern``: those become trainable, every other one frozen.
+        Returns the number of tensors changed; ValueError when the pattern matches nothing."""
+        return self._set_requires_grad(pattern, True, False)
 
     def _finish_micro_step(self, micro_step, mode, accumulate):
         """The ``grad_accumulate`` launch of a micro-step behind its backward launches, and the cycle's next state.
@@ -478,13 +606,17 @@ class WaveNet(nn.Module):
         if t_start is None:
             t_start = eng.receptive_field
         ragged = {} if lengths is None else {"lengths": lengths}
+        ts = self.trainable()
+        nothing = ts.empty and not aux_grad   # forward and loss only: no backward launch
         loss, dout = eng.mol_loss(out, y, t_start=t_start, grad_scale=grad_scale, num_classes=num_classes,
-                                  log_scale_min=log_scale_min, **ragged)
+                                  log_scale_min=log_scale_min, want_grad=not nothing, **ragged)
+        if nothing:
+            return self._nothing_to_train(loss, events, micro_step, mode)
         dh = self._aux_grad_buffer(h) if aux_grad else None
-        flat = eng.backward(dout, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh)
+        flat = eng.backward(dout, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh,
+                            **self._backward_needs(ts, aux_grad, events))
         self._finish_micro_step(micro_step, mode, _accumulate)
-        for p, (off, n, shape, dead) in zip(self.parameters(), self._param_slices):
-            p.grad = None if dead else flat[off:off + n].view(shape)
+        self._point_grads(flat)
         return (loss, dh) if aux_grad else loss
 
     def evaluate(self, x, h, t=None, y=None, t_start=None, lengths=None, acc=None, num_classes=65536):

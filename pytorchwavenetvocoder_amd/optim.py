@@ -30,6 +30,20 @@ Gradient accumulation (``loss_and_backward(micro_step=(i, A))``)
 the sum in the gradient buffer this optimizer reads, so the norm, the guard and the average see the accumulated (and reduced)
 gradient and count optimizer steps.  ``step()`` inside an open cycle raises RuntimeError.
 
+Frozen parameters: a live parameter whose ``p.grad`` is None at ``step()`` -- frozen (``requires_grad`` False,
+``WaveNet.freeze`` / ``train_only``; ``loss_and_backward`` then leaves its ``grad`` None) or dropped by the caller -- is left alone
+exactly: weights, both moments and the average keep their bits, no weight decay is applied, and whatever the gradient buffer holds
+in its range (NaN included) reaches neither the norm nor the guard.  The norm and the Adam launch then run over the live ranges
+of the flat buffers (``grad_sumsq_live`` / ``adam*_live``: the same number of launches, a live element gets the bits of the
+whole-buffer launch); with every live parameter holding a gradient they are the whole-buffer launches with their arguments of
+before.  An empty live set issues no launch and counts no step.  ONE STEP COUNT: the optimizer keeps a single count of applied
+steps for the bias correction.  With a freeze set that never changes the step is torch's
+``Adam(p for p in params if p.requires_grad)``; a tensor unfrozen later continues with the moments it has and the optimizer's
+global count, where torch would restart that tensor's own count at 1.  ``state_dict()`` carries an entry for every non-dead
+tensor that has been in the live set of at least one APPLIED step (all of them when nothing is frozen; a step the guard skipped
+does not count; a change of the set reads the device's step count once on the guarded path); ``load_state_dict`` takes
+a missing entry as zero moments.
+
 With all three at their defaults ``step()`` is the one ``adam`` launch with the host's step count, bit for bit as before.
 ``state_dict()`` never holds the average: it stays in torch.optim.Adam's format.
 """
@@ -63,6 +77,9 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError("ema_decay must lie in [0, 1) (None = no moving average)")
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
+        self._trained = [False] * len(model._param_slices)   # per tensor: was in the live set of an APPLIED step (state_dict carries those)
+        self._last_set = None      # the TrainableSet of the last step(); folded into _trained when it changes and by state_dict()
+        self._set_applied0 = 0     # applied steps when _last_set became the current set
         self._ema = None           # the shadow buffer: a copy of the flat weights at its first use
         self._ema_swapped = False  # inside ema_weights(): the two buffers have changed places
 
@@ -186,50 +203,60 @@ class FusedAdam(torch.optim.Optimizer):
         # gradients produced by the autograd path live in separate tensors: gather them
         lo = flat_g.data_ptr()
         hi = lo + flat_g.numel() * 4
-        skipped = []   # live parameters without a gradient: torch.optim.Adam leaves them (and their moments) untouched
+        has_grad = []   # a parameter without a gradient -- frozen, or dropped by the caller -- is left alone, as torch.optim.Adam does
         for p, (off, n, shape, dead) in zip(self.model.parameters(), self.model._param_slices):
-            if p.grad is None:
-                if not dead:
-                    flat_g[off:off + n].zero_()
-                    sl = slice(off, off + n)
-                    skipped.append((sl, eng.flat_params[sl].clone(), m[sl].clone(), v[sl].clone(),
-                                    None if ema is None else ema[sl].clone()))
-                continue
-            if not (lo <= p.grad.data_ptr() < hi):
+            has_grad.append(p.grad is not None)
+            if p.grad is not None and not (lo <= p.grad.data_ptr() < hi):
                 flat_g[off:off + n].copy_(p.grad.reshape(-1))
+        # every live parameter has one: today's launches over the whole buffer.  Otherwise the same kernels' arithmetic over the
+        # live ranges only: what the gradient buffer holds elsewhere is never read, and weights, moments and the
+        # average keep their bits there (no weight decay either).
+        ts = self.model.trainable(has_grad)
+        if ts.empty:
+            return loss   # nothing to update: no launch, and no step is counted
+        live = {} if ts.full else {"live": ts.table}
+        if ts is not self._last_set:
+            # a change of the set (rare) reads the count of applied steps, which on the guarded path lives on the device.  The
+            # test is the identity of the object model.trainable() caches: should the model drop and rebuild the set of the same
+            # flags, this branch runs once more and changes nothing (the fold is idempotent)
+            self._fold_trained()
+            self._set_applied0 = self._step if self._last_set is None else self.steps_applied()
+            self._last_set = ts
         group = self.param_groups[0]
         if self.guarded:
-            # the gather above comes first: the norm is the norm of what the Adam launch reads (zeroed slices of live parameters
-            # without a gradient add 0, which is torch leaving them out)
+            # the gather above comes first: the norm is the norm of what the Adam launch reads
             state, scratch = self._guard_buffers()
-            eng.grad_norm(state, scratch, self.max_grad_norm, self.skip_nonfinite, group["lr"], group["betas"])
+            eng.grad_norm(state, scratch, self.max_grad_norm, self.skip_nonfinite, group["lr"], group["betas"], **live)
             if ema is None:
-                eng.adam_step_guarded(m, v, state, group["eps"], group["weight_decay"])
+                eng.adam_step_guarded(m, v, state, group["eps"], group["weight_decay"], **live)
             else:
-                eng.adam_step_guarded_ema(m, v, ema, state, group["eps"], group["weight_decay"], self.ema_decay, self.ema_warmup)
+                eng.adam_step_guarded_ema(m, v, ema, state, group["eps"], group["weight_decay"], self.ema_decay, self.ema_warmup,
+                                          **live)
         else:
             self._step += 1
             if ema is None:
-                eng.adam_step(m, v, self._step, group["lr"], group["betas"], group["eps"], group["weight_decay"])
+                eng.adam_step(m, v, self._step, group["lr"], group["betas"], group["eps"], group["weight_decay"], **live)
             else:
                 eng.adam_step_ema(m, v, ema, self._step, group["lr"], group["betas"], group["eps"], group["weight_decay"],
-                                  self.ema_decay, self.ema_warmup)
-        for sl, p0, m0, v0, e0 in skipped:   # the one launch covers the whole flat buffer: put the skipped slices back
-            eng.flat_params[sl].copy_(p0)
-            m[sl].copy_(m0)
-            v[sl].copy_(v0)
-            if e0 is not None:
-                ema[sl].copy_(e0)
+                                  self.ema_decay, self.ema_warmup, **live)
         return loss
+
+    def _fold_trained(self):
+        """Mark the tensors of the current set as trained if a step was APPLIED since it became current: a step the non-finite
+        guard skipped trains nothing."""
+        if self._last_set is not None and self.steps_applied() > self._set_applied0:
+            self._trained = [was or (on and not dead) for was, on, (off, n, shape, dead)
+                             in zip(self._trained, self._last_set.mask, self.model._param_slices)]
 
     # ---- torch.optim.Adam compatible (de)serialisation --------------------------------------
     def state_dict(self):
+        self._fold_trained()
         m, v = self._buffers()
         state = {}
         step = self.steps_applied()
         if step > 0:
             for idx, (off, n, shape, dead) in enumerate(self.model._param_slices):
-                if dead:
+                if dead or not self._trained[idx]:   # (a tensor frozen in every step so far has no state, as in torch)
                     continue
                 state[idx] = {"step": torch.tensor(float(step)),
                               "exp_avg": m[off:off + n].view(shape).clone(),
@@ -246,8 +273,11 @@ class FusedAdam(torch.optim.Optimizer):
         m.zero_()
         v.zero_()
         step = 0
+        self._trained = [False] * len(self.model._param_slices)
+        self._last_set = None
         for idx, st in sd["state"].items():
             off, n, shape, dead = self.model._param_slices[int(idx)]
+            self._trained[int(idx)] = True
             m[off:off + n].copy_(st["exp_avg"].reshape(-1))
             v[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
             step = max(step, int(float(st["step"])))
