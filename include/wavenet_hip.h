@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 16
+#define WN_ABI_VERSION 17
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -484,6 +484,71 @@ int wn_adam_step_live(float* params, const float* grads, float* exp_avg, float* 
 int wn_adam_step_guarded_live(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
                               const int64_t* table, int n_ranges, int64_t n_live, float eps, float weight_decay,
                               const WnOptState* state, double ema_decay, int ema_warmup, void* stream);
+
+/* ---- parameter groups: per-group lr, eps and weight decay in ONE Adam launch (since ABI v17; additions only) ----
+ * Betas, the step count with its bias correction, the global gradient norm with its clip coefficient, the apply flag and the
+ * moving average stay one per optimizer.  A group has four values: */
+#define WN_MAX_PARAM_GROUPS 16
+typedef struct WnAdamGroup {
+    float lr;
+    float eps;
+    float weight_decay;
+    int32_t decoupled; /* 0: L2 decay inside the gradient (torch.optim.Adam); != 0: decoupled decay (torch.optim.AdamW) */
+} WnAdamGroup;
+/* What the Adam launch reads per group, 16 bytes.  The unguarded call forms WN_MAX_PARAM_GROUPS of them on the host and passes them
+ * as launch arguments; on the guarded path wn_grad_norm_groups writes them to a caller-owned device block of
+ * WN_MAX_PARAM_GROUPS * sizeof(WnGroupScalars) = 256 bytes (4-byte aligned), which depends on nothing it held before. */
+typedef struct WnGroupScalars {
+    float lr_over_bc1; /* lr_g / (1 - beta1^step), formed in double (0 when the step does not apply) */
+    float eps;
+    float l2;          /* the coefficient of the L2 term: weight_decay_g, 0 for a decoupled group */
+    float scale;       /* f_g = (float)(1.0 - (double)lr_g * (double)weight_decay_g) for a decoupled group, exactly 1 otherwise */
+} WnGroupScalars;
+/* For a live element i of group g at applied step t:
+ *   L2 group         exactly the update of wn_adam_step* with lr_g / bc1, eps_g and weight_decay_g in the places of the global
+ *                    scalars: params, exp_avg, exp_avg_sq and ema receive the bits the single-group entry point (wn_adam_step,
+ *                    _ema, _guarded, _guarded_ema or their _live forms) gives that element for the same inputs, state block and
+ *                    scalars.
+ *   decoupled group  torch.optim.AdamW: p_d = p * f_g as one separately rounded product; the gradient gets no decay term (after
+ *                    clipping it is clip_coef * g[i], as above); the moments as above; p_new = p_d - lr_g / bc1 * (m / denom).
+ *                    With weight_decay_g == 0, f_g is exactly 1 and the element gets the bits of an L2 group with no decay.
+ *
+ * wn_group_table (host only, no launch): wn_live_table for triples lo, hi, group -- the ranges sorted, disjoint, non-empty and
+ * inside [0, n), group in [0, n_groups).  It writes 4 * n_ranges int64 words to `table` (host memory): lo[n_ranges],
+ * hi[n_ranges], before[n_ranges] -- exactly the words wn_live_table writes for the same ranges, so wn_grad_norm_live reads the
+ * table as it is -- and group[n_ranges]; returns n_live, -1 on an error (wn_last_error: those of wn_live_table, a group index
+ * outside [0, n_groups), n_groups outside [1, WN_MAX_PARAM_GROUPS]).  Frozen parameters compose: the ranges are the live ranges
+ * split at group boundaries, and an element outside every range is neither read nor written in any buffer.  A group may own no
+ * range.  The launching calls trust the device copy (8-byte aligned) to be what wn_group_table wrote.
+ *
+ *   wn_adam_step_groups          the unguarded step, ONE launch with the grid, the table cursor and the LDS staging of
+ *                                wn_adam_step_live (the group block is staged beside the table; a thread picks up the four
+ *                                scalars of a range when it enters it; a block walks a contiguous share of the compacted
+ *                                space, so a table with a range per tensor costs no search per element).  The host forms lr_g / bc1, sqrt(bc2) and f_g in double as
+ *                                wn_adam_step does; `groups` is host memory and travels in the launch arguments, so a learning rate
+ *                                that changes every step costs no copy and no synchronisation.  ema == NULL: no moving average.
+ *   wn_grad_norm_groups          two launches.  table == NULL: the sum of squares of wn_grad_norm over [0, n) without
+ *                                [skip_lo, skip_hi) (a model with nothing frozen: the same launch, the same bits); otherwise that
+ *                                of wn_grad_norm_live over the table (skip_lo == skip_hi == 0).  The finalize launch fills `state`
+ *                                bit for bit as wn_grad_norm(_live) does with lr = groups[0].lr (WnOptState keeps its 56 bytes) and
+ *                                writes all WN_MAX_PARAM_GROUPS entries of `group_scalars` (zeros behind n_groups), lr_g / bc1 by
+ *                                the double formula of the state block from the device's count of applied steps.
+ *   wn_adam_step_guarded_groups  wn_adam_step_guarded(_ema) over the table with the scalars of `group_scalars` and `state` as the
+ *                                preceding wn_grad_norm_groups on the same stream left them; when apply == 0 nothing is written
+ *                                in any group.
+ * Errors (wn_last_error): those of the _live calls; groups or group_scalars NULL; n_groups outside [1, WN_MAX_PARAM_GROUPS];
+ * group_scalars not 4-byte aligned; wn_grad_norm_groups with a table AND a skip range, or (table == NULL) a skip range outside
+ * [0, n]. */
+int64_t wn_group_table(const int64_t* triples, int n_ranges, int64_t n, int n_groups, int64_t* table);
+int wn_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                        const int64_t* table, int n_ranges, int64_t n_live, int64_t step, const WnAdamGroup* groups, int n_groups,
+                        float beta1, float beta2, double ema_decay, int ema_warmup, void* stream);
+int wn_grad_norm_groups(const float* grads, int64_t n, const int64_t* table, int n_ranges, int64_t n_live, int64_t skip_lo,
+                        int64_t skip_hi, float max_norm, int guard, const WnAdamGroup* groups, int n_groups, float beta1,
+                        float beta2, float* scratch, WnOptState* state, WnGroupScalars* group_scalars, void* stream);
+int wn_adam_step_guarded_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                const int64_t* table, int n_ranges, int64_t n_live, const WnGroupScalars* group_scalars,
+                                const WnOptState* state, double ema_decay, int ema_warmup, void* stream);
 
 /* ---- op-level entry points (used by the composite calls above; exported for parity tests) ---- */
 

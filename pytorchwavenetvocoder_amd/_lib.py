@@ -68,6 +68,20 @@ class WnOptState(ctypes.Structure):
                 ("beta1", ctypes.c_float), ("beta2", ctypes.c_float)]
 
 
+MAX_PARAM_GROUPS = 16   # WN_MAX_PARAM_GROUPS
+
+
+class WnAdamGroup(ctypes.Structure):
+    """Mirror of ``struct WnAdamGroup`` (include/wavenet_hip.h, ABI v17): the four values of a parameter group."""
+    _fields_ = [("lr", ctypes.c_float), ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float), ("decoupled", ctypes.c_int32)]
+
+
+class WnGroupScalars(ctypes.Structure):
+    """Mirror of ``struct WnGroupScalars``: what the Adam launch reads per group (the guarded path's device block holds
+    ``MAX_PARAM_GROUPS`` of them)."""
+    _fields_ = [("lr_over_bc1", ctypes.c_float), ("eps", ctypes.c_float), ("l2", ctypes.c_float), ("scale", ctypes.c_float)]
+
+
 # tensor kinds (include/wavenet_hip.h)
 (P_CAUSAL_W, P_CAUSAL_B, P_UP_W, P_UP_B, P_DSIG_W, P_DSIG_B, P_DTANH_W, P_DTANH_B, P_ASIG_W, P_ASIG_B,
  P_ATANH_W, P_ATANH_B, P_SKIP_W, P_SKIP_B, P_RES_W, P_RES_B, P_POST1_W, P_POST1_B, P_POST2_W, P_POST2_B) = range(20)
@@ -124,7 +138,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -141,6 +155,7 @@ EXPORTS = [
     "wn_adam_step_ema", "wn_adam_step_guarded_ema", "wn_op_swap",
     "wn_op_accumulate",
     "wn_backward_needs", "wn_live_table", "wn_grad_norm_live", "wn_adam_step_live", "wn_adam_step_guarded_live",
+    "wn_group_table", "wn_adam_step_groups", "wn_grad_norm_groups", "wn_adam_step_guarded_groups",
 ]
 
 
@@ -211,6 +226,13 @@ class WnLibrary(object):
         L.wn_grad_norm_live.argtypes = [vp, i64, vp, i, i64, f, i, f, f, f, vp, vp, vp]
         L.wn_adam_step_live.argtypes = [vp, vp, vp, vp, vp, i64, vp, i, i64, i64, f, f, f, f, f, d, i, vp]
         L.wn_adam_step_guarded_live.argtypes = [vp, vp, vp, vp, vp, i64, vp, i, i64, f, f, vp, d, i, vp]
+        # parameter groups (ABI v17): (host triples, n_ranges, n, n_groups, host table) -> n_live; `groups` is a host array of
+        # WnAdamGroup, `group_scalars` the device block of MAX_PARAM_GROUPS WnGroupScalars
+        L.wn_group_table.argtypes = [vp, i, i64, i, vp]
+        L.wn_group_table.restype = i64
+        L.wn_adam_step_groups.argtypes = [vp, vp, vp, vp, vp, i64, vp, i, i64, i64, vp, i, f, f, d, i, vp]
+        L.wn_grad_norm_groups.argtypes = [vp, i64, vp, i, i64, i64, i64, f, i, vp, i, f, f, vp, vp, vp, vp]
+        L.wn_adam_step_guarded_groups.argtypes = [vp, vp, vp, vp, vp, i64, vp, i, i64, vp, vp, d, i, vp]
         L.wn_op_front.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.wn_op_causal_conv.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.wn_op_causal_conv_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]

@@ -20,6 +20,7 @@ import argparse
 import contextlib
 import logging
 import os
+import re
 import sys
 import time
 
@@ -612,7 +613,38 @@ def get_parser():
                         help="regular expression (re.search on the parameter names): the matching tensors are frozen")
     parser.add_argument("--train_only", default=None, type=str,
                         help="regular expression: only the matching tensors train, every other one is frozen; not together with --freeze")
+    # extension (not a reference flag): parameter groups of FusedAdam
+    parser.add_argument("--param_group", default=None, action="append", type=str, metavar="REGEX:KEY=VALUE[,KEY=VALUE...]",
+                        help="repeatable: the tensors whose name matches REGEX (re.search; the first matching group wins) get "
+                             "their own lr=, weight_decay=, eps= and decoupled=true|false (AdamW's decay); a missing key takes "
+                             "--lr / --weight_decay.  Give the same groups with --resume: the checkpoint's values then win")
     return parser
+
+
+PARAM_GROUP_KEYS = {"lr": "lr", "weight_decay": "weight_decay", "eps": "eps", "decoupled": "decoupled_weight_decay"}
+
+
+def parse_param_group(spec):
+    """``'REGEX:lr=3e-4,weight_decay=0,eps=1e-6,decoupled=true'`` -> ``(regex, dict)`` as ``FusedAdam(groups=)`` takes it.  The
+    values stand behind the LAST colon (a regex may hold one); ValueError with the reason for anything else."""
+    pattern, colon, values = spec.rpartition(":")
+    if not colon or not pattern or not values:
+        raise ValueError("--param_group %r: expected REGEX:KEY=VALUE[,KEY=VALUE...]" % spec)
+    try:
+        re.compile(pattern)
+    except re.error as err:
+        raise ValueError("--param_group %r: bad regular expression (%s)" % (spec, err))
+    out = {}
+    for item in values.split(","):
+        key, eq, value = item.partition("=")
+        key = key.strip()
+        if not eq or key not in PARAM_GROUP_KEYS:
+            raise ValueError("--param_group %r: %r is not one of %s=VALUE" % (spec, item, ", ".join(sorted(PARAM_GROUP_KEYS))))
+        try:
+            out[PARAM_GROUP_KEYS[key]] = bool(strtobool(value.strip())) if key == "decoupled" else float(value)
+        except ValueError:
+            raise ValueError("--param_group %r: bad value in %r" % (spec, item))
+    return pattern, out
 
 
 def _file_lists(waveforms, feats, flag):
@@ -736,10 +768,22 @@ def _worker(rank, world, args, port):
 
     max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
     ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
-    optimizer = FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay,
-                          max_grad_norm=max_grad_norm if max_grad_norm > 0.0 else None,
-                          skip_nonfinite=bool(getattr(args, "skip_nonfinite_steps", False)),
-                          ema_decay=ema_decay if ema_decay > 0.0 else None, ema_warmup=bool(getattr(args, "ema_warmup", True)))
+    groups = [parse_param_group(spec) for spec in (getattr(args, "param_group", None) or [])]   # (main() has checked the syntax)
+    try:
+        optimizer = FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay,
+                              max_grad_norm=max_grad_norm if max_grad_norm > 0.0 else None,
+                              skip_nonfinite=bool(getattr(args, "skip_nonfinite_steps", False)),
+                              ema_decay=ema_decay if ema_decay > 0.0 else None, ema_warmup=bool(getattr(args, "ema_warmup", True)),
+                              **({"groups": groups} if groups else {}))
+    except ValueError as err:
+        if not groups:
+            raise
+        logging.error("--param_group: %s" % err)
+        sys.exit(1)
+    for i, g in enumerate(optimizer.param_groups if groups else []):
+        logging.info("parameter group %d (%s): lr=%g weight_decay=%g eps=%g decoupled=%s, %d tensors, %d elements" % (
+            i, "default" if i == 0 else repr(groups[i - 1][0]), g["lr"], g["weight_decay"], g["eps"],
+            bool(g["decoupled_weight_decay"]), len(g["params"]), sum(p.numel() for p in g["params"])))
     pretrained, freeze, train_only = (getattr(args, k, None) or None for k in ("pretrained", "freeze", "train_only"))
     if pretrained:   # (main() has refused --pretrained beside --resume and --freeze beside --train_only)
         model.load_state_dict(torch.load(pretrained, map_location=lambda storage, loc: storage, weights_only=False)["model"])
@@ -900,6 +944,12 @@ def main(argv=None):
         sys.exit(1)
     if args.freeze and args.train_only:
         logging.error("--freeze and --train_only exclude each other.")
+        sys.exit(1)
+    try:
+        for spec in args.param_group or []:
+            parse_param_group(spec)
+    except ValueError as err:
+        logging.error(str(err))
         sys.exit(1)
     if args.pretrained and args.resume:
         logging.error("--pretrained starts iteration 0 from a checkpoint's weights, --resume continues a run: give one of them.")

@@ -688,3 +688,101 @@ extern "C" int wn_adam_step_guarded_live(float* params, const float* grads, floa
                                 eps, weight_decay, state, ema_decay, ema_warmup, (wn_stream_t)stream));
     return rt_check("wn_adam_step_guarded_live");
 }
+
+// ------------------------------------------------------------------------------------------
+// Parameter groups (ABI v17): the live table with a group index per range, and the three calls that walk it.  The group values
+// are host memory here and launch arguments from here on.
+extern "C" int64_t wn_group_table(const int64_t* triples, int n_ranges, int64_t n, int n_groups, int64_t* table) {
+    g_err[0] = 0;   // pure host code: no runtime call to clear
+    if (!triples || !table) return fail(1, "wn_group_table: NULL argument"), -1;
+    if (n_ranges <= 0) return fail(1, "wn_group_table: an empty table (n_ranges = %d)", n_ranges), -1;
+    if (n <= 0) return fail(1, "wn_group_table: n <= 0"), -1;
+    if (n_groups < 1 || n_groups > WN_MAX_PARAM_GROUPS) return fail(1, "wn_group_table: n_groups = %d outside [1, %d]", n_groups, WN_MAX_PARAM_GROUPS), -1;
+    int64_t before = 0, prev_hi = 0;
+    for (int r = 0; r < n_ranges; ++r) {
+        const int64_t lo = triples[3 * r], hi = triples[3 * r + 1], grp = triples[3 * r + 2];
+        if (lo < 0 || hi > n) return fail(1, "wn_group_table: range %d = [%lld, %lld) outside [0, %lld)", r, (long long)lo, (long long)hi, (long long)n), -1;
+        if (hi <= lo) return fail(1, "wn_group_table: range %d = [%lld, %lld) is empty", r, (long long)lo, (long long)hi), -1;
+        if (r > 0 && lo < prev_hi) return fail(1, "wn_group_table: range %d = [%lld, %lld) is not behind range %d (the ranges must be sorted and disjoint)", r, (long long)lo, (long long)hi, r - 1), -1;
+        if (grp < 0 || grp >= n_groups) return fail(1, "wn_group_table: range %d has group %lld outside [0, %d)", r, (long long)grp, n_groups), -1;
+        table[r] = lo;
+        table[n_ranges + r] = hi;
+        table[2 * (int64_t)n_ranges + r] = before;
+        table[3 * (int64_t)n_ranges + r] = grp;
+        before += hi - lo;
+        prev_hi = hi;
+    }
+    return before;
+}
+
+static const char* group_argument_error(const WnAdamGroup* groups, int n_groups) {
+    if (!groups) return "groups is NULL";
+    if (n_groups < 1 || n_groups > WN_MAX_PARAM_GROUPS) return "n_groups outside [1, WN_MAX_PARAM_GROUPS]";
+    return nullptr;
+}
+
+static const char* group_block_error(const WnGroupScalars* block) {
+    if (!block) return "group_scalars is NULL";
+    if (reinterpret_cast<uintptr_t>(block) & 3) return "group_scalars needs 4-byte alignment";
+    return nullptr;
+}
+
+extern "C" int wn_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                   const int64_t* table, int n_ranges, int64_t n_live, int64_t step, const WnAdamGroup* groups,
+                                   int n_groups, float beta1, float beta2, double ema_decay, int ema_warmup, void* stream) {
+    api_enter();
+    if (!adam_buffers_ok(params, grads, exp_avg, exp_avg_sq, n) || step < 1) return fail(1, "bad wn_adam_step_groups argument");
+    if (const char* why = live_argument_error(table, n_ranges, n_live, n)) return fail(1, "wn_adam_step_groups: %s", why);
+    if (const char* why = group_argument_error(groups, n_groups)) return fail(1, "wn_adam_step_groups: %s", why);
+    if (ema)
+        if (const char* why = ema_argument_error(params, ema, n, ema_decay)) return fail(1, "wn_adam_step_groups: %s", why);
+    // the two double formulas of adam_bias, bc1 kept in double for every group's quotient
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    WnGroupScalars block[WN_MAX_PARAM_GROUPS] = {};
+    for (int i = 0; i < n_groups; ++i) block[i] = wn_group_scalars(groups[i], bc1, true);
+    WN_TRY(wn_adam_groups(params, grads, exp_avg, exp_avg_sq, ema, reinterpret_cast<const long*>(table), n_ranges, (long)n_live, block,
+                          (float)sqrt(bc2), beta1, beta2, ema ? wn_ema_weight(ema_decay, ema_warmup, step) : 0.0f,
+                          (wn_stream_t)stream));
+    return rt_check("wn_adam_step_groups");
+}
+
+extern "C" int wn_grad_norm_groups(const float* grads, int64_t n, const int64_t* table, int n_ranges, int64_t n_live, int64_t skip_lo,
+                                   int64_t skip_hi, float max_norm, int guard, const WnAdamGroup* groups, int n_groups, float beta1,
+                                   float beta2, float* scratch, WnOptState* state, WnGroupScalars* group_scalars, void* stream) {
+    api_enter();
+    if (!grads || !scratch || !state || n <= 0) return fail(1, "bad wn_grad_norm_groups argument");
+    if (const char* why = group_argument_error(groups, n_groups)) return fail(1, "wn_grad_norm_groups: %s", why);
+    if (const char* why = group_block_error(group_scalars)) return fail(1, "wn_grad_norm_groups: %s", why);
+    if ((reinterpret_cast<uintptr_t>(grads) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 7) || (reinterpret_cast<uintptr_t>(state) & 7))
+        return fail(1, "wn_grad_norm_groups: grads needs 4-byte, scratch and state 8-byte alignment");
+    double* partial = reinterpret_cast<double*>(scratch);
+    int nb;
+    if (table) {
+        if (const char* why = live_argument_error(table, n_ranges, n_live, n)) return fail(1, "wn_grad_norm_groups: %s", why);
+        if (skip_lo != 0 || skip_hi != 0) return fail(1, "wn_grad_norm_groups: a table and a skip range (the table's ranges say what is read)");
+        WN_TRY(wn_grad_sumsq_live(grads, reinterpret_cast<const long*>(table), n_ranges, (long)n_live, partial, (wn_stream_t)stream));
+        nb = wn_grad_sumsq_blocks((long)n_live);
+    } else {
+        if (skip_lo < 0 || skip_hi > n || skip_lo > skip_hi) return fail(1, "wn_grad_norm_groups: skip range outside [0, n]");
+        WN_TRY(wn_grad_sumsq(grads, (long)n, (long)skip_lo, (long)skip_hi, partial, (wn_stream_t)stream));
+        nb = wn_grad_sumsq_blocks((long)n);
+    }
+    WN_TRY(wn_grad_norm_finalize_groups(partial, nb, max_norm, guard != 0, groups, n_groups, beta1, beta2, state, group_scalars,
+                                        (wn_stream_t)stream));
+    return rt_check("wn_grad_norm_groups");
+}
+
+extern "C" int wn_adam_step_guarded_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                           const int64_t* table, int n_ranges, int64_t n_live, const WnGroupScalars* group_scalars,
+                                           const WnOptState* state, double ema_decay, int ema_warmup, void* stream) {
+    api_enter();
+    if (!adam_buffers_ok(params, grads, exp_avg, exp_avg_sq, n) || !state) return fail(1, "bad wn_adam_step_guarded_groups argument");
+    if (const char* why = live_argument_error(table, n_ranges, n_live, n)) return fail(1, "wn_adam_step_guarded_groups: %s", why);
+    if (const char* why = group_block_error(group_scalars)) return fail(1, "wn_adam_step_guarded_groups: %s", why);
+    if (ema)
+        if (const char* why = ema_argument_error(params, ema, n, ema_decay)) return fail(1, "wn_adam_step_guarded_groups: %s", why);
+    WN_TRY(wn_adam_guarded_groups(params, grads, exp_avg, exp_avg_sq, ema, reinterpret_cast<const long*>(table), n_ranges, (long)n_live,
+                                  group_scalars, state, ema_decay, ema_warmup, (wn_stream_t)stream));
+    return rt_check("wn_adam_step_guarded_groups");
+}

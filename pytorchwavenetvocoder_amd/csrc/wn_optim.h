@@ -1,8 +1,10 @@
 // wn_optim.h -- launchers of the optimizer-side kernels (wn_optim.inl): Adam over a flat fp32 buffer in its four variants, the
 // global gradient norm, the in-place exchange of two buffers and gradient accumulation.  They depend on nothing of the network:
-// struct WnOptState and WN_ACCUM_* (include/wavenet_hip.h) are all they share with the rest of the library.
+// struct WnOptState, the group structs and WN_ACCUM_* (include/wavenet_hip.h) are all they share with the rest of the library.
 #pragma once
 #include "wn_device.h"
+
+#include "../../include/wavenet_hip.h"   // struct WnAdamGroup, struct WnGroupScalars, WN_MAX_PARAM_GROUPS
 
 // Adam over a flat fp32 buffer (torch.optim.Adam semantics, train.py:457-460): elements in
 // [skip_lo, skip_hi) are left untouched (parameters that never receive a gradient).
@@ -49,6 +51,30 @@ int wn_adam_guarded_live(float* p, const float* g, float* m, float* v, float* e,
                          float weight_decay, const struct WnOptState* state, double ema_decay, int ema_warmup, wn_stream_t st);
 // wn_grad_sumsq_blocks(n_live) partials for wn_grad_norm_finalize
 int wn_grad_sumsq_live(const float* g, const long* table, int nr, long n_live, double* partial, wn_stream_t st);
+// The Adam launches over PARAMETER GROUPS (include/wavenet_hip.h, ABI v17): `table` is the device copy of what wn_group_table wrote
+// (lo[nr], hi[nr], before[nr], group[nr]), the grid and the walk are those of wn_adam_live, and every range is updated with the
+// four scalars of its group.  wn_adam_groups takes the group block from the host (`block`: WN_MAX_PARAM_GROUPS entries, passed
+// on as a launch argument), wn_adam_guarded_groups reads the device block wn_grad_norm_finalize_groups left behind the state
+// block it fills exactly as wn_grad_norm_finalize does with lr = groups[0].lr.  e == NULL: no moving average.
+// The ONE place a group's four scalars are formed, in double, for the host (unguarded step: bc1 from the caller's step) and for
+// the finalize launch (guarded: bc1 from the device's count): the same inputs give the same bits on both paths.
+static __host__ __device__ __forceinline__ WnGroupScalars wn_group_scalars(const WnAdamGroup& a, double bc1, bool apply) {
+    WnGroupScalars s;
+    s.lr_over_bc1 = apply ? (float)((double)a.lr / bc1) : 0.0f;
+    s.eps = a.eps;
+    s.l2 = a.decoupled ? 0.0f : a.weight_decay;
+    s.scale = a.decoupled ? (float)(1.0 - (double)a.lr * (double)a.weight_decay) : 1.0f;
+    return s;
+}
+
+int wn_adam_groups(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live,
+                   const struct WnGroupScalars* block, float sqrt_bc2, float beta1, float beta2, float w, wn_stream_t st);
+int wn_adam_guarded_groups(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live,
+                           const struct WnGroupScalars* dev_block, const struct WnOptState* state, double ema_decay, int ema_warmup,
+                           wn_stream_t st);
+int wn_grad_norm_finalize_groups(const double* partial, int nb, float max_norm, int guard, const struct WnAdamGroup* groups,
+                                 int n_groups, float beta1, float beta2, struct WnOptState* state, struct WnGroupScalars* block,
+                                 wn_stream_t st);
 // a[i] <-> b[i], i < n: two non-overlapping fp32 buffers of 4-byte alignment, exchanged in place
 int wn_swap(float* a, float* b, long n, wn_stream_t st);
 // gradient accumulation over micro-batches (include/wavenet_hip.h WN_ACCUM_*, ABI v15): SET acc = grad, ADD acc = acc + grad,

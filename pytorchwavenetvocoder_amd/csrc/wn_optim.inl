@@ -42,12 +42,16 @@ static unsigned wn_quad_blocks(long n, long cap) {
 // Both are compile-time: a plain kernel carries no multiply by a coefficient and no access to e.  p, m and v get the same bits
 // from all four kernels because there is one expression for them (wn_adam_element), which no flag changes: GUARDED only puts a
 // separately rounded product in place of g[i], and the EMA only reads pn.  The kernels over live ranges (below) call the same one.
-template <bool GUARDED, bool EMA>
+//   SCALE    (the kernels over parameter groups only) the weight enters as the separately rounded product
+//            pscale * p[i]: torch.optim.AdamW's decoupled decay, p *= 1 - lr wd, in front of an update whose gradient carries no
+//            decay term (such a group passes wd = 0).  An L2 group passes pscale = 1, which is exact: the arithmetic below is the
+//            one of SCALE = false, which no other kernel leaves.
+template <bool GUARDED, bool EMA, bool SCALE = false>
 static __device__ __forceinline__ void wn_adam_element(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, float* __restrict__ e, long i, float lr_over_bc1,
                                                        float sqrt_bc2, float coef, float beta1, float beta2, float eps, float wd,
-                                                       float w) {
-    const float pv = p[i];
+                                                       float w, float pscale = 1.0f) {
+    const float pv = SCALE ? wn_fmul_rn(pscale, p[i]) : p[i];
     float ev = 0.0f;
     if (EMA) ev = e[i];
     // never contracted into the decay term's fma: coef == 1 leaves the unguarded arithmetic
@@ -211,9 +215,11 @@ int wn_grad_sumsq(const float* g, long n, long skip_lo, long skip_hi, double* pa
 }
 
 // One block: the partials in a fixed order, then every scalar the guarded Adam launch reads.  Everything in the state block except
-// the two step counters is written from scratch (nothing depends on what the block held before).
-__global__ __launch_bounds__(WN_TPB) void k_grad_norm_finalize(const double* __restrict__ partial, int nb, float max_norm, int guard,
-                                                               float lr, float beta1, float beta2, WnOptState* __restrict__ state) {
+// the two step counters is written from scratch (nothing depends on what the block held before).  Written once for the two
+// finalize kernels; true for the one thread that wrote the block, *bc1_out = this step's 1 - beta1^steps_applied (when it applies).
+static __device__ __forceinline__ bool wn_finalize_state(const double* __restrict__ partial, int nb, float max_norm, int guard,
+                                                         float lr, float beta1, float beta2, WnOptState* __restrict__ state,
+                                                         double* bc1_out) {
     __shared__ double red[WN_TPB >> 6];
     double acc = 0.0;
     for (int i = threadIdx.x; i < nb; i += WN_TPB) acc += partial[i];
@@ -221,7 +227,7 @@ __global__ __launch_bounds__(WN_TPB) void k_grad_norm_finalize(const double* __r
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) red[wave] = acc;
     __syncthreads();
-    if (threadIdx.x != 0) return;
+    if (threadIdx.x != 0) return false;
     double s = red[0];
     for (int i = 1; i < (WN_TPB >> 6); ++i) s += red[i];
     // judged on the double sum (exponent field not all ones): finite elements, +-3e38 included, can never make it inf or NaN
@@ -242,6 +248,7 @@ __global__ __launch_bounds__(WN_TPB) void k_grad_norm_finalize(const double* __r
     state->reserved = 0;
     state->beta1 = beta1;
     state->beta2 = beta2;
+    *bc1_out = 0.0;
     if (apply) {
         const int64_t step = state->steps_applied + 1;
         state->steps_applied = step;
@@ -250,11 +257,19 @@ __global__ __launch_bounds__(WN_TPB) void k_grad_norm_finalize(const double* __r
         const double bc2 = 1.0 - pow((double)beta2, (double)step);
         state->lr_over_bc1 = (float)((double)lr / bc1);
         state->sqrt_bc2 = (float)sqrt(bc2);
+        *bc1_out = bc1;
     } else {
         state->steps_skipped = state->steps_skipped + 1;
         state->lr_over_bc1 = 0.0f;
         state->sqrt_bc2 = 0.0f;
     }
+    return true;
+}
+
+__global__ __launch_bounds__(WN_TPB) void k_grad_norm_finalize(const double* __restrict__ partial, int nb, float max_norm, int guard,
+                                                               float lr, float beta1, float beta2, WnOptState* __restrict__ state) {
+    double bc1;
+    wn_finalize_state(partial, nb, max_norm, guard, lr, beta1, beta2, state, &bc1);
 }
 
 int wn_grad_norm_finalize(const double* partial, int nb, float max_norm, int guard, float lr, float beta1, float beta2,
@@ -419,6 +434,128 @@ __global__ __launch_bounds__(WN_TPB) void k_grad_sumsq_live(const float* __restr
 int wn_grad_sumsq_live(const float* g, const long* table, int nr, long n_live, double* partial, wn_stream_t st) {
     WN_PROF("grad_sumsq_live", 2.0 * (double)n_live, 4.0 * (double)n_live, st);
     WN_LAUNCH(k_grad_sumsq_live, dim3((unsigned)wn_grad_sumsq_blocks(n_live)), dim3(WN_TPB), 0, st, g, table, nr, n_live, partial);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adam over PARAMETER GROUPS (ABI v17): the ranges of a live table carry a group index, table word 3 nr + r
+// (wn_group_table writes it), and a group is four scalars, WnGroupScalars: lr / bc1, eps, the L2 coefficient and the decoupled
+// factor.  Betas, sqrt(bc2), the clip coefficient, the apply flag and the averaging weight stay one per launch.  The grid, the
+// cursor and the element are those of k_adam_live (a block's share of the compacted space is contiguous here, see below); a thread that enters a range picks up that range's four scalars and holds them
+// in registers until it leaves it.  Lanes of one wave may sit in different groups, so the scalars are per-lane values: an array
+// in the kernel arguments would be read by scalar loads, which a per-lane index turns into a loop over the distinct values of the
+// wave.  The group block (256 bytes) is therefore staged in LDS beside the table by every block, one 16-byte read per range
+// entered, and the group indices of a staged table as bytes (1 KiB, not a third more table).  The unguarded launch takes the
+// block as an argument, by value: a learning rate that changes every step costs no copy.  The guarded one reads the block
+// k_grad_norm_finalize_groups left in device memory.
+struct WnGroupBlock {
+    WnGroupScalars g[WN_MAX_PARAM_GROUPS];
+};
+
+template <bool GUARDED, bool EMA>
+__global__ __launch_bounds__(WN_TPB) void k_adam_groups(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* __restrict__ e, const long* __restrict__ table,
+                                                        int nr, long n_live, float sqrt_bc2, float beta1, float beta2, float w,
+                                                        WnGroupBlock host_block, const WnGroupScalars* __restrict__ dev_block,
+                                                        const WnOptState* __restrict__ state, double ema_decay, int ema_warmup) {
+    __shared__ long s_lo[WN_LIVE_LDS_RANGES], s_before[WN_LIVE_LDS_RANGES];
+    __shared__ unsigned char s_group[WN_LIVE_LDS_RANGES];
+    __shared__ WnGroupScalars s_block[WN_MAX_PARAM_GROUPS];
+    float coef = 1.0f;
+    if (GUARDED) {
+        if (!state->apply) return;
+        sqrt_bc2 = state->sqrt_bc2;
+        coef = state->clip_coef;
+        beta1 = state->beta1;
+        beta2 = state->beta2;
+        if (EMA) w = wn_ema_weight(ema_decay, ema_warmup, state->steps_applied);
+    }
+    const long* group = table + 3 * (long)nr;
+    const bool staged = nr <= WN_LIVE_LDS_RANGES;
+    if (threadIdx.x < WN_MAX_PARAM_GROUPS) s_block[threadIdx.x] = GUARDED ? dev_block[threadIdx.x] : host_block.g[threadIdx.x];
+    if (staged)
+        for (int i = threadIdx.x; i < nr; i += WN_TPB) s_group[i] = (unsigned char)group[i];
+    const WnLiveTable t = wn_live_stage(table, nr, n_live, s_lo, s_before);
+    if (!staged) __syncthreads();   // (wn_live_stage has no barrier of its own then)
+    // A block walks ONE contiguous share of the compacted space (whole trips of the block), a thread WN_TPB elements per trip:
+    // the cursor then leaves a range only where the share really crosses its end -- one step to the next range.  With the
+    // grid-wide stride of k_adam_live a table of a range per tensor (biases against weights) has a thread jump several ranges
+    // on nearly every trip, a bisection of dependent LDS reads each time, which at one element in flight per thread doubled
+    // the launch (profiles/groups/NOTES.md).
+    const long share = ((n_live + gridDim.x - 1) / gridDim.x + WN_TPB - 1) / WN_TPB * WN_TPB;
+    const long last = ((long)blockIdx.x + 1) * share < n_live ? ((long)blockIdx.x + 1) * share : n_live;
+    long c = (long)blockIdx.x * share + threadIdx.x;
+    if (c >= last) return;
+    WnLiveCursor k;
+    wn_live_seek(t, c, 0, &k);
+    int held = -1;
+    WnGroupScalars s = {0.0f, 0.0f, 0.0f, 1.0f};
+    for (; c < last; c += WN_TPB) {
+        const long i = wn_live_index(t, c, &k);
+        if (k.r != held) {
+            held = k.r;
+            s = s_block[(staged ? (int)s_group[held] : (int)group[held]) & (WN_MAX_PARAM_GROUPS - 1)];
+        }
+        wn_adam_element<GUARDED, EMA, true>(p, g, m, v, e, i, s.lr_over_bc1, sqrt_bc2, coef, beta1, beta2, s.eps, s.l2, w, s.scale);
+    }
+}
+
+template <bool GUARDED, bool EMA>
+static void wn_adam_groups_launch(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live,
+                                  float sqrt_bc2, float beta1, float beta2, float w, const WnGroupBlock& host_block,
+                                  const WnGroupScalars* dev_block, const WnOptState* state, double ema_decay, int ema_warmup,
+                                  wn_stream_t st) {
+    auto kernel = k_adam_groups<GUARDED, EMA>;
+    WN_LAUNCH(kernel, dim3(wn_adam_blocks(n_live)), dim3(WN_TPB), 0, st, p, g, m, v, e, table, nr, n_live, sqrt_bc2, beta1, beta2, w,
+              host_block, dev_block, state, ema_decay, ema_warmup);
+}
+
+int wn_adam_groups(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live,
+                   const WnGroupScalars* block, float sqrt_bc2, float beta1, float beta2, float w, wn_stream_t st) {
+    WN_PROF(e ? "adam_ema_groups" : "adam_groups", 0.0, (e ? 36.0 : 28.0) * (double)n_live, st);
+    WnGroupBlock b;
+    for (int i = 0; i < WN_MAX_PARAM_GROUPS; ++i) b.g[i] = block[i];
+    if (e) wn_adam_groups_launch<false, true>(p, g, m, v, e, table, nr, n_live, sqrt_bc2, beta1, beta2, w, b, nullptr, nullptr, 0.0, 0, st);
+    else wn_adam_groups_launch<false, false>(p, g, m, v, e, table, nr, n_live, sqrt_bc2, beta1, beta2, w, b, nullptr, nullptr, 0.0, 0, st);
+    return 0;
+}
+
+int wn_adam_guarded_groups(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live,
+                           const WnGroupScalars* dev_block, const WnOptState* state, double ema_decay, int ema_warmup,
+                           wn_stream_t st) {
+    WN_PROF(e ? "adam_guarded_ema_groups" : "adam_guarded_groups", 0.0, (e ? 36.0 : 28.0) * (double)n_live, st);
+    const WnGroupBlock b = {};
+    if (e) wn_adam_groups_launch<true, true>(p, g, m, v, e, table, nr, n_live, 0.0f, 0.0f, 0.0f, 0.0f, b, dev_block, state, ema_decay, ema_warmup, st);
+    else wn_adam_groups_launch<true, false>(p, g, m, v, e, table, nr, n_live, 0.0f, 0.0f, 0.0f, 0.0f, b, dev_block, state, ema_decay, ema_warmup, st);
+    return 0;
+}
+
+// k_grad_norm_finalize with group 0's lr in the state block (the same words, bit for bit), and the group block behind it: all
+// WN_MAX_PARAM_GROUPS entries are written (zeros behind n_groups); a step that does not apply leaves lr / bc1 = 0 in every group,
+// as it does in the state block.
+struct WnAdamGroupArgs {
+    WnAdamGroup g[WN_MAX_PARAM_GROUPS];
+};
+__global__ __launch_bounds__(WN_TPB) void k_grad_norm_finalize_groups(const double* __restrict__ partial, int nb, float max_norm,
+                                                                      int guard, WnAdamGroupArgs groups, int n_groups, float beta1,
+                                                                      float beta2, WnOptState* __restrict__ state,
+                                                                      WnGroupScalars* __restrict__ block) {
+    double bc1;
+    if (!wn_finalize_state(partial, nb, max_norm, guard, groups.g[0].lr, beta1, beta2, state, &bc1)) return;
+    const bool apply = state->apply != 0;
+    for (int i = 0; i < WN_MAX_PARAM_GROUPS; ++i) {
+        const WnGroupScalars zero = {0.0f, 0.0f, 0.0f, 0.0f};
+        block[i] = i < n_groups ? wn_group_scalars(groups.g[i], bc1, apply) : zero;
+    }
+}
+
+int wn_grad_norm_finalize_groups(const double* partial, int nb, float max_norm, int guard, const WnAdamGroup* groups, int n_groups,
+                                 float beta1, float beta2, WnOptState* state, WnGroupScalars* block, wn_stream_t st) {
+    WN_PROF("grad_norm_finalize", 0.0, 8.0 * (double)nb, st);
+    WnAdamGroupArgs a = {};
+    for (int i = 0; i < n_groups; ++i) a.g[i] = groups[i];
+    WN_LAUNCH(k_grad_norm_finalize_groups, dim3(1), dim3(WN_TPB), 0, st, partial, nb, max_norm, guard, a, n_groups, beta1, beta2, state,
+              block);
     return 0;
 }
 

@@ -74,6 +74,26 @@ class LiveTable(object):
         self.ranges, self.n_ranges, self.n_live, self.n, self.table = ranges, len(ranges), int(n_live), int(n), table
 
 
+class GroupTable(LiveTable):
+    """A ``LiveTable`` whose ranges carry a parameter-group index (include/wavenet_hip.h, ABI v17): ``groups`` one index per
+    range, ``n_groups`` the number of groups the indices refer to; ``table`` holds a fourth row, the indices, behind the three of
+    a ``LiveTable`` (the ``*_live`` calls read it as it is).  Built by ``WaveNetEngine.group_table``."""
+    __slots__ = ("groups", "n_groups")
+
+    def __init__(self, ranges, groups, n_groups, n_live, n, table):
+        LiveTable.__init__(self, ranges, n_live, n, table)
+        self.groups, self.n_groups = groups, int(n_groups)
+
+
+def group_array(groups):
+    """Host array of ``WnAdamGroup`` from ``(lr, eps, weight_decay, decoupled)`` tuples: what the ``*_groups`` calls take (the values
+    travel in the launch arguments)."""
+    arr = (_lib.WnAdamGroup * max(len(groups), 1))()
+    for a, (lr, eps, wd, decoupled) in zip(arr, groups):
+        a.lr, a.eps, a.weight_decay, a.decoupled = float(lr), float(eps), float(wd), int(bool(decoupled))
+    return arr
+
+
 def coalesce_ranges(ranges):
     """Sorted ``(lo, hi)`` pairs with empty ones dropped and touching or overlapping neighbours merged into maximal runs."""
     out = []
@@ -162,6 +182,21 @@ class WaveNetEngine(object):
         if n_live < 0:
             raise _lib.WnError("wn_live_table failed: %s" % self.lib.wn_last_error().decode())
         return LiveTable(ranges, n_live, n, host.to(self.device if device is None else device))
+
+    def group_table(self, triples, n_groups, n=None, device=None):
+        """``GroupTable`` of the given ``(lo, hi, group)`` triples -- ranges as for ``live_table``, ``group`` in
+        ``[0, n_groups)``, ``n_groups`` at most ``_lib.MAX_PARAM_GROUPS``; ``wn_group_table`` checks all of it.  One small
+        host-to-device copy: build it once per set of live ranges, not per step."""
+        n = self.n_params if n is None else int(n)
+        triples = [(int(a), int(b), int(c)) for a, b, c in triples]
+        nr = len(triples)
+        flat = (ctypes.c_int64 * max(3 * nr, 1))(*[x for r in triples for x in r])
+        host = torch.zeros(max(4 * nr, 1), dtype=torch.int64)
+        n_live = self.lib.wn_group_table(ctypes.cast(flat, ctypes.c_void_p), nr, n, int(n_groups), ctypes.c_void_p(host.data_ptr()))
+        if n_live < 0:
+            raise _lib.WnError("wn_group_table failed: %s" % self.lib.wn_last_error().decode())
+        return GroupTable([(a, b) for a, b, _ in triples], [c for _, _, c in triples], n_groups, n_live, n,
+                          host.to(self.device if device is None else device))
 
     def _live_args(self, live):
         self._check_device(live.table)
@@ -800,6 +835,59 @@ class WaveNetEngine(object):
                                                self.dead_range[1], _ptr(state), float(ema_decay), int(bool(ema_warmup)),
                                                _stream_handle(self.device))
         self.lib.check(rc, "wn_adam_step_guarded_ema")
+        self._params_epoch += 1
+
+    # ---- parameter groups (include/wavenet_hip.h, ABI v17) -----------------------------------------
+    def new_group_scalars(self):
+        """The device block of per-group scalars ``grad_norm_groups`` writes and ``adam_step_guarded_groups`` reads (256 bytes;
+        allocate it once per optimizer)."""
+        return torch.zeros(_lib.MAX_PARAM_GROUPS * ctypes.sizeof(_lib.WnGroupScalars) // 4, dtype=torch.float32, device=self.device)
+
+    def _group_args(self, table, groups):
+        if not isinstance(table, GroupTable):
+            raise TypeError("the *_groups calls take a GroupTable (WaveNetEngine.group_table)")
+        if len(groups) != table.n_groups:
+            raise ValueError("%d groups given, the table was built for %d" % (len(groups), table.n_groups))
+        return group_array(groups), len(groups)
+
+    def adam_step_groups(self, exp_avg, exp_avg_sq, ema, table, step, groups, betas=(0.9, 0.999), ema_decay=0.0, ema_warmup=False):
+        """One Adam step over the ranges of ``table`` (a ``GroupTable``), each with the ``(lr, eps, weight_decay, decoupled)`` of
+        its group: one launch (``wn_adam_step_groups``).  ``ema`` None or the average."""
+        self._check_device(exp_avg, exp_avg_sq, ema)
+        tab, nr, n_live = self._live_args(table)
+        arr, ng = self._group_args(table, groups)
+        rc = self.lib.wn_adam_step_groups(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(ema),
+                                          self.n_params, tab, nr, n_live, int(step), ctypes.cast(arr, ctypes.c_void_p), ng,
+                                          float(betas[0]), float(betas[1]), float(ema_decay), int(bool(ema_warmup)),
+                                          _stream_handle(self.device))
+        self.lib.check(rc, "wn_adam_step_groups")
+        self._params_epoch += 1
+
+    def grad_norm_groups(self, state, scratch, group_scalars, table, groups, max_norm=0.0, guard=False, betas=(0.9, 0.999),
+                         whole=False):
+        """``grad_norm`` for a grouped step: ``state`` as ``grad_norm`` fills it with group 0's lr, and every group's scalars in
+        ``group_scalars``.  ``whole``: the ranges of ``table`` are all of the buffer but the dead range (nothing frozen), and
+        the sum of squares is the whole-buffer launch of ``grad_norm``; otherwise that of ``grad_norm(live=)`` over the table."""
+        g = self.grads()
+        self._check_device(g, scratch, state, group_scalars)
+        tab, nr, n_live = self._live_args(table)
+        arr, ng = self._group_args(table, groups)
+        lo, hi = self.dead_range if whole else (0, 0)
+        rc = self.lib.wn_grad_norm_groups(_ptr(g), g.numel(), None if whole else tab, nr, n_live, int(lo), int(hi),
+                                          float(max_norm) if max_norm else 0.0, int(bool(guard)),
+                                          ctypes.cast(arr, ctypes.c_void_p), ng, float(betas[0]), float(betas[1]), _ptr(scratch),
+                                          _ptr(state), _ptr(group_scalars), _stream_handle(self.device))
+        self.lib.check(rc, "wn_grad_norm_groups")
+
+    def adam_step_guarded_groups(self, exp_avg, exp_avg_sq, ema, table, state, group_scalars, ema_decay=0.0, ema_warmup=False):
+        """``adam_step_groups`` with its scalars read from ``state`` and ``group_scalars`` as the preceding ``grad_norm_groups``
+        on the same stream left them."""
+        self._check_device(exp_avg, exp_avg_sq, ema, state, group_scalars)
+        tab, nr, n_live = self._live_args(table)
+        rc = self.lib.wn_adam_step_guarded_groups(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                                  _ptr(ema), self.n_params, tab, nr, n_live, _ptr(group_scalars), _ptr(state),
+                                                  float(ema_decay), int(bool(ema_warmup)), _stream_handle(self.device))
+        self.lib.check(rc, "wn_adam_step_guarded_groups")
         self._params_epoch += 1
 
     def swap_params(self, other):

@@ -44,25 +44,87 @@ tensor that has been in the live set of at least one APPLIED step (all of them w
 does not count; a change of the set reads the device's step count once on the guarded path); ``load_state_dict`` takes
 a missing entry as zero moments.
 
-With all three at their defaults ``step()`` is the one ``adam`` launch with the host's step count, bit for bit as before.
+Parameter groups: ``groups=[(regex, {"lr": .., "weight_decay": .., "eps": .., "decoupled_weight_decay": ..}), ..]``
+gives the tensors whose ``named_parameters()`` key ``re.search`` es ``regex`` (the first matching entry wins) their own learning rate,
+epsilon and weight decay -- L2 as above, or decoupled as in ``torch.optim.AdamW`` (``p *= 1 - lr wd`` in front of an update whose
+gradient carries no decay term).  A missing key inherits the constructor's value; unmatched tensors form the default group,
+``param_groups[0]``.  Betas, the step count, the norm with its clip coefficient, the guard and the average stay one per optimizer.
+``param_groups`` then holds ``1 + len(groups)`` torch-format entries with the real ``Parameter`` objects, and every ``step()`` reads
+the four values from them: ``torch.optim.lr_scheduler`` works on all groups, and because the values travel in the launch
+arguments a changing learning rate costs no copy and no synchronisation.  The step stays one launch (three guarded:
+``adam*_groups``, a live table whose ranges carry a group index; with nothing frozen the norm is the whole-buffer ``grad_sumsq``).
+An L2 group's elements get the bits the single-group launch gives them with that group's values.  The grouped launch is taken
+only when more than one group holds a live parameter or the one that does is decoupled.  ``state_dict()`` numbers the tensors as
+torch does -- consecutively over the groups in order, model order inside a group -- so a grouped checkpoint loads into
+``torch.optim.Adam`` built with the same groups, and back; a different group structure raises ValueError.  ``add_param_group``
+after construction raises: a group is a set of ranges of the flat buffer, fixed with the optimizer.
+
+With all of these at their defaults ``step()`` is the one ``adam`` launch with the host's step count, bit for bit as before.
 ``state_dict()`` never holds the average: it stays in torch.optim.Adam's format.
 """
 import contextlib
+import re
 
 import torch
 
 from . import _lib
 
 
+GROUP_KEYS = ("lr", "weight_decay", "eps", "decoupled_weight_decay")
+
+
+def assign_groups(names, groups):
+    """Group index per name for ``FusedAdam(groups=)``: 0 for the default group, ``1 + j`` for the first entry ``j`` whose regex
+    ``re.search`` es the name.  ValueError for an entry that is no ``(regex, dict)`` pair, an unknown key, a pattern that matches
+    no name and more than ``_lib.MAX_PARAM_GROUPS`` groups."""
+    groups = list(groups)
+    if 1 + len(groups) > _lib.MAX_PARAM_GROUPS:
+        raise ValueError("%d parameter groups and the default one: at most %d in all" % (len(groups), _lib.MAX_PARAM_GROUPS))
+    rxs = []
+    for entry in groups:
+        try:
+            pattern, values = entry
+            values = dict(values)
+        except (TypeError, ValueError):
+            raise ValueError("groups takes (regex, dict) pairs, got %r" % (entry,))
+        for k in values:
+            if k == "betas":
+                raise ValueError("group %r: betas are per optimizer, not per group (one step count and one bias correction)" % (pattern,))
+            if k not in GROUP_KEYS:
+                raise ValueError("group %r: unknown key %r (a group sets %s)" % (pattern, k, ", ".join(GROUP_KEYS)))
+        rx = re.compile(pattern)
+        if not any(rx.search(k) for k in names):
+            raise ValueError("group pattern %r matches no parameter of the model (keys look like %r)" % (pattern, names[0]))
+        rxs.append(rx)
+    return [next((1 + j for j, rx in enumerate(rxs) if rx.search(k)), 0) for k in names]
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
-                 skip_nonfinite=False, ema_decay=None, ema_warmup=True):
+                 skip_nonfinite=False, ema_decay=None, ema_warmup=True, groups=None):
         if not hasattr(model, "engine"):
             raise TypeError("FusedAdam takes the WaveNet model (it updates the model's flat buffer)")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                         maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
         self.model = model
-        super(FusedAdam, self).__init__(list(model.parameters()), defaults)
+        named = list(model.named_parameters())
+        self._built = False
+        if groups is None:
+            self._group_of = [0] * len(named)
+            super(FusedAdam, self).__init__([p for _, p in named], defaults)
+        else:
+            # torch's own key for the decay mode (torch.optim.Adam(decoupled_weight_decay=)): a grouped checkpoint carries it
+            defaults["decoupled_weight_decay"] = False
+            self._group_of = assign_groups([k for k, _ in named], groups)
+            entries = [{"params": [p for (_, p), g in zip(named, self._group_of) if g == 0]}]
+            for j, (_, values) in enumerate(groups):
+                entries.append(dict(values, params=[p for (_, p), g in zip(named, self._group_of) if g == 1 + j]))
+            super(FusedAdam, self).__init__(entries, defaults)
+        self._built = True
+        # torch's numbering of the tensors: consecutive over the groups in order, model order inside a group (one group: model order)
+        self._order = [i for g in range(len(self.param_groups)) for i, gi in enumerate(self._group_of) if gi == g]
+        self._route = (None, None, None)   # (TrainableSet, groups that hold a live tensor, its GroupTable): rebuilt when the set changes
+        self._group_scalars = None         # the guarded grouped step's device block of per-group scalars
         self._step = 0
         self._exp_avg = None
         self._exp_avg_sq = None
@@ -82,6 +144,32 @@ class FusedAdam(torch.optim.Optimizer):
         self._set_applied0 = 0     # applied steps when _last_set became the current set
         self._ema = None           # the shadow buffer: a copy of the flat weights at its first use
         self._ema_swapped = False  # inside ema_weights(): the two buffers have changed places
+
+    def add_param_group(self, param_group):
+        if getattr(self, "_built", False):
+            raise RuntimeError("FusedAdam: parameter groups are fixed at construction (groups=): a group is a set of ranges of "
+                               "the model's flat buffer")
+        return super(FusedAdam, self).add_param_group(param_group)
+
+    def _group_route(self, ts):
+        """``(live groups, GroupTable)`` of a trainable set: the groups that hold a live tensor, and -- built at its first use,
+        once per set -- the live ranges split at group boundaries."""
+        if self._route[0] is not ts:
+            live = tuple(sorted({g for g, on in zip(self._group_of, ts.mask) if on}))
+            self._route = (ts, live, None)
+        return self._route[1], self._route[2]
+
+    def _group_table(self, ts):
+        if self._route[2] is None:
+            triples = []   # in buffer order (not the model's), touching tensors of one group merged into one range
+            for lo, hi, g in sorted((off, off + n, g) for g, on, (off, n, shape, dead)
+                                    in zip(self._group_of, ts.mask, self.model._param_slices) if on and not dead and n > 0):
+                if triples and triples[-1][1] == lo and triples[-1][2] == g:
+                    triples[-1] = (triples[-1][0], hi, g)
+                else:
+                    triples.append((lo, hi, g))
+            self._route = (ts, self._route[1], self.model.engine.group_table(triples, len(self.param_groups)))
+        return self._route[2]
 
     def _guard_buffers(self):
         eng = self.model.engine
@@ -222,7 +310,11 @@ class FusedAdam(torch.optim.Optimizer):
             self._fold_trained()
             self._set_applied0 = self._step if self._last_set is None else self.steps_applied()
             self._last_set = ts
-        group = self.param_groups[0]
+        live_groups, _ = self._group_route(ts)
+        group = self.param_groups[live_groups[0]]
+        if len(live_groups) > 1 or group.get("decoupled_weight_decay", False):
+            self._step_groups(ts, m, v, ema)
+            return loss
         if self.guarded:
             # the gather above comes first: the norm is the norm of what the Adam launch reads
             state, scratch = self._guard_buffers()
@@ -241,6 +333,25 @@ class FusedAdam(torch.optim.Optimizer):
                                   self.ema_decay, self.ema_warmup, **live)
         return loss
 
+    def _step_groups(self, ts, m, v, ema):
+        """The step over parameter groups: the values of every group as ``param_groups`` holds them NOW, in the
+        launch arguments; the table from the set's cache."""
+        eng = self.model.engine
+        table = self._group_table(ts)
+        values = [(g["lr"], g["eps"], g["weight_decay"], g.get("decoupled_weight_decay", False)) for g in self.param_groups]
+        betas = self.param_groups[0]["betas"]
+        decay = 0.0 if ema is None else self.ema_decay
+        if self.guarded:
+            state, scratch = self._guard_buffers()
+            if self._group_scalars is None or self._group_scalars.device != eng.flat_params.device:
+                self._group_scalars = eng.new_group_scalars()
+            eng.grad_norm_groups(state, scratch, self._group_scalars, table, values, self.max_grad_norm, self.skip_nonfinite, betas,
+                                 whole=ts.full)
+            eng.adam_step_guarded_groups(m, v, ema, table, state, self._group_scalars, decay, self.ema_warmup)
+        else:
+            self._step += 1
+            eng.adam_step_groups(m, v, ema, table, self._step, values, betas, decay, self.ema_warmup)
+
     def _fold_trained(self):
         """Mark the tensors of the current set as trained if a step was APPLIED since it became current: a step the non-finite
         guard skipped trains nothing."""
@@ -254,30 +365,44 @@ class FusedAdam(torch.optim.Optimizer):
         m, v = self._buffers()
         state = {}
         step = self.steps_applied()
+        number = {idx: k for k, idx in enumerate(self._order)}
         if step > 0:
             for idx, (off, n, shape, dead) in enumerate(self.model._param_slices):
                 if dead or not self._trained[idx]:   # (a tensor frozen in every step so far has no state, as in torch)
                     continue
-                state[idx] = {"step": torch.tensor(float(step)),
+                state[number[idx]] = {"step": torch.tensor(float(step)),
                               "exp_avg": m[off:off + n].view(shape).clone(),
                               "exp_avg_sq": v[off:off + n].view(shape).clone()}
         groups = []
+        first = 0
         for g in self.param_groups:
             gg = {k: val for k, val in g.items() if k != "params"}
-            gg["params"] = list(range(len(self.model._param_slices)))
+            gg["params"] = list(range(first, first + len(g["params"])))
+            first += len(g["params"])
             groups.append(gg)
-        return {"state": state, "param_groups": groups}
+        return {"state": dict(sorted(state.items())), "param_groups": groups}
 
     def load_state_dict(self, sd):
+        if len(sd["param_groups"]) != len(self.param_groups):
+            raise ValueError("loaded state dict has a different number of parameter groups (%d, this optimizer %d)"
+                             % (len(sd["param_groups"]), len(self.param_groups)))
+        for i, (g, sg) in enumerate(zip(self.param_groups, sd["param_groups"])):
+            if len(sg["params"]) != len(g["params"]):
+                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group "
+                                 "(group %d: %d tensors, this optimizer %d)" % (i, len(sg["params"]), len(g["params"])))
         m, v = self._buffers()
         m.zero_()
         v.zero_()
         step = 0
         self._trained = [False] * len(self.model._param_slices)
         self._last_set = None
-        for idx, st in sd["state"].items():
-            off, n, shape, dead = self.model._param_slices[int(idx)]
-            self._trained[int(idx)] = True
+        # the checkpoint's own numbers, group by group, against ours (torch maps them the same way)
+        theirs = [k for sg in sd["param_groups"] for k in sg["params"]]
+        tensor_of = dict(zip(theirs, self._order))
+        for key, st in sd["state"].items():
+            idx = tensor_of[int(key)]
+            off, n, shape, dead = self.model._param_slices[idx]
+            self._trained[idx] = True
             m[off:off + n].copy_(st["exp_avg"].reshape(-1))
             v[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
             step = max(step, int(float(st["step"])))
@@ -285,6 +410,6 @@ class FusedAdam(torch.optim.Optimizer):
         if self.guarded:
             self._guard_buffers()[0][3] = step
         for g, sg in zip(self.param_groups, sd["param_groups"]):
-            for k in ("lr", "betas", "eps", "weight_decay"):
+            for k in ("lr", "betas", "eps", "weight_decay") + (("decoupled_weight_decay",) if "decoupled_weight_decay" in g else ()):
                 if k in sg:
                     g[k] = tuple(sg[k]) if k == "betas" else sg[k]
