@@ -237,8 +237,10 @@ __global__ __launch_bounds__(WN_TPB) void k_softmax_ce(const float* __restrict__
         }
         long long tg = target[(long)b * T + t] % Q;
         if (tg < 0) tg += Q;
-        const float lse = logf(sum) + mx;
-        my_loss = lse - lg[(long)tg * T];
+        // log-softmax as (v - mx) - log(sum), never through lse = log(sum) + mx: that sum is rounded at ulp(mx), which a common
+        // offset on the logits or a peak of some tens of nats turns into an absolute error of every probability
+        const float lsum = logf(sum);
+        my_loss = (mx - lg[(long)tg * T]) + lsum;
         if (dlogits != nullptr) {
             float* dl = dlogits + (long)b * Q * T + t;
             for (int q0 = 0; q0 < Q; q0 += 8) {
@@ -248,7 +250,7 @@ __global__ __launch_bounds__(WN_TPB) void k_softmax_ce(const float* __restrict__
                 WN_UNROLL
                 for (int u = 0; u < 8; ++u) {
                     if (q0 + u < Q) {
-                        float pq = expf(v[u] - lse);
+                        float pq = expf((v[u] - mx) - lsum);
                         if (q0 + u == (int)tg) pq -= 1.0f;
                         dl[(long)(q0 + u) * T] = pq * grad_scale;
                         my_amax = fmaxf(my_amax, fabsf(pq * grad_scale));
@@ -1404,19 +1406,21 @@ __global__ __launch_bounds__(WN_TPB) void k_mol_nll(const float* __restrict__ ou
         float s1 = 0.0f;
         for (int i = 0; i < nm; ++i) s1 += expf(o[(long)i * T] - m1);
         const float lse_p = m1 + logf(s1);
+        // (log prior as logit - lse_p FIRST, then added to the component's log-likelihood: summed left to right a common offset
+        // on the mixture logits rounds the log-likelihood at ulp(logit))
         // log-sum-exp over components of (component log-likelihood + log prior)
         float m2 = -3.0e38f;
         for (int i = 0; i < nm; ++i) {
             float a, c;
             const float ls = fmaxf(o[(long)(2 * nm + i) * T], log_scale_min);
-            const float lp = mol_component(y, o[(long)(nm + i) * T], ls, half_bin, log_half_classes, &a, &c) + o[(long)i * T] - lse_p;
+            const float lp = mol_component(y, o[(long)(nm + i) * T], ls, half_bin, log_half_classes, &a, &c) + (o[(long)i * T] - lse_p);
             m2 = fmaxf(m2, lp);
         }
         float s2 = 0.0f;
         for (int i = 0; i < nm; ++i) {
             float a, c;
             const float ls = fmaxf(o[(long)(2 * nm + i) * T], log_scale_min);
-            const float lp = mol_component(y, o[(long)(nm + i) * T], ls, half_bin, log_half_classes, &a, &c) + o[(long)i * T] - lse_p;
+            const float lp = mol_component(y, o[(long)(nm + i) * T], ls, half_bin, log_half_classes, &a, &c) + (o[(long)i * T] - lse_p);
             s2 += expf(lp - m2);
         }
         const float lse = m2 + logf(s2);
@@ -1427,7 +1431,7 @@ __global__ __launch_bounds__(WN_TPB) void k_mol_nll(const float* __restrict__ ou
                 const float raw = o[(long)(2 * nm + i) * T];
                 const float ls = fmaxf(raw, log_scale_min);
                 const float logit = o[(long)i * T];
-                const float lp = mol_component(y, o[(long)(nm + i) * T], ls, half_bin, log_half_classes, &dm, &dls) + logit - lse_p;
+                const float lp = mol_component(y, o[(long)(nm + i) * T], ls, half_bin, log_half_classes, &dm, &dls) + (logit - lse_p);
                 const float r = expf(lp - lse);           // posterior responsibility
                 const float pi = expf(logit - lse_p);     // prior
                 d[(long)i * T] = (pi - r) * grad_scale;

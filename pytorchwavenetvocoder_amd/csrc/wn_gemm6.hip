@@ -625,11 +625,12 @@ __global__ __launch_bounds__(G6_T, 2) void k_gemm6(WnGemm6Args g, int order G6_D
         for (int j = 0; j < 2; ++j) {
             const int col = n0 + 64 * wn + 32 * j + li;
             const float s = sm[j] + red[256 + (wave ^ 2) * 64 + 32 * j + li];
-            const float lse = wn_log2(s) * 0.6931471805599453f + mx[j];
+            // loss = (max - v_t) + log(s), like k_softmax_ce: log(s) + max first would round the loss at ulp(max)
+            const float lsum = wn_log2(s) * 0.6931471805599453f;
             const float scale = live[j] ? wn_rcp(s) * g.ce_gs : 0.f;
             const float hot = live[j] ? g.ce_gs : 0.f;
             const int tl = tq[j] - 128 * wm - 4 * hi;   // row == tq  <=>  32 i + mfma32_row(r, 0) == tl
-            my_loss += (live[j] && tl >= 0 && tl < 128 && ((tl >> 2) & 1) == 0) ? (lse - vt[j]) : 0.f;
+            my_loss += (live[j] && tl >= 0 && tl < 128 && ((tl >> 2) & 1) == 0) ? ((mx[j] - vt[j]) + lsum) : 0.f;
             const int vC = okc[j] ? ((128 * wm + 4 * hi) * (int)g.ldc + col) * 4 : 0x7ffffff0;
             WN_UNROLL
             for (int i = 0; i < 4; ++i) {
