@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 17
+#define WN_ABI_VERSION 18
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -286,6 +286,32 @@ int wn_forward_loss_ragged(const WnConfig* cfg, int B, int T, const float* param
                            const int64_t* target, int t_start, const int32_t* t_end, int64_t n_loss, float grad_scale,
                            float loss_scale, float* loss, float* dlogits, float* logits_scratch, void* ws, size_t ws_bytes,
                            int flags, void* stream);
+
+/* Knowledge distillation (since ABI v18; additions only): the softmax head's loss against a teacher's distribution.  For every
+ * loss position (t_start <= t < t_end[b], as wn_softmax_ce_loss_ragged) with s the student's and u the teacher's logit column,
+ * y = target mod n_quantize, P = softmax(u / tau), S = softmax(s / tau):
+ *   ce = logsumexp(s) - s_y,   kl = sum_q P_q (log P_q - log S_q)  (a class with P_q == 0 adds exactly 0; not clamped)
+ *   l  = (1 - alpha) ce + alpha tau^2 kl                            (Hinton's form: tau^2 keeps the gradient's scale)
+ *   loss[0] = loss_scale / N * sum l,  loss[1] = loss_scale / N * sum ce,  loss[2] = loss_scale / N * sum kl (unweighted)
+ *   dlogits_q = grad_scale / N * ((1 - alpha) (softmax(s)_q - [q == y]) + alpha tau (S_q - P_q)), EXACTLY 0.0f off the loss
+ *   positions.  The teacher is a constant: nothing is differentiated with respect to u.
+ *   teacher_logits : (B, n_quantize, T) fp32, the layout wn_forward writes
+ *   alpha in [0, 1], tau > 0 and finite.  alpha == 1: target is not read (may be NULL) and ce is 0; alpha == 0: l = ce.
+ *   loss     : THREE floats on the device
+ *   dlogits  : nullable; pos_loss : nullable, (B, T) out = l per position, unscaled, 0 off the loss positions.  The loss bits do
+ *              not depend on whether either is given.
+ *   scratch  : wn_softmax_distill_scratch_floats(B, T) floats on the device; holds the per-block partial sums, which are added
+ *              in a fixed order (no atomics: the same inputs give the same bits).  Nothing is read from it, or from the
+ *              workspace, that the call did not write: the result does not depend on what either held before.
+ * The workspace keeps its size and layout; the call leaves max |dlogits| in the word the other loss calls use, so a backward
+ * call may take WN_FLAG_DW_F16_AMAX_WS.  Two plain launches on `stream`.  A mixture-of-logistics model (out_channels > 0),
+ * alpha or tau out of range, a NULL among logits / teacher_logits / target (alpha < 1) / loss / scratch and the n_loss
+ * conditions of the ragged entry points are errors: no launch is made. */
+int64_t wn_softmax_distill_scratch_floats(int B, int T);
+int wn_softmax_distill_loss(const WnConfig* cfg, int B, int T, const float* logits, const float* teacher_logits,
+                            const int64_t* target, int t_start, const int32_t* t_end, int64_t n_loss, float alpha, float tau,
+                            float grad_scale, float loss_scale, float* loss, float* dlogits, float* pos_loss, float* scratch,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* Scoring held-out data (since ABI v13; additions only): the negative log-likelihood of each sequence of a batch, without a
  * gradient and without a divisor.

@@ -138,7 +138,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -156,6 +156,7 @@ EXPORTS = [
     "wn_op_accumulate",
     "wn_backward_needs", "wn_live_table", "wn_grad_norm_live", "wn_adam_step_live", "wn_adam_step_guarded_live",
     "wn_group_table", "wn_adam_step_groups", "wn_grad_norm_groups", "wn_adam_step_guarded_groups",
+    "wn_softmax_distill_scratch_floats", "wn_softmax_distill_loss",
 ]
 
 
@@ -233,6 +234,11 @@ class WnLibrary(object):
         L.wn_adam_step_groups.argtypes = [vp, vp, vp, vp, vp, i64, vp, i, i64, i64, vp, i, f, f, d, i, vp]
         L.wn_grad_norm_groups.argtypes = [vp, i64, vp, i, i64, i64, i64, f, i, vp, i, f, f, vp, vp, vp, vp]
         L.wn_adam_step_guarded_groups.argtypes = [vp, vp, vp, vp, vp, i64, vp, i, i64, vp, vp, d, i, vp]
+        # soft-target loss (ABI v18): (.., logits, teacher, target, t_start, t_end, n_loss, alpha, tau, grad_scale, loss_scale,
+        # loss (3 floats), dlogits, pos_loss, scratch, ws, ws_bytes, stream)
+        L.wn_softmax_distill_scratch_floats.argtypes = [i, i]
+        L.wn_softmax_distill_scratch_floats.restype = i64
+        L.wn_softmax_distill_loss.argtypes = [cfgp, i, i, vp, vp, vp, i, vp, i64, f, f, f, f, vp, vp, vp, vp, vp, sz, vp]
         L.wn_op_front.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.wn_op_causal_conv.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.wn_op_causal_conv_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]

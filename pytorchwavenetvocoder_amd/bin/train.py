@@ -618,7 +618,61 @@ def get_parser():
                         help="repeatable: the tensors whose name matches REGEX (re.search; the first matching group wins) get "
                              "their own lr=, weight_decay=, eps= and decoupled=true|false (AdamW's decay); a missing key takes "
                              "--lr / --weight_decay.  Give the same groups with --resume: the checkpoint's values then win")
+    # extension (not reference flags): knowledge distillation from a trained model
+    parser.add_argument("--teacher", default=None, type=str,
+                        help="checkpoint of a trained softmax-head model whose output distribution the model is trained against "
+                             "(its \"model\" weights; with --teacher_config)")
+    parser.add_argument("--teacher_config", default=None, type=str, help="the model.conf the teacher's run saved")
+    parser.add_argument("--distill_alpha", default=0.5, type=float,
+                        help="weight of the teacher term in [0, 1]: loss = (1 - alpha) * ce + alpha * T^2 * kl")
+    parser.add_argument("--distill_temperature", default=1.0, type=float, help="softmax temperature T > 0 of the teacher term")
     return parser
+
+
+TEACHER_MUST_MATCH = ("n_quantize", "n_aux", "upsampling_factor", "use_upsampling_layer")
+
+
+def check_teacher_args(args):
+    """The refusals of --teacher, made while main() looks at the arguments; returns the teacher's configuration (None: no
+    teacher).  ValueError with the reason."""
+    teacher, conf = getattr(args, "teacher", None), getattr(args, "teacher_config", None)
+    if not teacher and not conf:
+        return None
+    if not teacher or not conf:
+        raise ValueError("--teacher and --teacher_config go together: the checkpoint holds no model configuration.")
+    if args.n_mixture > 0:
+        raise ValueError("--teacher needs the softmax head: distillation is not defined for --n_mixture %d." % args.n_mixture)
+    alpha, temperature = float(args.distill_alpha), float(args.distill_temperature)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("--distill_alpha %g is outside [0, 1]." % alpha)
+    if not (temperature > 0.0 and temperature < float("inf")):
+        raise ValueError("--distill_temperature %g must be positive and finite." % temperature)
+    for path, flag in ((conf, "--teacher_config"), (teacher, "--teacher")):
+        if not os.path.isfile(path):
+            raise ValueError("%s %s does not exist." % (flag, path))
+    config = torch.load(conf, weights_only=False)
+    if getattr(config, "n_mixture", 0) > 0:
+        raise ValueError("--teacher_config %s describes a mixture-of-logistics model: the teacher needs the softmax head." % conf)
+    for key in TEACHER_MUST_MATCH:
+        if getattr(config, key) != getattr(args, key):
+            raise ValueError("the teacher's %s (%s) differs from the model's (%s): the two must read the same inputs and share the "
+                             "classes." % (key, getattr(config, key), getattr(args, key)))
+    return config
+
+
+def build_teacher(config, checkpoint, device):
+    """The teacher of --teacher: built from its run's model.conf, its "model" weights loaded (a checkpoint-best.pkl contributes
+    its averaged weights), on the rank's device, never trained.  The global random state is left as it was."""
+    with torch.random.fork_rng(devices=[]):
+        teacher = WaveNet(n_quantize=config.n_quantize, n_aux=config.n_aux, n_resch=config.n_resch, n_skipch=config.n_skipch,
+                          dilation_depth=config.dilation_depth, dilation_repeat=config.dilation_repeat,
+                          kernel_size=config.kernel_size,
+                          upsampling_factor=config.upsampling_factor if config.use_upsampling_layer else 0)
+    teacher.load_state_dict(torch.load(checkpoint, map_location=lambda storage, loc: storage, weights_only=False)["model"])
+    teacher.requires_grad_(False)
+    teacher.eval()
+    teacher.to(device)
+    return teacher
 
 
 PARAM_GROUP_KEYS = {"lr": "lr", "weight_decay": "weight_decay", "eps": "eps", "decoupled": "decoupled_weight_decay"}
@@ -732,9 +786,17 @@ def _worker(rank, world, args, port):
     assert len(wav_list) == len(feat_list)
     logging.info("number of training data = %d." % len(wav_list))
     utterance_batch = bool(getattr(args, "utterance_batch", False))
+    # --teacher: windows carry the context of the deeper of the two models, and the loss starts behind it
+    teacher, rf = None, model.receptive_field
+    if getattr(args, "teacher", None):
+        teacher = build_teacher(check_teacher_args(args), args.teacher, device)   # (main() has made the refusals)
+        rf = max(model.receptive_field, teacher.receptive_field)
+        distill_alpha, distill_temperature = float(args.distill_alpha), float(args.distill_temperature)
+        logging.info("teacher from %s: receptive field %d (the model's: %d), alpha %g, temperature %g." % (
+            args.teacher, teacher.receptive_field, model.receptive_field, distill_alpha, distill_temperature))
     generator = train_generator(
         wav_list, feat_list,
-        receptive_field=model.receptive_field,
+        receptive_field=rf,
         batch_length=None if utterance_batch else args.batch_length,
         batch_size=args.batch_size,
         pad_utterances=utterance_batch,
@@ -818,6 +880,8 @@ def _worker(rank, world, args, port):
         dist.broadcast(model.engine.flat_params, src=0)
 
     loss_acc = torch.zeros(1, device=device)
+    distilling = teacher is not None and distill_alpha != 0.0   # (alpha == 0: the teacher has no say, the step is the plain one)
+    parts_acc = torch.zeros(3, device=device) if distilling else None   # the total, its cross-entropy and its (unweighted) kl part
     norm_acc = torch.zeros(1, device=device)     # guarded optimizer: sum of the finite pre-clip gradient norms of the interval
     skipped_seen = optimizer.steps_skipped()
     total = 0.0
@@ -840,7 +904,6 @@ def _worker(rank, world, args, port):
                 # padded whole utterances: the loss is the mean over the valid positions behind the receptive field.  This rank's
                 # share of the minibatch is N_local / N_global loss positions (every rank knows every length: no communication).
                 lengths, all_lengths = item[-2], item[-1]
-                rf = model.receptive_field
                 n_local = int((lengths - rf).clamp_(min=0).sum())
                 n_global = int((all_lengths - rf).clamp_(min=0).sum())
                 ragged["lengths"] = lengths
@@ -862,11 +925,18 @@ def _worker(rank, world, args, port):
             (batch_x, batch_h), batch_t = item[0], item[1]
             if accum_steps > 1:
                 ragged["micro_step"] = (k, accum_steps)
+            if teacher is not None:
+                ragged["t_start"] = rf
+            if distilling:   # the teacher's forward on this rank's own micro-batch, then the student's step with its logits
+                ragged.update(teacher_logits=teacher.teacher_logits(batch_x, batch_h), distill_alpha=distill_alpha,
+                              distill_temperature=distill_temperature)
             batch_loss = reducer.loss_and_backward(batch_x, batch_h, batch_t, y=item[2] if args.n_mixture > 0 else None,
                                                    grad_scale=share, **ragged)
             if k == accum_steps - 1:
                 optimizer.step()
             loss_acc += batch_loss.detach() * (share * world)
+            if distilling:
+                parts_acc += model.distill_parts.detach() * (share * world)
         if optimizer.guarded:   # device-side accumulation, read at the interval's synchronisation below
             norm_acc += torch.nan_to_num(optimizer.grad_norm, nan=0.0, posinf=0.0)
         if args.verbose > 1:
@@ -878,9 +948,16 @@ def _worker(rank, world, args, port):
             if world > 1:
                 dist.all_reduce(loss_acc)
                 loss_acc /= world
+                if distilling:
+                    dist.all_reduce(parts_acc)
+                    parts_acc /= world
             if is_main:
                 logging.info("(iter:%d) average loss = %.6f (%.3f sec / batch)" % (
                     i + 1, loss_acc.item() / args.intervals, total / args.intervals))
+                if distilling:
+                    parts = (parts_acc / args.intervals).tolist()
+                    logging.info("(iter:%d) average ce = %.6f, average kl = %.6f (alpha %g, temperature %g)" % (
+                        i + 1, parts[1], parts[2], distill_alpha, distill_temperature))
                 logging.info("estimated required time = " + _fmt_eta((args.iters - (i + 1)) * (total / args.intervals)))
             if optimizer.guarded:
                 # every rank holds the same reduced gradient, hence the same norm: nothing to exchange
@@ -892,6 +969,8 @@ def _worker(rank, world, args, port):
                         i + 1, norm_acc.item() / finite, skipped))
                 norm_acc.zero_()
             loss_acc.zero_()
+            if distilling:
+                parts_acc.zero_()
             total = 0.0
         if eval_interval > 0 and (i + 1) % eval_interval == 0:
             # every rank scores its shard of the held-out list; one all-reduce of [nll, positions] makes the mean
@@ -953,6 +1032,11 @@ def main(argv=None):
         sys.exit(1)
     if args.pretrained and args.resume:
         logging.error("--pretrained starts iteration 0 from a checkpoint's weights, --resume continues a run: give one of them.")
+        sys.exit(1)
+    try:
+        check_teacher_args(args)
+    except ValueError as err:
+        logging.error(str(err))
         sys.exit(1)
     if world_env > 1:  # launched by torch.distributed.run: one process per GPU already
         _worker(int(os.environ.get("LOCAL_RANK", os.environ.get("RANK", "0"))), world_env, args,

@@ -10,6 +10,7 @@
 
 #include "../../include/wavenet_hip.h"
 #include "wn_decode.h"
+#include "wn_distill.h"
 #include "wn_dlp.h"
 #include "wn_elem.h"
 #include "wn_fused.h"
@@ -1266,6 +1267,33 @@ extern "C" int wn_mol_loss(const WnConfig* cfg, int B, int T, const float* out, 
                            size_t ws_bytes, void* stream) {
     return wn_mol_loss_ragged(cfg, B, T, out, y, t_start, nullptr, (int64_t)B * (int64_t)(T - t_start), grad_scale, loss_scale,
                               num_classes, log_scale_min, loss, dout, wsp, ws_bytes, stream);
+}
+
+// Soft-target loss head (since ABI v18): hard-label cross-entropy blended with the tempered KL divergence from a teacher's
+// logits, wn_distill.h.  The partial sums live in the caller's scratch, the workspace keeps its layout; only its
+// max |dlogits| word is written, as by the other loss calls.
+extern "C" int64_t wn_softmax_distill_scratch_floats(int B, int T) { return (int64_t)wn_distill_scratch_floats(B, T); }
+
+extern "C" int wn_softmax_distill_loss(const WnConfig* cfg, int B, int T, const float* logits, const float* teacher_logits,
+                                       const int64_t* target, int t_start, const int32_t* t_end, int64_t n_loss, float alpha,
+                                       float tau, float grad_scale, float loss_scale, float* loss, float* dlogits, float* pos_loss,
+                                       float* scratch, void* wsp, size_t ws_bytes, void* stream) {
+    api_enter();
+    Ctx c;
+    WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, 0, stream));
+    if (cfg->out_channels > 0) return fail(1, "out_channels=%d: the soft-target loss is defined for the softmax head only", cfg->out_channels);
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(1, "alpha=%g outside [0, 1]", (double)alpha);
+    if (!(tau > 0.0f) || !(tau <= 3.0e38f)) return fail(1, "tau=%g must be positive and finite", (double)tau);
+    if (!logits) return fail(1, "logits is NULL");
+    if (!teacher_logits) return fail(1, "teacher_logits is NULL");
+    if (!target && alpha != 1.0f) return fail(1, "target is NULL (allowed with alpha == 1 only)");
+    if (!loss) return fail(1, "loss is NULL");
+    if (!scratch) return fail(1, "scratch is NULL");
+    float count = 0.f;
+    WN_TRY(loss_count(B, T, t_start, t_end, n_loss, &count));
+    WN_TRY(wn_softmax_distill(logits, teacher_logits, target, dlogits, pos_loss, scratch, B, T, c.d.Qo, t_start, t_end, alpha, tau,
+                              grad_scale / count, loss_scale / count, loss, c.ws + c.w.dw_ovf + 2, c.st));   // + max |dlogits| (WN_FLAG_DW_F16_AMAX_WS)
+    return rt_check("wn_softmax_distill_loss");
 }
 
 // ------------------------------------------------------------------------------------------

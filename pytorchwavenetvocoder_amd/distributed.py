@@ -96,7 +96,8 @@ class GradientReducer(object):
             return self.model.mol_loss_and_backward(x, h, y, **kw)
         return self.model.loss_and_backward(x, h, t, **kw)
 
-    def loss_and_backward(self, x, h, t, t_start=None, y=None, grad_scale=None, lengths=None, micro_step=None):
+    def loss_and_backward(self, x, h, t, t_start=None, y=None, grad_scale=None, lengths=None, micro_step=None,
+                          teacher_logits=None, distill_alpha=0.5, distill_temperature=1.0):
         """forward + loss + backward with the bucketed all-reduce overlapped; returns the local
         mean loss (device tensor).  ``y`` (B, T) float selects the mixture-of-logistics loss.
         ``grad_scale``: this rank's share of the global minibatch (default 1/world = equal shards; pass
@@ -111,8 +112,15 @@ class GradientReducer(object):
         structure, no events, no side-stream work; its ``grad_accumulate`` launch covers the whole buffer on the caller's stream);
         the final one keeps the overlap -- per bucket the side stream waits for the bucket's event, finishes the sum on the
         bucket's range and all-reduces it.  ``grad_scale`` is then this rank's share of the loss positions of the whole
-        optimizer step, over all ranks and micro-steps (default 1 / (world * A): equal shards, equal micro-batches)."""
+        optimizer step, over all ranks and micro-steps (default 1 / (world * A): equal shards, equal micro-batches).
+
+        ``teacher_logits`` / ``distill_alpha`` / ``distill_temperature``: knowledge distillation on this rank's shard, handed to
+        ``WaveNet.loss_and_backward`` on every route (the gradient is exchanged as ever; softmax head only)."""
         kw = {} if lengths is None else {"lengths": lengths}
+        if teacher_logits is not None:
+            if y is not None:
+                raise ValueError("distillation is defined for the softmax head: teacher_logits cannot go with y")
+            kw.update(teacher_logits=teacher_logits, distill_alpha=distill_alpha, distill_temperature=distill_temperature)
         if self.eng.begin_micro_step(micro_step) is not None:   # (checks the pair against the cycle; None: a plain call, A = 1 included)
             return self._micro_step(x, h, t, y, t_start, grad_scale, micro_step, kw)
         if self.world == 1 and not self.exchange_alone:   # same launch structure as N > 1 (weight gradients flushed per bucket), no exchange

@@ -135,6 +135,7 @@ class WaveNetEngine(object):
         self._lengths_key = None  # (lengths, device) of the int32 array _lengths_arg uploaded last
         self._lengths_dev = None
         self._eval_lengths = (None, None)  # the same pair for forward_nll
+        self._distill_scratch = None  # partial sums of distill_loss (grown on demand; the call reads nothing it did not write)
         self._last_shape = None
         self._fwd_window = 0      # first loss position of the last forward_loss (0: a full forward)
         self._fwd_version = None  # parameter version the last forward packed its weight sets from
@@ -532,6 +533,53 @@ class WaveNetEngine(object):
             self.lib.check(rc, "wn_softmax_ce_loss_ragged")
         self._note_bound(dlogits, grad_scale, count)
         return loss, dlogits
+
+    def distill_loss(self, logits, teacher_logits, target, alpha, temperature, t_start=None, grad_scale=1.0, loss_scale=1.0,
+                     want_grad=True, lengths=None, want_pos=False):
+        """Soft-target loss of the softmax head (knowledge distillation, ``wn_softmax_distill_loss``): per loss position
+        ``l = (1 - alpha) * ce + alpha * temperature^2 * kl`` with ``ce`` the cross-entropy against ``target`` and ``kl`` the
+        divergence of ``softmax(logits / temperature)`` from ``softmax(teacher_logits / temperature)``.  ``logits`` and
+        ``teacher_logits``: (B, Q, T) fp32 in the physical layout ``forward`` returns; the teacher is a constant.  ``target`` may
+        be None with ``alpha == 1``.  Returns ``(loss3, dlogits[, pos_loss])``: ``loss3`` a 3-element device tensor, the means of
+        ``l``, ``ce`` and the unweighted ``kl``; ``dlogits`` for ``backward`` (None without ``want_grad``; exactly zero off the loss
+        positions); ``pos_loss`` (B, T), ``l`` per position and 0 elsewhere, with ``want_pos``.  ``t_start`` / ``lengths`` /
+        ``grad_scale`` / ``loss_scale`` as ``loss``."""
+        self._check_device(logits, teacher_logits, target)
+        if self.cfg.out_channels > 0:
+            raise ValueError("the soft-target loss is defined for the softmax head (n_mixture = 0)")
+        if logits.dim() != 3 or logits.dtype != torch.float32 or not logits.is_contiguous():
+            raise ValueError("logits must be a contiguous float32 (B, Q, T) tensor")
+        B, Q, T = logits.shape
+        if tuple(teacher_logits.shape) != (B, Q, T) or teacher_logits.dtype != torch.float32 or not teacher_logits.is_contiguous():
+            raise ValueError("teacher_logits must be a contiguous float32 tensor of the logits' shape %s, got %s %s"
+                             % ((B, Q, T), tuple(teacher_logits.shape), teacher_logits.dtype))
+        if target is None:
+            if float(alpha) != 1.0:
+                raise ValueError("target may be None with alpha == 1 only")
+        else:
+            if tuple(target.shape) != (B, T) or target.dtype != torch.int64:
+                raise ValueError("target must be a (B, T) LongTensor")
+            target = target.contiguous()
+        if t_start is None:
+            t_start = self.receptive_field
+        ws = self.workspace(B, T)
+        n_scratch = int(self.lib.wn_softmax_distill_scratch_floats(B, T))
+        if self._distill_scratch is None or self._distill_scratch.numel() < n_scratch or self._distill_scratch.device != logits.device:
+            self._distill_scratch = torch.empty(n_scratch, dtype=torch.float32, device=self.device)
+        loss3 = torch.empty(3, dtype=torch.float32, device=self.device)
+        dlogits = torch.empty_like(logits) if want_grad else None
+        pos = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_pos else None
+        if lengths is None:
+            t_end, count = None, B * (T - int(t_start))
+        else:
+            t_end, count = self._lengths_arg(lengths, B, T, t_start)
+        rc = self.lib.wn_softmax_distill_loss(ctypes.byref(self.cfg), B, T, _ptr(logits), _ptr(teacher_logits), _ptr(target),
+                                              int(t_start), _ptr(t_end), count, float(alpha), float(temperature),
+                                              float(grad_scale), float(loss_scale), _ptr(loss3), _ptr(dlogits), _ptr(pos),
+                                              _ptr(self._distill_scratch), _ptr(ws), ws.numel() * 4, _stream_handle(self.device))
+        self.lib.check(rc, "wn_softmax_distill_loss")
+        self._note_bound(dlogits, grad_scale, count)
+        return (loss3, dlogits, pos) if want_pos else (loss3, dlogits)
 
     def mol_loss(self, out, y, t_start=None, grad_scale=1.0, loss_scale=1.0, want_grad=True, num_classes=65536,
                  log_scale_min=-7.0, lengths=None):

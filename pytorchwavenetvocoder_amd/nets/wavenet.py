@@ -380,6 +380,7 @@ class WaveNet(nn.Module):
             upsampling_factor, device="cpu", library=_library, out_channels=3 * n_mixture))
         assert self._engine.receptive_field == self.receptive_field
         self._fwd_serial = 0
+        self.distill_parts = None   # (total, ce, kl) means of the last distillation step, a device tensor
         self._param_slices = []
         self._trainable_cache = {}   # trainable(): flags as given -> TrainableSet
         self._flatten()
@@ -444,7 +445,8 @@ class WaveNet(nn.Module):
         return _WaveNetFunction.apply(self, x, h, *params)
 
     def loss_and_backward(self, x, h, t, t_start=None, grad_scale=1.0, events=None, layers_per_bucket=0, aux_grad=False,
-                          lengths=None, micro_step=None, _accumulate=True):
+                          lengths=None, micro_step=None, _accumulate=True, teacher_logits=None, distill_alpha=0.5,
+                          distill_temperature=1.0):
         """Fused training half-step: forward -> CrossEntropy on ``[:, t_start:]`` -> backward
         (reference train.py:533-538) without an autograd graph.
 
@@ -473,11 +475,44 @@ class WaveNet(nn.Module):
         positions) makes the sum the gradient of the mean over all loss positions of the cycle.  The micro-batches may differ in
         B, T, ``lengths`` and ``aux_grad`` (``dh`` belongs to its micro-batch and is never accumulated).  ``None`` or A = 1:
         the plain call, no launch, no accumulator.  Out of order, a changed A, a plain call or ``optimizer.step()`` inside a
-        cycle raise; ``engine.abandon_accumulation()`` drops a cycle."""
+        cycle raise; ``engine.abandon_accumulation()`` drops a cycle.
+
+        ``teacher_logits``: knowledge distillation -- a (B, Q, T) fp32 device tensor in the physical layout ``engine.forward``
+        returns (``teacher.teacher_logits(x, h)``), a constant.  The loss per position becomes
+        ``(1 - distill_alpha) * ce + distill_alpha * distill_temperature^2 * KL(softmax(teacher / temperature) ||
+        softmax(student / temperature))`` (``engine.distill_loss``): the step is ``engine.forward`` -> ``distill_loss`` ->
+        ``engine.backward``, the logits reach memory.  Returns the mean of that loss; its parts (total, ce, unweighted kl) stay
+        in ``self.distill_parts``, a 3-element device tensor.  Everything else composes unchanged.  ``None``, or
+        ``distill_alpha == 0`` (the teacher then has no say): the fused cross-entropy step."""
+        if teacher_logits is not None:
+            if self.n_mixture > 0:
+                raise ValueError("distillation is defined for the softmax head (n_mixture = 0)")
+            if not 0.0 <= float(distill_alpha) <= 1.0:
+                raise ValueError("distill_alpha = %r outside [0, 1]" % (distill_alpha,))
+            if not (float(distill_temperature) > 0.0 and float(distill_temperature) < float("inf")):
+                raise ValueError("distill_temperature = %r must be positive and finite" % (distill_temperature,))
         eng = self._engine
         mode = eng.begin_micro_step(micro_step)
         if t_start is None:
             t_start = eng.receptive_field
+        if teacher_logits is not None and float(distill_alpha) != 0.0:
+            ragged = {} if lengths is None else {"lengths": lengths}
+            ts = self.trainable()
+            nothing = ts.empty and not aux_grad   # forward and loss only: no backward launch
+            logits = eng.forward(x, h)
+            self._fwd_serial += 1
+            loss3, dlogits = eng.distill_loss(logits, teacher_logits, t, distill_alpha, distill_temperature, t_start=t_start,
+                                              grad_scale=grad_scale, want_grad=not nothing, **ragged)
+            self.distill_parts = loss3
+            loss = loss3[0:1]
+            if nothing:
+                return self._nothing_to_train(loss, events, micro_step, mode)
+            dh = self._aux_grad_buffer(h) if aux_grad else None
+            flat = eng.backward(dlogits, events=events, layers_per_bucket=layers_per_bucket, t_first=t_start, dh=dh,
+                                **self._backward_needs(ts, aux_grad, events))
+            self._finish_micro_step(micro_step, mode, _accumulate)
+            self._point_grads(flat)
+            return (loss, dh) if aux_grad else loss
         # forward + loss in one call: the cross-entropy is the epilogue of conv_post_2 where the model allows it (the logits
         # never reach memory), and the backward pass runs its post-net part over the loss window only
         ragged = {} if lengths is None else {"lengths": lengths}
@@ -493,6 +528,12 @@ class WaveNet(nn.Module):
         self._finish_micro_step(micro_step, mode, _accumulate)
         self._point_grads(flat)
         return (loss, dh) if aux_grad else loss
+
+    def teacher_logits(self, x, h):
+        """This model as a distillation teacher: its logits for ``loss_and_backward(teacher_logits=...)`` of a student --
+        ``engine.forward`` without an autograd graph, the physical (B, Q, T) fp32 tensor."""
+        with torch.no_grad():
+            return self._engine.forward(x, h)
 
     def _backward_needs(self, ts, aux_grad, events=None):
         """What ``engine.backward`` has to compute for the model's trainable set: nothing extra when every parameter trains (the
