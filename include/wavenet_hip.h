@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 18
+#define WN_ABI_VERSION 19
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -312,6 +312,43 @@ int wn_softmax_distill_loss(const WnConfig* cfg, int B, int T, const float* logi
                             const int64_t* target, int t_start, const int32_t* t_end, int64_t n_loss, float alpha, float tau,
                             float grad_scale, float loss_scale, float* loss, float* dlogits, float* pos_loss, float* scratch,
                             void* ws, size_t ws_bytes, void* stream);
+
+/* Weighted cross-entropy (since ABI v19; additions only): the softmax head's criterion with one weight per class, label
+ * smoothing and one weight per position.  For every loss position i = (b, t) (t_start <= t < t_end[b], as
+ * wn_softmax_ce_loss_ragged) with s the logit column, y = target mod n_quantize, p = softmax(s), w = class_weights (NULL: ones),
+ * r = pos_weights (NULL: ones), Q = n_quantize, W = sum_q w_q:
+ *   ce_i = -log p_y
+ *   l_i  = (1 - eps) w_y ce_i + (eps / Q) sum_q w_q (-log p_q)      (a class with w_q == 0 adds exactly 0; not clamped)
+ *   g_iq = (1 - eps) w_y (p_q - [q == y]) + (eps / Q) (W p_q - w_q)
+ *   D    = sum_i r_i w_{y_i}  (normalize == 0, "weights": torch's mean reduction)  or  n_loss  (normalize == 1, "positions")
+ *   loss[0] = loss_scale * sum_i r_i l_i / D   -- the criterion; with r == NULL and normalize == 0 this is
+ *             torch.nn.functional.cross_entropy(s, y, weight=w, label_smoothing=eps)
+ *   loss[1] = loss_scale * sum_i ce_i / n_loss -- the plain unweighted cross-entropy of the same positions
+ *   loss[2] = D
+ *   dlogits_iq = grad_scale * r_i g_iq / D, EXACTLY 0.0f off the loss positions and where r_i == 0
+ *   pos_loss_i = r_i l_i (nullable, (B, T) out), 0 off the loss positions and where r_i == 0
+ * One deviation from torch: D == 0 gives loss[0] = 0 and dlogits = 0 exactly (torch: NaN).  A position with r_i == 0 is off: it
+ * adds 0 whatever its column holds.  Otherwise nothing is clamped: a -inf logit with eps > 0 and w_q > 0 gives l = +inf as in
+ * torch, a NaN or +inf stays in its column.
+ *   class_weights : nullable, (n_quantize,) fp32 on the device; pos_weights : nullable, (B, T) fp32 on the device.  Every weight
+ *                   finite and >= 0: the caller's contract, not checked here.
+ *   eps in [0, 1); normalize 0 or 1.  With "positions" and per-call shares n_loss_k / sum n_loss of grad_scale the objective
+ *   pooled over ranks and micro-batches is exact; with "weights" it is the share-weighted mean of per-call weighted means.
+ *   loss    : THREE floats on the device
+ *   dlogits : nullable; pos_loss : nullable.  The loss bits do not depend on whether either is given.
+ *   scratch : wn_softmax_cew_scratch_floats(B, T) floats on the device, 8-byte aligned; holds D, 1 / D and the per-block
+ *             partial sums, which are added in a fixed order (no atomics, no host synchronisation: the same inputs give the
+ *             same bits).  Nothing is read from it, or from the workspace, that the call did not write.
+ * The workspace keeps its size and layout; the call leaves max |dlogits| in the word the other loss calls use, so a backward
+ * call may take WN_FLAG_DW_F16_AMAX_WS.  Two plain launches on `stream`, four when D has to be summed on the device
+ * (normalize == 0 with a weight of either kind).  A mixture-of-logistics model (out_channels > 0), eps outside [0, 1), another
+ * normalize, a NULL among logits / target / loss / scratch, a misaligned scratch and the n_loss conditions of the ragged entry
+ * points are errors: no launch is made. */
+int64_t wn_softmax_cew_scratch_floats(int B, int T);
+int wn_softmax_cew_loss(const WnConfig* cfg, int B, int T, const float* logits, const int64_t* target, int t_start,
+                        const int32_t* t_end, int64_t n_loss, const float* class_weights, const float* pos_weights, float eps,
+                        int normalize, float grad_scale, float loss_scale, float* loss, float* dlogits, float* pos_loss,
+                        float* scratch, void* ws, size_t ws_bytes, void* stream);
 
 /* Scoring held-out data (since ABI v13; additions only): the negative log-likelihood of each sequence of a batch, without a
  * gradient and without a divisor.

@@ -138,7 +138,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -157,6 +157,7 @@ EXPORTS = [
     "wn_backward_needs", "wn_live_table", "wn_grad_norm_live", "wn_adam_step_live", "wn_adam_step_guarded_live",
     "wn_group_table", "wn_adam_step_groups", "wn_grad_norm_groups", "wn_adam_step_guarded_groups",
     "wn_softmax_distill_scratch_floats", "wn_softmax_distill_loss",
+    "wn_softmax_cew_scratch_floats", "wn_softmax_cew_loss",
 ]
 
 
@@ -239,6 +240,11 @@ class WnLibrary(object):
         L.wn_softmax_distill_scratch_floats.argtypes = [i, i]
         L.wn_softmax_distill_scratch_floats.restype = i64
         L.wn_softmax_distill_loss.argtypes = [cfgp, i, i, vp, vp, vp, i, vp, i64, f, f, f, f, vp, vp, vp, vp, vp, sz, vp]
+        # weighted cross-entropy (ABI v19): (.., logits, target, t_start, t_end, n_loss, class_weights, pos_weights, eps, normalize,
+        # grad_scale, loss_scale, loss (3 floats), dlogits, pos_loss, scratch, ws, ws_bytes, stream)
+        L.wn_softmax_cew_scratch_floats.argtypes = [i, i]
+        L.wn_softmax_cew_scratch_floats.restype = i64
+        L.wn_softmax_cew_loss.argtypes = [cfgp, i, i, vp, vp, i, vp, i64, vp, vp, f, i, f, f, vp, vp, vp, vp, vp, sz, vp]
         L.wn_op_front.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.wn_op_causal_conv.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.wn_op_causal_conv_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]

@@ -626,7 +626,47 @@ def get_parser():
     parser.add_argument("--distill_alpha", default=0.5, type=float,
                         help="weight of the teacher term in [0, 1]: loss = (1 - alpha) * ce + alpha * T^2 * kl")
     parser.add_argument("--distill_temperature", default=1.0, type=float, help="softmax temperature T > 0 of the teacher term")
+    # extension (not reference flags): torch's CrossEntropyLoss(weight=, label_smoothing=) in the HIP step
+    parser.add_argument("--label_smoothing", default=0.0, type=float,
+                        help="label smoothing E in [0, 1) of the softmax head's criterion (0: none)")
+    parser.add_argument("--class_weights", default=None, type=str,
+                        help="a .npy or text file of n_quantize floats, finite and >= 0: one weight per class of the criterion")
+    parser.add_argument("--loss_normalize", default="weights", type=str,
+                        help="weights: divide the weighted loss by the sum of the targets' weights (torch's mean); positions: by "
+                             "the number of loss positions (exact over ranks, --accum_steps and uneven batches)")
     return parser
+
+
+def check_criterion_args(args):
+    """The refusals of --label_smoothing / --class_weights / --loss_normalize, made while main() looks at the arguments; returns
+    the class weights as a host float32 tensor (None: no --class_weights).  ValueError with the reason."""
+    eps, path = float(getattr(args, "label_smoothing", 0.0)), getattr(args, "class_weights", None)
+    normalize = getattr(args, "loss_normalize", "weights")
+    if normalize not in ("weights", "positions"):
+        raise ValueError("--loss_normalize %s: weights or positions." % normalize)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError("--label_smoothing %g is outside [0, 1)." % eps)
+    if not path and eps == 0.0:
+        return None
+    for flag, on in (("--label_smoothing", eps != 0.0), ("--class_weights", bool(path))):
+        if on and args.n_mixture > 0:
+            raise ValueError("%s needs the softmax head: the criterion's options are not defined for --n_mixture %d." % (flag, args.n_mixture))
+        if on and getattr(args, "teacher", None):
+            raise ValueError("%s cannot go with --teacher: the distillation loss has no such option." % flag)
+    if not path:
+        return None
+    if not os.path.isfile(path):
+        raise ValueError("--class_weights %s does not exist." % path)
+    try:
+        values = np.load(path) if path.endswith(".npy") else np.loadtxt(path)
+        weights = torch.as_tensor(np.asarray(values, dtype=np.float64).reshape(-1))
+    except (ValueError, OSError) as err:
+        raise ValueError("--class_weights %s cannot be read as floats: %s" % (path, err))
+    if weights.numel() != args.n_quantize:
+        raise ValueError("--class_weights %s holds %d values, the model has n_quantize = %d classes." % (path, weights.numel(), args.n_quantize))
+    if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
+        raise ValueError("--class_weights %s: every weight must be finite and >= 0." % path)
+    return weights.float()
 
 
 TEACHER_MUST_MATCH = ("n_quantize", "n_aux", "upsampling_factor", "use_upsampling_layer")
@@ -880,6 +920,14 @@ def _worker(rank, world, args, port):
         dist.broadcast(model.engine.flat_params, src=0)
 
     loss_acc = torch.zeros(1, device=device)
+    # --label_smoothing / --class_weights: the weighted criterion (main() has made the refusals); its plain cross-entropy part is logged
+    class_weights, label_smoothing = check_criterion_args(args), float(getattr(args, "label_smoothing", 0.0))
+    weighted = class_weights is not None or label_smoothing != 0.0
+    if weighted:
+        class_weights = None if class_weights is None else class_weights.to(device)
+        logging.info("criterion: label smoothing %g, class weights from %s, normalized by %s." % (
+            label_smoothing, getattr(args, "class_weights", None), args.loss_normalize))
+    ce_acc = torch.zeros(1, device=device) if weighted else None
     distilling = teacher is not None and distill_alpha != 0.0   # (alpha == 0: the teacher has no say, the step is the plain one)
     parts_acc = torch.zeros(3, device=device) if distilling else None   # the total, its cross-entropy and its (unweighted) kl part
     norm_acc = torch.zeros(1, device=device)     # guarded optimizer: sum of the finite pre-clip gradient norms of the interval
@@ -930,6 +978,8 @@ def _worker(rank, world, args, port):
             if distilling:   # the teacher's forward on this rank's own micro-batch, then the student's step with its logits
                 ragged.update(teacher_logits=teacher.teacher_logits(batch_x, batch_h), distill_alpha=distill_alpha,
                               distill_temperature=distill_temperature)
+            if weighted:
+                ragged.update(class_weights=class_weights, label_smoothing=label_smoothing, normalize=args.loss_normalize)
             batch_loss = reducer.loss_and_backward(batch_x, batch_h, batch_t, y=item[2] if args.n_mixture > 0 else None,
                                                    grad_scale=share, **ragged)
             if k == accum_steps - 1:
@@ -937,6 +987,8 @@ def _worker(rank, world, args, port):
             loss_acc += batch_loss.detach() * (share * world)
             if distilling:
                 parts_acc += model.distill_parts.detach() * (share * world)
+            if weighted:
+                ce_acc += model.criterion_parts[1:2].detach() * (share * world)
         if optimizer.guarded:   # device-side accumulation, read at the interval's synchronisation below
             norm_acc += torch.nan_to_num(optimizer.grad_norm, nan=0.0, posinf=0.0)
         if args.verbose > 1:
@@ -951,6 +1003,9 @@ def _worker(rank, world, args, port):
                 if distilling:
                     dist.all_reduce(parts_acc)
                     parts_acc /= world
+                if weighted:
+                    dist.all_reduce(ce_acc)
+                    ce_acc /= world
             if is_main:
                 logging.info("(iter:%d) average loss = %.6f (%.3f sec / batch)" % (
                     i + 1, loss_acc.item() / args.intervals, total / args.intervals))
@@ -958,6 +1013,9 @@ def _worker(rank, world, args, port):
                     parts = (parts_acc / args.intervals).tolist()
                     logging.info("(iter:%d) average ce = %.6f, average kl = %.6f (alpha %g, temperature %g)" % (
                         i + 1, parts[1], parts[2], distill_alpha, distill_temperature))
+                if weighted:
+                    logging.info("(iter:%d) average ce = %.6f (label smoothing %g, normalized by %s)" % (
+                        i + 1, ce_acc.item() / args.intervals, label_smoothing, args.loss_normalize))
                 logging.info("estimated required time = " + _fmt_eta((args.iters - (i + 1)) * (total / args.intervals)))
             if optimizer.guarded:
                 # every rank holds the same reduced gradient, hence the same norm: nothing to exchange
@@ -971,6 +1029,8 @@ def _worker(rank, world, args, port):
             loss_acc.zero_()
             if distilling:
                 parts_acc.zero_()
+            if weighted:
+                ce_acc.zero_()
             total = 0.0
         if eval_interval > 0 and (i + 1) % eval_interval == 0:
             # every rank scores its shard of the held-out list; one all-reduce of [nll, positions] makes the mean
@@ -1035,6 +1095,7 @@ def main(argv=None):
         sys.exit(1)
     try:
         check_teacher_args(args)
+        check_criterion_args(args)
     except ValueError as err:
         logging.error(str(err))
         sys.exit(1)

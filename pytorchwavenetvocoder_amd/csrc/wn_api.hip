@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "../../include/wavenet_hip.h"
+#include "wn_cew.h"
 #include "wn_decode.h"
 #include "wn_distill.h"
 #include "wn_dlp.h"
@@ -1294,6 +1295,34 @@ extern "C" int wn_softmax_distill_loss(const WnConfig* cfg, int B, int T, const 
     WN_TRY(wn_softmax_distill(logits, teacher_logits, target, dlogits, pos_loss, scratch, B, T, c.d.Qo, t_start, t_end, alpha, tau,
                               grad_scale / count, loss_scale / count, loss, c.ws + c.w.dw_ovf + 2, c.st));   // + max |dlogits| (WN_FLAG_DW_F16_AMAX_WS)
     return rt_check("wn_softmax_distill_loss");
+}
+
+// Weighted cross-entropy head (since ABI v19): class weights, label smoothing and position weights, wn_cew.h.  The divisor and the
+// partial sums live in the caller's scratch, the workspace keeps its layout; only its max |dlogits| word is written, as by the
+// other loss calls.
+extern "C" int64_t wn_softmax_cew_scratch_floats(int B, int T) { return (int64_t)wn_cew_scratch_floats(B, T); }
+
+extern "C" int wn_softmax_cew_loss(const WnConfig* cfg, int B, int T, const float* logits, const int64_t* target, int t_start,
+                                   const int32_t* t_end, int64_t n_loss, const float* class_weights, const float* pos_weights,
+                                   float eps, int normalize, float grad_scale, float loss_scale, float* loss, float* dlogits,
+                                   float* pos_loss, float* scratch, void* wsp, size_t ws_bytes, void* stream) {
+    api_enter();
+    Ctx c;
+    WN_TRY(make_ctx(&c, cfg, B, T, wsp, ws_bytes, 0, stream));
+    if (cfg->out_channels > 0) return fail(1, "out_channels=%d: the weighted cross-entropy is defined for the softmax head only", cfg->out_channels);
+    if (!(eps >= 0.0f && eps < 1.0f)) return fail(1, "eps=%g outside [0, 1)", (double)eps);
+    if (normalize != 0 && normalize != 1) return fail(1, "normalize=%d: 0 (weights) or 1 (positions)", normalize);
+    if (!logits) return fail(1, "logits is NULL");
+    if (!target) return fail(1, "target is NULL");
+    if (!loss) return fail(1, "loss is NULL");
+    if (!scratch) return fail(1, "scratch is NULL");
+    if (((uintptr_t)scratch & 7u) != 0) return fail(1, "scratch is not 8-byte aligned");
+    float count = 0.f;
+    WN_TRY(loss_count(B, T, t_start, t_end, n_loss, &count));
+    const double n = t_end ? (double)n_loss : (double)B * (double)(T - t_start);
+    WN_TRY(wn_softmax_cew(logits, target, class_weights, pos_weights, dlogits, pos_loss, scratch, B, T, c.d.Qo, t_start, t_end, n, eps,
+                          normalize, grad_scale, loss_scale, loss, c.ws + c.w.dw_ovf + 2, c.st));   // + max |dlogits| (WN_FLAG_DW_F16_AMAX_WS)
+    return rt_check("wn_softmax_cew_loss");
 }
 
 // ------------------------------------------------------------------------------------------

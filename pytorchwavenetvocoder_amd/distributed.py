@@ -97,7 +97,8 @@ class GradientReducer(object):
         return self.model.loss_and_backward(x, h, t, **kw)
 
     def loss_and_backward(self, x, h, t, t_start=None, y=None, grad_scale=None, lengths=None, micro_step=None,
-                          teacher_logits=None, distill_alpha=0.5, distill_temperature=1.0):
+                          teacher_logits=None, distill_alpha=0.5, distill_temperature=1.0, class_weights=None,
+                          label_smoothing=0.0, position_weights=None, normalize="weights"):
         """forward + loss + backward with the bucketed all-reduce overlapped; returns the local
         mean loss (device tensor).  ``y`` (B, T) float selects the mixture-of-logistics loss.
         ``grad_scale``: this rank's share of the global minibatch (default 1/world = equal shards; pass
@@ -115,8 +116,18 @@ class GradientReducer(object):
         optimizer step, over all ranks and micro-steps (default 1 / (world * A): equal shards, equal micro-batches).
 
         ``teacher_logits`` / ``distill_alpha`` / ``distill_temperature``: knowledge distillation on this rank's shard, handed to
-        ``WaveNet.loss_and_backward`` on every route (the gradient is exchanged as ever; softmax head only)."""
+        ``WaveNet.loss_and_backward`` on every route (the gradient is exchanged as ever; softmax head only).
+
+        ``class_weights`` / ``label_smoothing`` / ``position_weights`` / ``normalize``: the weighted cross-entropy on this rank's
+        shard, handed to ``WaveNet.loss_and_backward`` likewise.  With the shares ``N_local / N_global`` as ``grad_scale``,
+        ``normalize="positions"`` makes the pooled objective exact; ``"weights"`` gives the share-weighted mean of the ranks'
+        weighted means, as torch DDP does."""
         kw = {} if lengths is None else {"lengths": lengths}
+        if class_weights is not None or float(label_smoothing) != 0.0 or position_weights is not None or normalize != "weights":
+            if y is not None:
+                raise ValueError("the weighted cross-entropy is defined for the softmax head: its options cannot go with y")
+            kw.update(class_weights=class_weights, label_smoothing=label_smoothing, position_weights=position_weights,
+                      normalize=normalize)
         if teacher_logits is not None:
             if y is not None:
                 raise ValueError("distillation is defined for the softmax head: teacher_logits cannot go with y")

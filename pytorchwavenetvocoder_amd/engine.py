@@ -136,6 +136,8 @@ class WaveNetEngine(object):
         self._lengths_dev = None
         self._eval_lengths = (None, None)  # the same pair for forward_nll
         self._distill_scratch = None  # partial sums of distill_loss (grown on demand; the call reads nothing it did not write)
+        self._cew_scratch = None  # divisor and partial sums of weighted_loss (likewise)
+        self._weights_seen = {}   # weighted_loss: name -> (weak reference, version, device copy) of the weight tensor checked last
         self._last_shape = None
         self._fwd_window = 0      # first loss position of the last forward_loss (0: a full forward)
         self._fwd_version = None  # parameter version the last forward packed its weight sets from
@@ -578,6 +580,90 @@ class WaveNetEngine(object):
                                               float(grad_scale), float(loss_scale), _ptr(loss3), _ptr(dlogits), _ptr(pos),
                                               _ptr(self._distill_scratch), _ptr(ws), ws.numel() * 4, _stream_handle(self.device))
         self.lib.check(rc, "wn_softmax_distill_loss")
+        self._note_bound(dlogits, grad_scale, count)
+        return (loss3, dlogits, pos) if want_pos else (loss3, dlogits)
+
+    NORMALIZE = {"weights": 0, "positions": 1}
+
+    def _weight_arg(self, w, shape, name):
+        """A weight tensor of ``weighted_loss`` -> its float32 copy on the engine's device.  Shape and dtype are checked, and on a
+        host tensor that every entry is finite and >= 0 -- once per tensor object and version, not once per step (a tensor that is
+        already on the device is the caller's contract: checking it would synchronise)."""
+        if w is None:
+            return None
+        if not isinstance(w, torch.Tensor):
+            w = torch.as_tensor(w, dtype=torch.float32)
+        seen = self._weights_seen.get(name)
+        if seen is not None and seen[2] is w:   # the copy this method made (loss_and_backward checks before it launches)
+            return w
+        if seen is not None and seen[0]() is w and seen[1] == w._version and seen[2].device == self.device:
+            return seen[2]
+        if tuple(w.shape) != tuple(shape) or w.dtype != torch.float32:
+            raise ValueError("%s must be a float32 tensor of shape %s, got %s %s" % (name, tuple(shape), tuple(w.shape), w.dtype))
+        if w.device.type == "cpu" and (not bool(torch.isfinite(w).all()) or bool((w < 0).any())):
+            raise ValueError("%s must be finite and >= 0 everywhere" % name)
+        dev = w.detach().contiguous().to(self.device)
+        self._weights_seen[name] = (weakref.ref(w), w._version, dev)
+        return dev
+
+    def weighted_loss_args(self, class_weights, label_smoothing, position_weights, normalize, B, Q, T):
+        """The refusals of ``weighted_loss``'s options, made before anything is launched; returns (eps, class weights, position
+        weights) with the weights on the device."""
+        if self.cfg.out_channels > 0:
+            raise ValueError("the weighted cross-entropy is defined for the softmax head (n_mixture = 0)")
+        eps = float(label_smoothing)
+        if not 0.0 <= eps < 1.0:
+            raise ValueError("label_smoothing = %r outside [0, 1)" % (label_smoothing,))
+        if normalize not in self.NORMALIZE:
+            raise ValueError("normalize = %r: \"weights\" or \"positions\"" % (normalize,))
+        return (eps, self._weight_arg(class_weights, (Q,), "class_weights"),
+                self._weight_arg(position_weights, (B, T), "position_weights"))
+
+    def weighted_loss(self, logits, target, class_weights=None, label_smoothing=0.0, position_weights=None, normalize="weights",
+                      t_start=None, grad_scale=1.0, loss_scale=1.0, want_grad=True, lengths=None, want_pos=False):
+        """Weighted cross-entropy of the softmax head (``wn_softmax_cew_loss``): torch's ``CrossEntropyLoss(weight=class_weights,
+        label_smoothing=label_smoothing)`` with one more weight per position.  Per loss position, with ``p = softmax(logits)``,
+        ``y`` the target, ``w`` the (Q,) ``class_weights`` and ``r`` the (B, T) ``position_weights`` (None: ones),
+        ``l = (1 - eps) w_y (-log p_y) + eps / Q sum_q w_q (-log p_q)``; the criterion is ``sum r l / D`` with
+        ``D = sum r w_y`` (``normalize="weights"``: torch's mean; with ``r`` None exactly ``F.cross_entropy(weight=,
+        label_smoothing=)``) or ``D = N``, the number of loss positions (``normalize="positions"``).  ``"positions"`` is the
+        choice for several ranks or micro-batches: with the per-call shares ``N_k / sum N`` as ``grad_scale`` the pooled
+        objective is exact; with ``"weights"`` it is the share-weighted mean of the per-call weighted means, which is what torch
+        DDP gives.  ``D == 0`` gives a loss and a gradient of exactly 0 (torch: NaN); a position with ``r == 0`` is off.
+
+        ``logits``: (B, Q, T) fp32 in the physical layout ``forward`` returns.  Weights must be finite and >= 0: checked on host
+        tensors, once per tensor.  Returns ``(loss3, dlogits[, pos_loss])``: ``loss3`` a 3-element device tensor -- the
+        criterion, the plain unweighted cross-entropy mean over the same positions, and ``D``; ``dlogits`` for ``backward``
+        (None without ``want_grad``; exactly zero off the loss positions and where ``r == 0``); ``pos_loss`` (B, T), ``r l`` per
+        position, with ``want_pos``.  ``t_start`` / ``lengths`` / ``grad_scale`` / ``loss_scale`` as ``loss``."""
+        self._check_device(logits, target)
+        if self.cfg.out_channels > 0:
+            raise ValueError("the weighted cross-entropy is defined for the softmax head (n_mixture = 0)")
+        if logits.dim() != 3 or logits.dtype != torch.float32 or not logits.is_contiguous():
+            raise ValueError("logits must be a contiguous float32 (B, Q, T) tensor")
+        B, Q, T = logits.shape
+        if tuple(target.shape) != (B, T) or target.dtype != torch.int64:
+            raise ValueError("target must be a (B, T) LongTensor")
+        target = target.contiguous()
+        eps, cw, pw = self.weighted_loss_args(class_weights, label_smoothing, position_weights, normalize, B, Q, T)
+        if t_start is None:
+            t_start = self.receptive_field
+        ws = self.workspace(B, T)
+        n_scratch = int(self.lib.wn_softmax_cew_scratch_floats(B, T))
+        if self._cew_scratch is None or self._cew_scratch.numel() < n_scratch or self._cew_scratch.device != logits.device:
+            self._cew_scratch = torch.empty(n_scratch, dtype=torch.float32, device=self.device)
+        loss3 = torch.empty(3, dtype=torch.float32, device=self.device)
+        dlogits = torch.empty_like(logits) if want_grad else None
+        pos = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_pos else None
+        if lengths is None:
+            t_end, count = None, B * (T - int(t_start))
+        else:
+            t_end, count = self._lengths_arg(lengths, B, T, t_start)
+        rc = self.lib.wn_softmax_cew_loss(ctypes.byref(self.cfg), B, T, _ptr(logits), _ptr(target), int(t_start), _ptr(t_end), count,
+                                          _ptr(cw), _ptr(pw), eps, self.NORMALIZE[normalize], float(grad_scale), float(loss_scale),
+                                          _ptr(loss3), _ptr(dlogits), _ptr(pos), _ptr(self._cew_scratch), _ptr(ws), ws.numel() * 4,
+                                          _stream_handle(self.device))
+        self.lib.check(rc, "wn_softmax_cew_loss")
         self._note_bound(dlogits, grad_scale, count)
         return (loss3, dlogits, pos) if want_pos else (loss3, dlogits)
 

@@ -381,6 +381,7 @@ class WaveNet(nn.Module):
         assert self._engine.receptive_field == self.receptive_field
         self._fwd_serial = 0
         self.distill_parts = None   # (total, ce, kl) means of the last distillation step, a device tensor
+        self.criterion_parts = None   # (criterion, plain ce mean, divisor) of the last step with class / position weights or smoothing
         self._param_slices = []
         self._trainable_cache = {}   # trainable(): flags as given -> TrainableSet
         self._flatten()
@@ -446,7 +447,8 @@ class WaveNet(nn.Module):
 
     def loss_and_backward(self, x, h, t, t_start=None, grad_scale=1.0, events=None, layers_per_bucket=0, aux_grad=False,
                           lengths=None, micro_step=None, _accumulate=True, teacher_logits=None, distill_alpha=0.5,
-                          distill_temperature=1.0):
+                          distill_temperature=1.0, class_weights=None, label_smoothing=0.0, position_weights=None,
+                          normalize="weights"):
         """Fused training half-step: forward -> CrossEntropy on ``[:, t_start:]`` -> backward
         (reference train.py:533-538) without an autograd graph.
 
@@ -483,7 +485,26 @@ class WaveNet(nn.Module):
         softmax(student / temperature))`` (``engine.distill_loss``): the step is ``engine.forward`` -> ``distill_loss`` ->
         ``engine.backward``, the logits reach memory.  Returns the mean of that loss; its parts (total, ce, unweighted kl) stay
         in ``self.distill_parts``, a 3-element device tensor.  Everything else composes unchanged.  ``None``, or
-        ``distill_alpha == 0`` (the teacher then has no say): the fused cross-entropy step."""
+        ``distill_alpha == 0`` (the teacher then has no say): the fused cross-entropy step.
+
+        ``class_weights`` ((Q,) fp32), ``label_smoothing`` (in [0, 1)), ``position_weights`` ((B, T) fp32): the criterion becomes
+        torch's ``CrossEntropyLoss(weight=class_weights, label_smoothing=label_smoothing)`` with one more weight per position
+        (``engine.weighted_loss``, where the formulas are): the step is ``engine.forward`` -> ``weighted_loss`` ->
+        ``engine.backward``, the logits reach memory.  ``normalize="weights"`` divides by the sum of the weights of the targets
+        (torch's mean), ``"positions"`` by the number of loss positions: with shares ``N_k / sum N`` as ``grad_scale`` over ranks
+        and micro-batches ``"positions"`` pools exactly, ``"weights"`` gives the share-weighted mean of per-call weighted means
+        (what torch DDP gives).  Weights must be finite and >= 0 (checked on host tensors, once per tensor).  Returns the
+        criterion; (criterion, plain unweighted cross-entropy mean, divisor) stay in ``self.criterion_parts``, a 3-element device
+        tensor.  Everything else composes unchanged; not together with ``teacher_logits``.  With the three options at their
+        defaults the step is the fused one, launch for launch."""
+        weighted = class_weights is not None or float(label_smoothing) != 0.0 or position_weights is not None
+        if weighted or normalize != "weights":
+            if self.n_mixture > 0:
+                raise ValueError("the weighted cross-entropy is defined for the softmax head (n_mixture = 0)")
+            if teacher_logits is not None:
+                raise ValueError("class_weights / label_smoothing / position_weights cannot go with teacher_logits")
+            eps, class_weights, position_weights = self._engine.weighted_loss_args(
+                class_weights, label_smoothing, position_weights, normalize, x.shape[0], self.n_quantize, x.shape[1])
         if teacher_logits is not None:
             if self.n_mixture > 0:
                 raise ValueError("distillation is defined for the softmax head (n_mixture = 0)")
@@ -495,15 +516,21 @@ class WaveNet(nn.Module):
         mode = eng.begin_micro_step(micro_step)
         if t_start is None:
             t_start = eng.receptive_field
-        if teacher_logits is not None and float(distill_alpha) != 0.0:
+        distilling = teacher_logits is not None and float(distill_alpha) != 0.0
+        if distilling or weighted:   # another loss head beside the fused epilogue: the logits reach memory
             ragged = {} if lengths is None else {"lengths": lengths}
             ts = self.trainable()
             nothing = ts.empty and not aux_grad   # forward and loss only: no backward launch
             logits = eng.forward(x, h)
             self._fwd_serial += 1
-            loss3, dlogits = eng.distill_loss(logits, teacher_logits, t, distill_alpha, distill_temperature, t_start=t_start,
-                                              grad_scale=grad_scale, want_grad=not nothing, **ragged)
-            self.distill_parts = loss3
+            if distilling:
+                loss3, dlogits = eng.distill_loss(logits, teacher_logits, t, distill_alpha, distill_temperature, t_start=t_start,
+                                                  grad_scale=grad_scale, want_grad=not nothing, **ragged)
+                self.distill_parts = loss3
+            else:
+                loss3, dlogits = eng.weighted_loss(logits, t, class_weights, eps, position_weights, normalize, t_start=t_start,
+                                                   grad_scale=grad_scale, want_grad=not nothing, **ragged)
+                self.criterion_parts = loss3
             loss = loss3[0:1]
             if nothing:
                 return self._nothing_to_train(loss, events, micro_step, mode)
