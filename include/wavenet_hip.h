@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 19
+#define WN_ABI_VERSION 20
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -612,6 +612,58 @@ int wn_grad_norm_groups(const float* grads, int64_t n, const int64_t* table, int
 int wn_adam_step_guarded_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
                                 const int64_t* table, int n_ranges, int64_t n_live, const WnGroupScalars* group_scalars,
                                 const WnOptState* state, double ema_decay, int ema_warmup, void* stream);
+
+/* ---- layer-wise adaptive steps (LAMB) and per-tensor norms (since ABI v20; additions only) ----
+ * A per-tensor trust ratio on top of the grouped Adam update (You et al. 2019), for batch sizes far above the one a recipe's
+ * learning rate was tuned at.  For tensor k of group g at applied step t (1-based: `step` unguarded, the state block's
+ * steps_applied guarded), bc1 = 1 - beta1^t and bc2 = 1 - beta2^t formed in double:
+ *     ghat = clip_coef * grad                     (guarded; one separately rounded product, grad itself keeps its values)
+ *     L2 group:        ghat += wd_g * p           (before the moments, as in wn_adam_step*)
+ *     m, v             the expressions of wn_adam_step*: an adapted tensor's moments are the grouped launch's bit for bit
+ *     u    = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps_g)
+ *     decoupled group: u = fma(wd_g, p, u)
+ *     wn_k = sqrt(sum p^2), un_k = sqrt(sum u^2)  over the tensor, p BEFORE the update, both sums in double
+ *     r_k  = wn_k == 0 or un_k == 0 ? 1 : wn_k / un_k;   r_k = min(r_k, max_trust) when max_trust > 0
+ *     p    = fma(-(lr_g * r_k), u, p);   ema = fmaf(w, p_new - ema, ema), w as in wn_adam_step_ema
+ * A tensor that does not adapt takes the grouped Adam update: params, exp_avg, exp_avg_sq and ema receive the bits
+ * wn_adam_step_groups / wn_adam_step_guarded_groups give them for the same inputs.  Guard: when apply == 0 nothing is written --
+ * weights, moments, average and `stats` stay.  An element outside every range is neither read nor written in any buffer.
+ * Guard off and a non-finite gradient: the norm of u is not finite, so the ratio and with it EVERY weight of that tensor is
+ * poisoned (plain Adam poisons the one element); no other tensor is touched.  Use the guard.
+ *
+ * wn_tensor_table (host only, no launch): wn_group_table for quadruples lo, hi, group, adapt (0 | 1) -- ONE range per tensor, never
+ * coalesced.  It writes at most 7 * n_ranges + 1 + n / WN_TENSOR_CHUNK int64 words (size `table` for that; copy them all to the
+ * device): the four rows of wn_group_table (the _live and _groups norm calls read the table as it is), adapt[n_ranges],
+ * block0[n_ranges] = the index of the first block of each range, the number of blocks, and the range of every block.
+ * Every range owns ceil(len / WN_TENSOR_CHUNK) blocks of its own: the grid and every summation order are functions of the table
+ * alone (and of the buffers' address modulo 16), never of the device, so data-parallel ranks derive the same ratios bit for bit
+ * without communicating.  Returns n_live, -1 on an error (wn_last_error: those of wn_group_table, an adapt flag that is not 0 | 1).
+ * wn_tensor_blocks: the number of blocks of a HOST table; wn_lamb_scratch_floats(n_blocks): floats of scratch (8-byte aligned)
+ * wn_lamb_step and wn_tensor_sumsq need for it.
+ *
+ *   wn_lamb_step     three launches: (1) per block of an adapted range the moments, u and the sums of p^2 and u^2 in double, one
+ *                    pair of partials per block, no atomics -- a range that does not adapt gets its whole Adam update here; (2)
+ *                    per tensor the partials in block order -> stats[3 k .. 3 k + 2] = wn_k, un_k, r_k as floats (a tensor that
+ *                    does not adapt: 0, 0, 1); (3) adapted ranges again: u recomputed from the stored moments, the weight and the
+ *                    average written (10 words per element in all, no n-sized temporary).  16-byte accesses where the buffers
+ *                    share their address modulo 16.  state == NULL: the unguarded step with `step`; otherwise `step` is ignored
+ *                    and apply, clip_coef, steps_applied and the betas are read from `state` as the preceding wn_grad_norm* call
+ *                    on the same stream left them (WnOptState keeps its 56 bytes).  `groups` is host memory and travels in the
+ *                    launch arguments.  ema == NULL: no moving average.  max_trust == 0: no clamp.
+ *   wn_tensor_sumsq  the same segmented reduction for any flat fp32 buffer of n elements: out[k] (device, double) = the sum of
+ *                    x[i]^2 over range k.  Two launches.
+ * Errors (wn_last_error): those of the _groups calls; max_trust < 0 or NaN; scratch, stats or out NULL; scratch / out not
+ * 8-byte aligned. */
+#define WN_TENSOR_CHUNK 8192
+int64_t wn_tensor_table(const int64_t* quads, int n_ranges, int64_t n, int n_groups, int64_t* table);
+int64_t wn_tensor_blocks(const int64_t* table, int n_ranges);
+int64_t wn_lamb_scratch_floats(int64_t n_blocks);
+int wn_tensor_sumsq(const float* x, int64_t n, const int64_t* table, int n_ranges, int64_t n_live, float* scratch, double* out,
+                    void* stream);
+int wn_lamb_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, const int64_t* table,
+                 int n_ranges, int64_t n_live, int64_t step, const WnAdamGroup* groups, int n_groups, float beta1, float beta2,
+                 float max_trust, const WnOptState* state, double ema_decay, int ema_warmup, float* scratch, float* stats,
+                 void* stream);
 
 /* ---- op-level entry points (used by the composite calls above; exported for parity tests) ---- */
 

@@ -69,6 +69,7 @@ class WnOptState(ctypes.Structure):
 
 
 MAX_PARAM_GROUPS = 16   # WN_MAX_PARAM_GROUPS
+TENSOR_CHUNK = 8192     # WN_TENSOR_CHUNK: elements per block of a tensor table (ABI v20)
 
 
 class WnAdamGroup(ctypes.Structure):
@@ -138,7 +139,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -158,6 +159,7 @@ EXPORTS = [
     "wn_group_table", "wn_adam_step_groups", "wn_grad_norm_groups", "wn_adam_step_guarded_groups",
     "wn_softmax_distill_scratch_floats", "wn_softmax_distill_loss",
     "wn_softmax_cew_scratch_floats", "wn_softmax_cew_loss",
+    "wn_tensor_table", "wn_tensor_blocks", "wn_lamb_scratch_floats", "wn_tensor_sumsq", "wn_lamb_step",
 ]
 
 
@@ -245,6 +247,17 @@ class WnLibrary(object):
         L.wn_softmax_cew_scratch_floats.argtypes = [i, i]
         L.wn_softmax_cew_scratch_floats.restype = i64
         L.wn_softmax_cew_loss.argtypes = [cfgp, i, i, vp, vp, i, vp, i64, vp, vp, f, i, f, f, vp, vp, vp, vp, vp, sz, vp]
+        # layer-wise adaptive steps (ABI v20): (host quadruples lo, hi, group, adapt; n_ranges, n, n_groups, host table) -> n_live;
+        # (host table, n_ranges) -> blocks; wn_lamb_step(.., table, n_ranges, n_live, step, groups, n_groups, beta1, beta2, max_trust,
+        # state | NULL, ema_decay, ema_warmup, scratch, stats, stream)
+        L.wn_tensor_table.argtypes = [vp, i, i64, i, vp]
+        L.wn_tensor_table.restype = i64
+        L.wn_tensor_blocks.argtypes = [vp, i]
+        L.wn_tensor_blocks.restype = i64
+        L.wn_lamb_scratch_floats.argtypes = [i64]
+        L.wn_lamb_scratch_floats.restype = i64
+        L.wn_tensor_sumsq.argtypes = [vp, i64, vp, i, i64, vp, vp, vp]
+        L.wn_lamb_step.argtypes = [vp, vp, vp, vp, vp, i64, vp, i, i64, i64, vp, i, f, f, f, vp, d, i, vp, vp, vp]
         L.wn_op_front.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.wn_op_causal_conv.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.wn_op_causal_conv_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]

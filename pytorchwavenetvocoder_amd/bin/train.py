@@ -618,6 +618,11 @@ def get_parser():
                         help="repeatable: the tensors whose name matches REGEX (re.search; the first matching group wins) get "
                              "their own lr=, weight_decay=, eps= and decoupled=true|false (AdamW's decay); a missing key takes "
                              "--lr / --weight_decay.  Give the same groups with --resume: the checkpoint's values then win")
+    # extension (not reference flags): layer-wise adaptive steps of FusedAdam (LAMB) for large batches
+    parser.add_argument("--layer_adaptation", default=False, type=strtobool,
+                        help="scale every adapted tensor's step by its trust ratio ||w|| / ||update||; tensors with two or more "
+                             "dimensions adapt, biases do not (--param_group 'REGEX:adapt=true|false' overrides that per group)")
+    parser.add_argument("--max_trust_ratio", default=0.0, type=float, help="upper bound of the trust ratio (0: none)")
     # extension (not reference flags): knowledge distillation from a trained model
     parser.add_argument("--teacher", default=None, type=str,
                         help="checkpoint of a trained softmax-head model whose output distribution the model is trained against "
@@ -715,7 +720,8 @@ def build_teacher(config, checkpoint, device):
     return teacher
 
 
-PARAM_GROUP_KEYS = {"lr": "lr", "weight_decay": "weight_decay", "eps": "eps", "decoupled": "decoupled_weight_decay"}
+PARAM_GROUP_KEYS = {"lr": "lr", "weight_decay": "weight_decay", "eps": "eps", "decoupled": "decoupled_weight_decay",
+                    "adapt": "layer_adaptation"}
 
 
 def parse_param_group(spec):
@@ -735,7 +741,7 @@ def parse_param_group(spec):
         if not eq or key not in PARAM_GROUP_KEYS:
             raise ValueError("--param_group %r: %r is not one of %s=VALUE" % (spec, item, ", ".join(sorted(PARAM_GROUP_KEYS))))
         try:
-            out[PARAM_GROUP_KEYS[key]] = bool(strtobool(value.strip())) if key == "decoupled" else float(value)
+            out[PARAM_GROUP_KEYS[key]] = bool(strtobool(value.strip())) if key in ("decoupled", "adapt") else float(value)
         except ValueError:
             raise ValueError("--param_group %r: bad value in %r" % (spec, item))
     return pattern, out
@@ -871,17 +877,25 @@ def _worker(rank, world, args, port):
     max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
     ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
     groups = [parse_param_group(spec) for spec in (getattr(args, "param_group", None) or [])]   # (main() has checked the syntax)
+    layer_adaptation = bool(getattr(args, "layer_adaptation", False))
+    max_trust_ratio = float(getattr(args, "max_trust_ratio", 0.0) or 0.0)
+    lamb = {"layer_adaptation": True, "max_trust_ratio": max_trust_ratio if max_trust_ratio > 0.0 else None} if layer_adaptation else {}
     try:
         optimizer = FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay,
                               max_grad_norm=max_grad_norm if max_grad_norm > 0.0 else None,
                               skip_nonfinite=bool(getattr(args, "skip_nonfinite_steps", False)),
                               ema_decay=ema_decay if ema_decay > 0.0 else None, ema_warmup=bool(getattr(args, "ema_warmup", True)),
-                              **({"groups": groups} if groups else {}))
+                              **dict({"groups": groups} if groups else {}, **lamb))
     except ValueError as err:
         if not groups:
             raise
         logging.error("--param_group: %s" % err)
         sys.exit(1)
+    if layer_adaptation:
+        logging.info("layer-wise adaptive steps: tensors with two or more dimensions adapt, max trust ratio %s%s" % (
+            "%g" % max_trust_ratio if max_trust_ratio > 0.0 else "none",
+            "".join("; group %d (%r) adapt=%s" % (i, groups[i - 1][0], g["layer_adaptation"])
+                    for i, g in enumerate(optimizer.param_groups) if "layer_adaptation" in g)))
     for i, g in enumerate(optimizer.param_groups if groups else []):
         logging.info("parameter group %d (%s): lr=%g weight_decay=%g eps=%g decoupled=%s, %d tensors, %d elements" % (
             i, "default" if i == 0 else repr(groups[i - 1][0]), g["lr"], g["weight_decay"], g["eps"],
@@ -1026,6 +1040,11 @@ def _worker(rank, world, args, port):
                     logging.info("(iter:%d) average gradient norm before clipping = %.6f, skipped steps = %d" % (
                         i + 1, norm_acc.item() / finite, skipped))
                 norm_acc.zero_()
+            if layer_adaptation and is_main and any(optimizer.tensor_adapts or ()):
+                # one read, here only: every rank derives the same ratios (the step needs none of them on the host)
+                ratios = optimizer.trust_ratios.cpu()[torch.tensor(optimizer.tensor_adapts)]
+                logging.info("(iter:%d) trust ratio min = %.4g, median = %.4g, max = %.4g (%d adapted tensors)" % (
+                    i + 1, ratios.min().item(), ratios.median().item(), ratios.max().item(), ratios.numel()))
             loss_acc.zero_()
             if distilling:
                 parts_acc.zero_()
@@ -1089,6 +1108,12 @@ def main(argv=None):
             parse_param_group(spec)
     except ValueError as err:
         logging.error(str(err))
+        sys.exit(1)
+    if args.max_trust_ratio < 0.0 or (args.max_trust_ratio > 0.0 and not args.layer_adaptation):
+        logging.error("--max_trust_ratio takes a positive bound and needs --layer_adaptation true.")
+        sys.exit(1)
+    if not args.layer_adaptation and any("layer_adaptation" in parse_param_group(spec)[1] for spec in args.param_group or []):
+        logging.error("--param_group ...:adapt= needs --layer_adaptation true.")
         sys.exit(1)
     if args.pretrained and args.resume:
         logging.error("--pretrained starts iteration 0 from a checkpoint's weights, --resume continues a run: give one of them.")

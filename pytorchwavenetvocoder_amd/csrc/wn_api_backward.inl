@@ -786,3 +786,77 @@ extern "C" int wn_adam_step_guarded_groups(float* params, const float* grads, fl
                                   group_scalars, state, ema_decay, ema_warmup, (wn_stream_t)stream));
     return rt_check("wn_adam_step_guarded_groups");
 }
+
+// ------------------------------------------------------------------------------------------
+// Layer-wise adaptive steps and per-tensor sums of squares (ABI v20): the tensor table -- the group table with one range per
+// tensor, an adapt flag and the first block of every range -- and the calls that walk it.
+extern "C" int64_t wn_tensor_table(const int64_t* quads, int n_ranges, int64_t n, int n_groups, int64_t* table) {
+    g_err[0] = 0;   // pure host code: no runtime call to clear
+    if (!quads || !table) return fail(1, "wn_tensor_table: NULL argument"), -1;
+    if (n_ranges <= 0) return fail(1, "wn_tensor_table: an empty table (n_ranges = %d)", n_ranges), -1;
+    if (n <= 0) return fail(1, "wn_tensor_table: n <= 0"), -1;
+    if (n_groups < 1 || n_groups > WN_MAX_PARAM_GROUPS) return fail(1, "wn_tensor_table: n_groups = %d outside [1, %d]", n_groups, WN_MAX_PARAM_GROUPS), -1;
+    const int64_t nr = n_ranges;
+    int64_t before = 0, prev_hi = 0, blocks = 0;
+    for (int r = 0; r < n_ranges; ++r) {
+        const int64_t lo = quads[4 * r], hi = quads[4 * r + 1], grp = quads[4 * r + 2], adapt = quads[4 * r + 3];
+        if (lo < 0 || hi > n) return fail(1, "wn_tensor_table: range %d = [%lld, %lld) outside [0, %lld)", r, (long long)lo, (long long)hi, (long long)n), -1;
+        if (hi <= lo) return fail(1, "wn_tensor_table: range %d = [%lld, %lld) is empty", r, (long long)lo, (long long)hi), -1;
+        if (r > 0 && lo < prev_hi) return fail(1, "wn_tensor_table: range %d = [%lld, %lld) is not behind range %d (the ranges must be sorted and disjoint)", r, (long long)lo, (long long)hi, r - 1), -1;
+        if (grp < 0 || grp >= n_groups) return fail(1, "wn_tensor_table: range %d has group %lld outside [0, %d)", r, (long long)grp, n_groups), -1;
+        if (adapt != 0 && adapt != 1) return fail(1, "wn_tensor_table: range %d has adapt flag %lld (0 or 1)", r, (long long)adapt), -1;
+        table[r] = lo;
+        table[nr + r] = hi;
+        table[2 * nr + r] = before;
+        table[3 * nr + r] = grp;
+        table[4 * nr + r] = adapt;
+        table[5 * nr + r] = blocks;
+        before += hi - lo;
+        for (int64_t left = hi - lo; left > 0; left -= WN_TENSOR_CHUNK) table[6 * nr + 1 + blocks++] = r;
+        prev_hi = hi;
+    }
+    table[6 * nr] = blocks;
+    return before;
+}
+
+extern "C" int64_t wn_tensor_blocks(const int64_t* table, int n_ranges) {
+    g_err[0] = 0;
+    if (!table || n_ranges <= 0) return fail(1, "wn_tensor_blocks: NULL table or n_ranges <= 0"), -1;
+    return table[6 * (int64_t)n_ranges];
+}
+
+extern "C" int64_t wn_lamb_scratch_floats(int64_t n_blocks) {
+    return n_blocks > 0 ? 4 * n_blocks : 0;   // two doubles per block
+}
+
+extern "C" int wn_tensor_sumsq(const float* x, int64_t n, const int64_t* table, int n_ranges, int64_t n_live, float* scratch,
+                               double* out, void* stream) {
+    api_enter();
+    if (!x || !scratch || !out || n <= 0) return fail(1, "bad wn_tensor_sumsq argument");
+    if (const char* why = live_argument_error(table, n_ranges, n_live, n)) return fail(1, "wn_tensor_sumsq: %s", why);
+    if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 7) || (reinterpret_cast<uintptr_t>(out) & 7))
+        return fail(1, "wn_tensor_sumsq: x needs 4-byte, scratch and out 8-byte alignment");
+    WN_TRY(wn_tensor_sumsq_launch(x, reinterpret_cast<const long*>(table), n_ranges, (long)n_live, reinterpret_cast<double*>(scratch),
+                                  out, (wn_stream_t)stream));
+    return rt_check("wn_tensor_sumsq");
+}
+
+extern "C" int wn_lamb_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                            const int64_t* table, int n_ranges, int64_t n_live, int64_t step, const WnAdamGroup* groups, int n_groups,
+                            float beta1, float beta2, float max_trust, const WnOptState* state, double ema_decay, int ema_warmup,
+                            float* scratch, float* stats, void* stream) {
+    api_enter();
+    if (!adam_buffers_ok(params, grads, exp_avg, exp_avg_sq, n) || (!state && step < 1)) return fail(1, "bad wn_lamb_step argument");
+    if (const char* why = live_argument_error(table, n_ranges, n_live, n)) return fail(1, "wn_lamb_step: %s", why);
+    if (const char* why = group_argument_error(groups, n_groups)) return fail(1, "wn_lamb_step: %s", why);
+    if (ema)
+        if (const char* why = ema_argument_error(params, ema, n, ema_decay)) return fail(1, "wn_lamb_step: %s", why);
+    if (!(max_trust >= 0.0f)) return fail(1, "wn_lamb_step: max_trust < 0 (0 = no clamp)");
+    if (!scratch || !stats) return fail(1, "wn_lamb_step: scratch or stats is NULL");
+    if ((reinterpret_cast<uintptr_t>(scratch) & 7) || (reinterpret_cast<uintptr_t>(stats) & 3) || (reinterpret_cast<uintptr_t>(state) & 7))
+        return fail(1, "wn_lamb_step: scratch and state need 8-byte, stats 4-byte alignment");
+    WN_TRY(wn_lamb(params, grads, exp_avg, exp_avg_sq, ema, reinterpret_cast<const long*>(table), n_ranges, (long)n_live, (long)step,
+                   groups, n_groups, beta1, beta2, max_trust, state, ema_decay, ema_warmup, reinterpret_cast<double*>(scratch), stats,
+                   (wn_stream_t)stream));
+    return rt_check("wn_lamb_step");
+}

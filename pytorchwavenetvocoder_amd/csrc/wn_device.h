@@ -53,6 +53,7 @@ static inline void wn_rt_event_record(void*, wn_stream_t) {}
 #define WN_PIN(x) ((void)(x))
 #define WN_PIN2(x, y) ((void)(x), (void)(y))
 static inline float wn_fmul_rn(float a, float b) { return a * b; }   // (built with -ffp-contract=off)
+static inline float wn_fma_contracted(float a, float b, float c) { return a * b + c; }   // (two roundings here, as always)
 // 2^x, 1 / x, log2 x; the sum over each aligned group of 16 lanes
 static inline float wn_exp2(float x) { return exp2f(x); }
 static inline float wn_rcp(float x) { return 1.0f / x; }
@@ -250,6 +251,9 @@ static inline void wn_rt_event_record(void* ev, wn_stream_t st) { (void)hipEvent
 #define WN_PIN2(x, y) asm volatile("" : "+v"(x), "+v"(y))   // (one statement: two would be two scheduling points)
 // a product that is never contracted into a neighbouring fma
 static __device__ __forceinline__ float wn_fmul_rn(float a, float b) { return __fmul_rn(a, b); }
+// a * b + c as the fma hipcc contracts it into, said out loud: an expression that several kernels must round alike cannot leave
+// the choice of WHICH of its products is fused to each kernel's instruction selection
+static __device__ __forceinline__ float wn_fma_contracted(float a, float b, float c) { return __fmaf_rn(a, b, c); }
 #define WN_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) char name[]
 static __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);

@@ -75,6 +75,22 @@ int wn_adam_guarded_groups(float* p, const float* g, float* m, float* v, float* 
 int wn_grad_norm_finalize_groups(const double* partial, int nb, float max_norm, int guard, const struct WnAdamGroup* groups,
                                  int n_groups, float beta1, float beta2, struct WnOptState* state, struct WnGroupScalars* block,
                                  wn_stream_t st);
+// Layer-wise adaptive steps and per-tensor sums of squares over a TENSOR table (include/wavenet_hip.h, ABI v20; wn_tensor_table
+// wrote it).  wn_bias_correction is the ONE place the two bias corrections of an applied step t are formed, in double, for the host
+// (unguarded step: t = the caller's step) and for every thread of the guarded launches (t = the state block's steps_applied).
+struct WnBiasCorrection {
+    double bc1, bc2;
+};
+static __host__ __device__ __forceinline__ WnBiasCorrection wn_bias_correction(float beta1, float beta2, int64_t t) {
+    return {1.0 - pow((double)beta1, (double)t), 1.0 - pow((double)beta2, (double)t)};
+}
+// three launches (moments + partial sums, ratios, apply); state == NULL: the unguarded step with the host's `step`, otherwise
+// apply, clip_coef, steps_applied and the betas come from the state block.  partial: 2 doubles per block; stats: 3 floats per range
+int wn_lamb(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live, long step,
+            const struct WnAdamGroup* groups, int n_groups, float beta1, float beta2, float max_trust, const struct WnOptState* state,
+            double ema_decay, int ema_warmup, double* partial, float* stats, wn_stream_t st);
+// out[r] = sum of x[i]^2 over range r of the table, in double (two launches; partial: one double per block)
+int wn_tensor_sumsq_launch(const float* x, const long* table, int nr, long n_live, double* partial, double* out, wn_stream_t st);
 // a[i] <-> b[i], i < n: two non-overlapping fp32 buffers of 4-byte alignment, exchanged in place
 int wn_swap(float* a, float* b, long n, wn_stream_t st);
 // gradient accumulation over micro-batches (include/wavenet_hip.h WN_ACCUM_*, ABI v15): SET acc = grad, ADD acc = acc + grad,

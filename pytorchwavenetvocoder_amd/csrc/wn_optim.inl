@@ -46,6 +46,20 @@ static unsigned wn_quad_blocks(long n, long cap) {
 //            pscale * p[i]: torch.optim.AdamW's decoupled decay, p *= 1 - lr wd, in front of an update whose gradient carries no
 //            decay term (such a group passes wd = 0).  An L2 group passes pscale = 1, which is exact: the arithmetic below is the
 //            one of SCALE = false, which no other kernel leaves.
+// the two moments from the values of one element (pv: the weight as the L2 term sees it); the layer-wise kernels (below) form
+// theirs with this very expression, so an adapted tensor's moments are the grouped launch's bit for bit
+template <bool GUARDED>
+static __device__ __forceinline__ void wn_adam_moments(float pv, float g, float m, float v, float coef, float beta1, float beta2,
+                                                       float wd, float* m_new, float* v_new) {
+    // never contracted into the decay term's fma: coef == 1 leaves the unguarded arithmetic
+    float gv = GUARDED ? wn_fmul_rn(coef, g) : g;
+    // gv += wd * pv;  m = beta1 * m + (1 - beta1) * gv;  v = beta2 * v + (1 - beta2) * gv * gv -- with the products hipcc has
+    // always fused here named, so that a kernel with another loop shape (16-byte quads) cannot fuse the other ones
+    if (wd != 0.0f) gv = wn_fma_contracted(wd, pv, gv);
+    *m_new = wn_fma_contracted(beta1, m, wn_fmul_rn(1.0f - beta1, gv));
+    *v_new = wn_fma_contracted(beta2, v, wn_fmul_rn(wn_fmul_rn(1.0f - beta2, gv), gv));
+}
+
 template <bool GUARDED, bool EMA, bool SCALE = false>
 static __device__ __forceinline__ void wn_adam_element(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, float* __restrict__ e, long i, float lr_over_bc1,
@@ -54,11 +68,8 @@ static __device__ __forceinline__ void wn_adam_element(float* __restrict__ p, co
     const float pv = SCALE ? wn_fmul_rn(pscale, p[i]) : p[i];
     float ev = 0.0f;
     if (EMA) ev = e[i];
-    // never contracted into the decay term's fma: coef == 1 leaves the unguarded arithmetic
-    float gv = GUARDED ? wn_fmul_rn(coef, g[i]) : g[i];
-    if (wd != 0.0f) gv += wd * pv;
-    const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
-    const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
+    float mv, vv;
+    wn_adam_moments<GUARDED>(pv, g[i], m[i], v[i], coef, beta1, beta2, wd, &mv, &vv);
     m[i] = mv;
     v[i] = vv;
     const float denom = sqrtf(vv) / sqrt_bc2 + eps;
@@ -556,6 +567,356 @@ int wn_grad_norm_finalize_groups(const double* partial, int nb, float max_norm, 
     for (int i = 0; i < n_groups; ++i) a.g[i] = groups[i];
     WN_LAUNCH(k_grad_norm_finalize_groups, dim3(1), dim3(WN_TPB), 0, st, partial, nb, max_norm, guard, a, n_groups, beta1, beta2, state,
               block);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Layer-wise adaptive steps (LAMB) and per-tensor sums of squares (ABI v20): ONE segmented reduction over the flat
+// buffers.  The tensor table (wn_tensor_table writes it, int64 words): the four rows of a group table -- lo[nr], hi[nr], before[nr],
+// group[nr], one range per TENSOR, never coalesced --, adapt[nr], block0[nr] = the index of the range's first block, one word for
+// the number of blocks, and range_of[blocks] = the range of every block.  Every tensor owns ceil(len / WN_TENSOR_CHUNK) blocks of
+// its own and block block0[r] + j walks elements [lo + j CHUNK, lo + (j + 1) CHUNK) of range r: a block lies inside ONE range,
+// which it reads from range_of (one load, then the range's five words side by side: a bisection of block0 is eleven DEPENDENT
+// loads at the recipe's size, and held the reduction at 1.8 TB/s), and needs neither the staged table nor the cursor of the
+// kernels above.  The grid is the bound n_live / CHUNK + nr the
+// launcher can form without reading the table (blocks behind the real count return at once), and every sum has a fixed order --
+// per thread front to back, the xor butterfly, the waves of a block in order, the blocks of a tensor in order --: ratios are a
+// function of the table, the buffers and their address modulo 16, never of the device.
+struct WnTensorChunk {
+    int r, group, adapt;
+    long lo, len;   // the block's elements: [lo, lo + len)
+};
+static __device__ __forceinline__ bool wn_tensor_chunk(const long* __restrict__ table, int nr, WnTensorChunk* c) {
+    const long b = blockIdx.x;
+    if (b >= table[6 * (long)nr]) return false;
+    const int a = (int)table[6 * (long)nr + 1 + b];
+    const long lo = table[a] + (b - table[5 * (long)nr + a]) * WN_TENSOR_CHUNK, left = table[nr + a] - lo;
+    c->r = a;
+    c->group = (int)table[3 * (long)nr + a] & (WN_MAX_PARAM_GROUPS - 1);
+    c->adapt = (int)table[4 * (long)nr + a];
+    c->lo = lo;
+    c->len = left < WN_TENSOR_CHUNK ? left : WN_TENSOR_CHUNK;
+    return true;
+}
+// wn_quad_edge for a walk every block does on its own chunk: threads 0..3 own the head, 4..7 the tail
+static __device__ __forceinline__ bool wn_chunk_edge(const WnQuadSplit& s, long n, long* i) {
+    if (threadIdx.x >= 8) return false;
+    const long t = threadIdx.x & 3;
+    *i = threadIdx.x < 4 ? t : s.head + 4 * s.n4 + t;
+    return *i < (threadIdx.x < 4 ? s.head : n);
+}
+// W = 4: one 16-byte access (the caller has checked the address), W = 1: one element
+template <int W>
+static __device__ __forceinline__ void wn_load(const float* a, long i, float (&x)[W]) {
+    if constexpr (W == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(a + i);
+        x[0] = q.x, x[1] = q.y, x[2] = q.z, x[3] = q.w;
+    } else {
+        x[0] = a[i];
+    }
+}
+template <int W>
+static __device__ __forceinline__ void wn_store(float* a, long i, const float (&x)[W]) {
+    if constexpr (W == 4) *reinterpret_cast<float4*>(a + i) = make_float4(x[0], x[1], x[2], x[3]);
+    else a[i] = x[0];
+}
+// thread 0 returns the block's sum: the waves in order
+static __device__ __forceinline__ double wn_block_sum_f64(double acc, double* red /*[WN_TPB >> 6]*/) {
+    acc = wn_wave_sum_f64(acc);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    double s = red[0];
+    for (int i = 1; i < (WN_TPB >> 6); ++i) s += red[i];
+    return s;
+}
+static __device__ __forceinline__ bool wn_same_mod16(const float* a, const float* b) {
+    return ((reinterpret_cast<uintptr_t>(a) ^ reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
+
+// what the step reads per launch: the unguarded call forms it on the host, the guarded kernels from the state block (bc1 and bc2
+// by wn_bias_correction from the device's count, as the finalize launch did)
+struct WnLambScalars {
+    double bc1;                                  // in double: a non-adapted tensor's lr / bc1 is wn_group_scalars' quotient
+    float bc1f, sqrt_bc2, coef, beta1, beta2, w;
+};
+template <bool GUARDED, bool EMA>
+static __device__ __forceinline__ WnLambScalars wn_lamb_scalars(WnLambScalars s, const WnOptState* __restrict__ state, double ema_decay,
+                                                                int ema_warmup) {
+    if (GUARDED) {
+        const WnBiasCorrection b = wn_bias_correction(state->beta1, state->beta2, state->steps_applied);
+        s.bc1 = b.bc1;
+        s.bc1f = (float)b.bc1;
+        s.sqrt_bc2 = (float)sqrt(b.bc2);
+        s.coef = state->clip_coef;
+        s.beta1 = state->beta1;
+        s.beta2 = state->beta2;
+        if (EMA) s.w = wn_ema_weight(ema_decay, ema_warmup, state->steps_applied);
+    }
+    return s;
+}
+// the update direction of an adapted element from its NEW moments and its weight before the step: passes 1 and 3 both call it
+static __device__ __forceinline__ float wn_lamb_update(float pv, float mv, float vv, float bc1f, float sqrt_bc2, float eps, float dwd) {
+    const float u = (mv / bc1f) / (sqrtf(vv) / sqrt_bc2 + eps);
+    return dwd != 0.0f ? fmaf(dwd, pv, u) : u;
+}
+
+// Pass 1.  Adapted range: the moments (wn_adam_moments: the grouped launch's bits), u, and the block's sums of p^2 and u^2 in
+// double -> partial[2 b], partial[2 b + 1]; 16-byte accesses when the four buffers share their address modulo 16.  A range that
+// does not adapt gets the whole grouped Adam element and is finished (its partials are neither written nor read).
+// One trip of a thread: units i, i + stride, ..., at most N of them (those with an index below `end`), W elements each.  The loads
+// of all N units are issued back to back before anything is computed (a unit beyond the end re-reads unit i and is dropped): a
+// block is short, and with one unit in flight per thread its life was a chain of memory round trips (profiles/lamb/NOTES.md).
+#define WN_TENSOR_BATCH 4
+template <bool GUARDED, int W, int N>
+static __device__ __forceinline__ void wn_lamb_moments_unit(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, long i, long stride, long end,
+                                                            const WnLambScalars& s, float eps, float l2, float dwd, double* sp,
+                                                            double* su) {
+    float pv[N][W], gv[N][W], mv[N][W], vv[N][W];
+    WN_UNROLL
+    for (int b = 0; b < N; ++b) {
+        const long ib = i + b * stride < end ? i + b * stride : i;
+        wn_load<W>(p, ib, pv[b]);
+        wn_load<W>(g, ib, gv[b]);
+        wn_load<W>(m, ib, mv[b]);
+        wn_load<W>(v, ib, vv[b]);
+    }
+    WN_UNROLL
+    for (int b = 0; b < N; ++b) {
+        if (i + b * stride >= end) break;
+        WN_UNROLL
+        for (int k = 0; k < W; ++k) {
+            wn_adam_moments<GUARDED>(pv[b][k], gv[b][k], mv[b][k], vv[b][k], s.coef, s.beta1, s.beta2, l2, &mv[b][k], &vv[b][k]);
+            const float u = wn_lamb_update(pv[b][k], mv[b][k], vv[b][k], s.bc1f, s.sqrt_bc2, eps, dwd);
+            *sp += (double)pv[b][k] * (double)pv[b][k];
+            *su += (double)u * (double)u;
+        }
+        wn_store<W>(m, i + b * stride, mv[b]);
+        wn_store<W>(v, i + b * stride, vv[b]);
+    }
+}
+
+template <bool GUARDED, bool EMA>
+__global__ __launch_bounds__(WN_TPB) void k_lamb_moments(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, float* __restrict__ e, const long* __restrict__ table,
+                                                         int nr, WnLambScalars s, WnAdamGroupArgs groups, WnGroupBlock host_block,
+                                                         const WnOptState* __restrict__ state, double ema_decay, int ema_warmup,
+                                                         double* __restrict__ partial) {
+    __shared__ double red_p[WN_TPB >> 6], red_u[WN_TPB >> 6];
+    if (GUARDED && !state->apply) return;
+    WnTensorChunk c;
+    if (!wn_tensor_chunk(table, nr, &c)) return;
+    s = wn_lamb_scalars<GUARDED, EMA>(s, state, ema_decay, ema_warmup);
+    const WnAdamGroup a = groups.g[c.group];
+    if (!c.adapt) {
+        const WnGroupScalars gs = GUARDED ? wn_group_scalars(a, s.bc1, true) : host_block.g[c.group];
+        for (long i = c.lo + threadIdx.x; i < c.lo + c.len; i += WN_TPB)
+            wn_adam_element<GUARDED, EMA, true>(p, g, m, v, e, i, gs.lr_over_bc1, s.sqrt_bc2, s.coef, s.beta1, s.beta2, gs.eps, gs.l2, s.w,
+                                                gs.scale);
+        return;
+    }
+    const float l2 = a.decoupled ? 0.0f : a.weight_decay, dwd = a.decoupled ? a.weight_decay : 0.0f;
+    double sp = 0.0, su = 0.0;
+    if (wn_same_mod16(p, g) && wn_same_mod16(p, m) && wn_same_mod16(p, v)) {
+        const WnQuadSplit qs = wn_quad_split(p + c.lo, c.len);
+        const long q0 = c.lo + qs.head, q1 = q0 + 4 * qs.n4;
+        for (long i = q0 + 4 * threadIdx.x; i < q1; i += WN_TENSOR_BATCH * 4 * WN_TPB)
+            wn_lamb_moments_unit<GUARDED, 4, WN_TENSOR_BATCH>(p, g, m, v, i, 4 * WN_TPB, q1, s, a.eps, l2, dwd, &sp, &su);
+        long i;
+        if (wn_chunk_edge(qs, c.len, &i)) wn_lamb_moments_unit<GUARDED, 1, 1>(p, g, m, v, c.lo + i, 0, c.lo + c.len, s, a.eps, l2, dwd, &sp, &su);
+    } else {
+        const long end = c.lo + c.len;
+        for (long i = c.lo + threadIdx.x; i < end; i += WN_TENSOR_BATCH * WN_TPB)
+            wn_lamb_moments_unit<GUARDED, 1, WN_TENSOR_BATCH>(p, g, m, v, i, WN_TPB, end, s, a.eps, l2, dwd, &sp, &su);
+    }
+    sp = wn_block_sum_f64(sp, red_p);
+    su = wn_block_sum_f64(su, red_u);
+    if (threadIdx.x == 0) {
+        partial[2 * (long)blockIdx.x] = sp;
+        partial[2 * (long)blockIdx.x + 1] = su;
+    }
+}
+
+// Pass 2: one thread per tensor adds its blocks' partials in block order and writes ||w||, ||u|| and the trust ratio (three
+// floats per tensor).  ||w|| == 0 or ||u|| == 0: ratio 1; a non-finite norm (guard off) stays in the ratio.  max_trust > 0 clamps.
+__global__ __launch_bounds__(WN_TPB) void k_lamb_ratios(const double* __restrict__ partial, const long* __restrict__ table, int nr,
+                                                        float max_trust, const WnOptState* __restrict__ state,
+                                                        float* __restrict__ stats) {
+    if (state && !state->apply) return;
+    const int r = blockIdx.x * WN_TPB + threadIdx.x;
+    if (r >= nr) return;
+    float wn = 0.0f, un = 0.0f, ratio = 1.0f;
+    if (table[4 * (long)nr + r]) {
+        const long b0 = table[5 * (long)nr + r], b1 = r + 1 < nr ? table[5 * (long)nr + r + 1] : table[6 * (long)nr];
+        double sp = 0.0, su = 0.0;
+        for (long b = b0; b < b1; ++b) {
+            sp += partial[2 * b];
+            su += partial[2 * b + 1];
+        }
+        const double w2 = sqrt(sp), u2 = sqrt(su);
+        wn = (float)w2;
+        un = (float)u2;
+        if (!(w2 == 0.0) && !(u2 == 0.0)) ratio = (float)(w2 / u2);
+        if (max_trust > 0.0f && ratio > max_trust) ratio = max_trust;
+    }
+    stats[3 * (long)r] = wn;
+    stats[3 * (long)r + 1] = un;
+    stats[3 * (long)r + 2] = ratio;
+}
+
+// Pass 3, adapted ranges only: u again from the stored moments and the weight (wn_lamb_update, as pass 1), p -= (lr_g r) u and
+// the moving average.  No n-sized temporary: 10 words per element over the two passes.
+template <bool EMA, int W, int N>
+static __device__ __forceinline__ void wn_lamb_apply_unit(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
+                                                          float* __restrict__ e, long i, long stride, long end, const WnLambScalars& s,
+                                                          float eps, float dwd, float step) {
+    float pv[N][W], mv[N][W], vv[N][W], ev[N][W];
+    WN_UNROLL
+    for (int b = 0; b < N; ++b) {
+        const long ib = i + b * stride < end ? i + b * stride : i;
+        wn_load<W>(p, ib, pv[b]);
+        wn_load<W>(m, ib, mv[b]);
+        wn_load<W>(v, ib, vv[b]);
+        if (EMA) wn_load<W>(e, ib, ev[b]);
+    }
+    WN_UNROLL
+    for (int b = 0; b < N; ++b) {
+        if (i + b * stride >= end) break;
+        WN_UNROLL
+        for (int k = 0; k < W; ++k) {
+            const float u = wn_lamb_update(pv[b][k], mv[b][k], vv[b][k], s.bc1f, s.sqrt_bc2, eps, dwd);
+            pv[b][k] = fmaf(-step, u, pv[b][k]);
+            if (EMA) ev[b][k] = fmaf(s.w, pv[b][k] - ev[b][k], ev[b][k]);
+        }
+        wn_store<W>(p, i + b * stride, pv[b]);
+        if (EMA) wn_store<W>(e, i + b * stride, ev[b]);
+    }
+}
+
+template <bool GUARDED, bool EMA>
+__global__ __launch_bounds__(WN_TPB) void k_lamb_apply(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
+                                                       float* __restrict__ e, const long* __restrict__ table, int nr, WnLambScalars s,
+                                                       WnAdamGroupArgs groups, const WnOptState* __restrict__ state, double ema_decay,
+                                                       int ema_warmup, const float* __restrict__ stats) {
+    if (GUARDED && !state->apply) return;
+    WnTensorChunk c;
+    if (!wn_tensor_chunk(table, nr, &c) || !c.adapt) return;
+    s = wn_lamb_scalars<GUARDED, EMA>(s, state, ema_decay, ema_warmup);
+    const WnAdamGroup a = groups.g[c.group];
+    const float dwd = a.decoupled ? a.weight_decay : 0.0f;
+    const float step = wn_fmul_rn(a.lr, stats[3 * (long)c.r + 2]);
+    if (wn_same_mod16(p, m) && wn_same_mod16(p, v) && (!EMA || wn_same_mod16(p, e))) {
+        const WnQuadSplit qs = wn_quad_split(p + c.lo, c.len);
+        const long q0 = c.lo + qs.head, q1 = q0 + 4 * qs.n4;
+        for (long i = q0 + 4 * threadIdx.x; i < q1; i += WN_TENSOR_BATCH * 4 * WN_TPB)
+            wn_lamb_apply_unit<EMA, 4, WN_TENSOR_BATCH>(p, m, v, e, i, 4 * WN_TPB, q1, s, a.eps, dwd, step);
+        long i;
+        if (wn_chunk_edge(qs, c.len, &i)) wn_lamb_apply_unit<EMA, 1, 1>(p, m, v, e, c.lo + i, 0, c.lo + c.len, s, a.eps, dwd, step);
+    } else {
+        const long end = c.lo + c.len;
+        for (long i = c.lo + threadIdx.x; i < end; i += WN_TENSOR_BATCH * WN_TPB)
+            wn_lamb_apply_unit<EMA, 1, WN_TENSOR_BATCH>(p, m, v, e, i, WN_TPB, end, s, a.eps, dwd, step);
+    }
+}
+
+static unsigned wn_tensor_grid(int nr, long n_live) { return (unsigned)(n_live / WN_TENSOR_CHUNK + nr); }
+
+template <bool GUARDED, bool EMA>
+static void wn_lamb_launch(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live,
+                           const WnLambScalars& s, const WnAdamGroupArgs& groups, const WnGroupBlock& block, float max_trust,
+                           const WnOptState* state, double ema_decay, int ema_warmup, double* partial, float* stats, wn_stream_t st) {
+    const dim3 grid(wn_tensor_grid(nr, n_live));
+    auto moments = k_lamb_moments<GUARDED, EMA>;
+    auto apply = k_lamb_apply<GUARDED, EMA>;
+    {
+        WN_PROF("lamb_moments", 0.0, 24.0 * (double)n_live, st);
+        WN_LAUNCH(moments, grid, dim3(WN_TPB), 0, st, p, g, m, v, e, table, nr, s, groups, block, state, ema_decay, ema_warmup, partial);
+    }
+    {
+        WN_PROF("lamb_ratios", 0.0, 16.0 * (double)grid.x, st);
+        WN_LAUNCH(k_lamb_ratios, dim3((unsigned)((nr + WN_TPB - 1) / WN_TPB)), dim3(WN_TPB), 0, st, partial, table, nr, max_trust, state,
+                  stats);
+    }
+    {
+        WN_PROF("lamb_apply", 0.0, (EMA ? 24.0 : 16.0) * (double)n_live, st);
+        WN_LAUNCH(apply, grid, dim3(WN_TPB), 0, st, p, m, v, e, table, nr, s, groups, state, ema_decay, ema_warmup, stats);
+    }
+}
+
+int wn_lamb(float* p, const float* g, float* m, float* v, float* e, const long* table, int nr, long n_live, long step,
+            const WnAdamGroup* groups, int n_groups, float beta1, float beta2, float max_trust, const WnOptState* state,
+            double ema_decay, int ema_warmup, double* partial, float* stats, wn_stream_t st) {
+    WnAdamGroupArgs a = {};
+    WnGroupBlock block = {};
+    WnLambScalars s = {};
+    s.coef = 1.0f;
+    if (!state) {
+        const WnBiasCorrection b = wn_bias_correction(beta1, beta2, step);
+        s.bc1 = b.bc1;
+        s.bc1f = (float)b.bc1;
+        s.sqrt_bc2 = (float)sqrt(b.bc2);
+        s.beta1 = beta1;
+        s.beta2 = beta2;
+        if (e) s.w = wn_ema_weight(ema_decay, ema_warmup, step);
+    }
+    for (int i = 0; i < n_groups; ++i) {
+        a.g[i] = groups[i];
+        if (!state) block.g[i] = wn_group_scalars(groups[i], s.bc1, true);
+    }
+    if (state) {
+        if (e) wn_lamb_launch<true, true>(p, g, m, v, e, table, nr, n_live, s, a, block, max_trust, state, ema_decay, ema_warmup, partial, stats, st);
+        else wn_lamb_launch<true, false>(p, g, m, v, e, table, nr, n_live, s, a, block, max_trust, state, ema_decay, ema_warmup, partial, stats, st);
+    } else {
+        if (e) wn_lamb_launch<false, true>(p, g, m, v, e, table, nr, n_live, s, a, block, max_trust, state, ema_decay, ema_warmup, partial, stats, st);
+        else wn_lamb_launch<false, false>(p, g, m, v, e, table, nr, n_live, s, a, block, max_trust, state, ema_decay, ema_warmup, partial, stats, st);
+    }
+    return 0;
+}
+
+// The same segmented reduction for any flat fp32 buffer: out[r] = the sum of x[i]^2 over range r, in double.
+__global__ __launch_bounds__(WN_TPB) void k_tensor_sumsq(const float* __restrict__ x, const long* __restrict__ table, int nr,
+                                                         double* __restrict__ partial) {
+    __shared__ double red[WN_TPB >> 6];
+    WnTensorChunk c;
+    if (!wn_tensor_chunk(table, nr, &c)) return;
+    double acc = 0.0;
+    const WnQuadSplit qs = wn_quad_split(x + c.lo, c.len);
+    const long q0 = c.lo + qs.head, q1 = q0 + 4 * qs.n4;
+    for (long j = q0 + 4 * threadIdx.x; j < q1; j += WN_TENSOR_BATCH * 4 * WN_TPB) {
+        float q[WN_TENSOR_BATCH][4];
+        WN_UNROLL
+        for (int b = 0; b < WN_TENSOR_BATCH; ++b) wn_load<4>(x, j + b * 4 * WN_TPB < q1 ? j + b * 4 * WN_TPB : j, q[b]);
+        WN_UNROLL
+        for (int b = 0; b < WN_TENSOR_BATCH; ++b) {
+            if (j + b * 4 * WN_TPB >= q1) break;
+            WN_UNROLL
+            for (int k = 0; k < 4; ++k) acc += (double)q[b][k] * (double)q[b][k];
+        }
+    }
+    long i;
+    if (wn_chunk_edge(qs, c.len, &i)) acc += (double)x[c.lo + i] * (double)x[c.lo + i];
+    acc = wn_block_sum_f64(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(WN_TPB) void k_tensor_sums(const double* __restrict__ partial, const long* __restrict__ table, int nr,
+                                                        double* __restrict__ out) {
+    const int r = blockIdx.x * WN_TPB + threadIdx.x;
+    if (r >= nr) return;
+    const long b0 = table[5 * (long)nr + r], b1 = r + 1 < nr ? table[5 * (long)nr + r + 1] : table[6 * (long)nr];
+    double s = 0.0;
+    for (long b = b0; b < b1; ++b) s += partial[b];
+    out[r] = s;
+}
+
+int wn_tensor_sumsq_launch(const float* x, const long* table, int nr, long n_live, double* partial, double* out, wn_stream_t st) {
+    {
+        WN_PROF("tensor_sumsq", 2.0 * (double)n_live, 4.0 * (double)n_live, st);
+        WN_LAUNCH(k_tensor_sumsq, dim3(wn_tensor_grid(nr, n_live)), dim3(WN_TPB), 0, st, x, table, nr, partial);
+    }
+    WN_PROF("tensor_sums", 0.0, 8.0 * (double)nr, st);
+    WN_LAUNCH(k_tensor_sums, dim3((unsigned)((nr + WN_TPB - 1) / WN_TPB)), dim3(WN_TPB), 0, st, partial, table, nr, out);
     return 0;
 }
 

@@ -85,6 +85,18 @@ class GroupTable(LiveTable):
         self.groups, self.n_groups = groups, int(n_groups)
 
 
+class TensorTable(GroupTable):
+    """A ``GroupTable`` with ONE range per tensor (never coalesced) for ``lamb_step`` and ``tensor_norms`` (include/wavenet_hip.h,
+    ABI v20): ``adapt`` one flag per range, ``n_blocks`` the blocks the ranges own (``ceil(len / _lib.TENSOR_CHUNK)`` each),
+    ``scratch`` the per-block partial sums the calls write.  ``table`` holds the rows of a ``GroupTable`` first, so the
+    ``*_live`` and ``*_groups`` norm calls read it as it is.  Built by ``WaveNetEngine.tensor_table``."""
+    __slots__ = ("adapt", "n_blocks", "scratch")
+
+    def __init__(self, ranges, groups, n_groups, n_live, n, table, adapt, n_blocks, scratch):
+        GroupTable.__init__(self, ranges, groups, n_groups, n_live, n, table)
+        self.adapt, self.n_blocks, self.scratch = adapt, int(n_blocks), scratch
+
+
 def group_array(groups):
     """Host array of ``WnAdamGroup`` from ``(lr, eps, weight_decay, decoupled)`` tuples: what the ``*_groups`` calls take (the values
     travel in the launch arguments)."""
@@ -1023,6 +1035,66 @@ class WaveNetEngine(object):
                                                   float(ema_decay), int(bool(ema_warmup)), _stream_handle(self.device))
         self.lib.check(rc, "wn_adam_step_guarded_groups")
         self._params_epoch += 1
+
+    # ---- layer-wise adaptive steps and per-tensor norms (include/wavenet_hip.h, ABI v20) ------------
+    def tensor_table(self, quads, n_groups=1, n=None, device=None):
+        """``TensorTable`` of ``(lo, hi, group, adapt)`` quadruples, ONE range per tensor (``wn_tensor_table`` checks them as
+        ``wn_group_table`` does, and the adapt flags).  It carries the scratch of the calls that walk it.  One small
+        host-to-device copy: build it once per set of live tensors, not per step."""
+        n = self.n_params if n is None else int(n)
+        quads = [(int(a), int(b), int(c), int(d)) for a, b, c, d in quads]
+        nr = len(quads)
+        flat = (ctypes.c_int64 * max(4 * nr, 1))(*[x for q in quads for x in q])
+        host = torch.zeros(7 * nr + 1 + n // _lib.TENSOR_CHUNK, dtype=torch.int64)
+        n_live = self.lib.wn_tensor_table(ctypes.cast(flat, ctypes.c_void_p), nr, n, int(n_groups), ctypes.c_void_p(host.data_ptr()))
+        if n_live < 0:
+            raise _lib.WnError("wn_tensor_table failed: %s" % self.lib.wn_last_error().decode())
+        n_blocks = int(self.lib.wn_tensor_blocks(ctypes.c_void_p(host.data_ptr()), nr))
+        host = host[:6 * nr + 1 + n_blocks]
+        device = self.device if device is None else device
+        scratch = torch.empty(int(self.lib.wn_lamb_scratch_floats(n_blocks)), dtype=torch.float32, device=device)
+        return TensorTable([(a, b) for a, b, _, _ in quads], [c for _, _, c, _ in quads], n_groups, n_live, n, host.to(device),
+                           [bool(d) for _, _, _, d in quads], n_blocks, scratch)
+
+    def _tensor_args(self, table):
+        if not isinstance(table, TensorTable):
+            raise TypeError("this call takes a TensorTable (WaveNetEngine.tensor_table)")
+        self._check_device(table.table, table.scratch)
+        return _ptr(table.table), table.n_ranges, table.n_live
+
+    def lamb_step(self, exp_avg, exp_avg_sq, ema, table, stats, groups, step=0, state=None, betas=(0.9, 0.999), max_trust_ratio=None,
+                  ema_decay=0.0, ema_warmup=False):
+        """One layer-wise adaptive step over the tensors of ``table`` (a ``TensorTable``), each with the
+        ``(lr, eps, weight_decay, decoupled)`` of its group: three launches (``wn_lamb_step``).  ``state`` None: unguarded, with
+        the host's ``step``; otherwise the state block as the preceding ``grad_norm*`` call left it.  ``stats``: ``3 * n_ranges``
+        floats on the device, per tensor the weight norm, the update norm and the trust ratio."""
+        self._check_device(exp_avg, exp_avg_sq, ema, stats, state)
+        if table.n != self.n_params:
+            raise ValueError("the tensor table was built for a buffer of %d elements, the flat buffers hold %d" % (table.n, self.n_params))
+        tab, nr, n_live = self._tensor_args(table)
+        if stats.dtype != torch.float32 or stats.numel() < 3 * nr:
+            raise ValueError("stats takes 3 * n_ranges floats")
+        arr, ng = self._group_args(table, groups)
+        rc = self.lib.wn_lamb_step(_ptr(self.flat_params), _ptr(self.grads()), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(ema), self.n_params,
+                                   tab, nr, n_live, int(step), ctypes.cast(arr, ctypes.c_void_p), ng, float(betas[0]), float(betas[1]),
+                                   float(max_trust_ratio) if max_trust_ratio else 0.0, _ptr(state), float(ema_decay),
+                                   int(bool(ema_warmup)), _ptr(table.scratch), _ptr(stats), _stream_handle(self.device))
+        self.lib.check(rc, "wn_lamb_step")
+        self._params_epoch += 1
+
+    def tensor_norms(self, buf, table, out=None):
+        """Per-tensor L2 norms of the flat fp32 buffer ``buf`` over the ranges of ``table`` (a ``TensorTable`` built for
+        ``buf.numel()`` elements): a float64 device tensor of ``n_ranges`` elements, two launches and one ``sqrt``, whatever the
+        number of tensors.  ``out``: a float64 tensor to take the sums of squares (it is returned square-rooted in place)."""
+        tab, nr, n_live = self._tensor_args(table)
+        self._check_device(buf)
+        if buf.dtype != torch.float32 or not buf.is_contiguous() or buf.numel() != table.n:
+            raise ValueError("tensor_norms takes a contiguous fp32 buffer of the %d elements the table was built for" % table.n)
+        out = torch.empty(nr, dtype=torch.float64, device=buf.device) if out is None else out
+        rc = self.lib.wn_tensor_sumsq(_ptr(buf), buf.numel(), tab, nr, n_live, _ptr(table.scratch), _ptr(out),
+                                      _stream_handle(self.device))
+        self.lib.check(rc, "wn_tensor_sumsq")
+        return out.sqrt_()
 
     def swap_params(self, other):
         """Exchange the flat parameter buffer with ``other`` (same length, same device) element by element: one launch, no

@@ -59,6 +59,19 @@ torch does -- consecutively over the groups in order, model order inside a group
 ``torch.optim.Adam`` built with the same groups, and back; a different group structure raises ValueError.  ``add_param_group``
 after construction raises: a group is a set of ranges of the flat buffer, fixed with the optimizer.
 
+Layer-wise adaptive steps (LAMB): ``layer_adaptation=True`` scales every adapted tensor's step by its trust ratio
+``r = ||w|| / ||u||`` (``u`` the bias-corrected Adam direction, plus ``wd w`` in a decoupled group; ``r = 1`` when either norm is
+zero; ``max_trust_ratio`` clamps it): ``w -= lr r u``.  Tensors with two or more dimensions adapt, one-dimensional ones (every bias:
+``initialize()`` zeroes them, and an adapted bias would get ``r = 1`` once and then steps proportional to its own tiny norm) take
+the plain Adam update; a group's ``"layer_adaptation": True | False`` overrides that for its tensors.  The moments are Adam's bit
+for bit, so ``state_dict()`` keeps torch.optim.Adam's format and a run may switch between the two on resume.  The step is three
+launches (``lamb_moments``, ``lamb_ratios``, ``lamb_apply``) behind the two of the norm on the guarded path, over a table with one
+range per live tensor, rebuilt once when the trainable set changes.  ``opt.trust_ratios``, ``opt.weight_norms`` and
+``opt.update_norms`` are device tensors in the order of ``opt.tensor_names`` (``named_parameters()`` order), valid after ``step()``
+without synchronisation; a step the guard skipped leaves them.  WITHOUT the guard a non-finite gradient poisons every weight of
+its tensor through the ratio (plain Adam poisons one element).  ``opt.grad_norms()`` gives the per-tensor gradient norms (two
+launches for all tensors) with or without layer adaptation.
+
 With all of these at their defaults ``step()`` is the one ``adam`` launch with the host's step count, bit for bit as before.
 ``state_dict()`` never holds the average: it stays in torch.optim.Adam's format.
 """
@@ -70,7 +83,7 @@ import torch
 from . import _lib
 
 
-GROUP_KEYS = ("lr", "weight_decay", "eps", "decoupled_weight_decay")
+GROUP_KEYS = ("lr", "weight_decay", "eps", "decoupled_weight_decay", "layer_adaptation")
 
 
 def assign_groups(names, groups):
@@ -92,6 +105,8 @@ def assign_groups(names, groups):
                 raise ValueError("group %r: betas are per optimizer, not per group (one step count and one bias correction)" % (pattern,))
             if k not in GROUP_KEYS:
                 raise ValueError("group %r: unknown key %r (a group sets %s)" % (pattern, k, ", ".join(GROUP_KEYS)))
+            if k == "layer_adaptation" and not isinstance(values[k], bool):
+                raise ValueError("group %r: layer_adaptation takes True or False, got %r" % (pattern, values[k]))
         rx = re.compile(pattern)
         if not any(rx.search(k) for k in names):
             raise ValueError("group pattern %r matches no parameter of the model (keys look like %r)" % (pattern, names[0]))
@@ -101,13 +116,23 @@ def assign_groups(names, groups):
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
-                 skip_nonfinite=False, ema_decay=None, ema_warmup=True, groups=None):
+                 skip_nonfinite=False, ema_decay=None, ema_warmup=True, groups=None, layer_adaptation=False, max_trust_ratio=None):
         if not hasattr(model, "engine"):
             raise TypeError("FusedAdam takes the WaveNet model (it updates the model's flat buffer)")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                         maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
         self.model = model
         named = list(model.named_parameters())
+        self.layer_adaptation = bool(layer_adaptation)
+        if max_trust_ratio is not None and not float(max_trust_ratio) > 0.0:
+            raise ValueError("max_trust_ratio must be positive (None = no clamp)")
+        self.max_trust_ratio = None if max_trust_ratio is None else float(max_trust_ratio)
+        if not self.layer_adaptation:
+            if self.max_trust_ratio is not None:
+                raise ValueError("max_trust_ratio needs layer_adaptation=True")
+            if any("layer_adaptation" in dict(values) for _, values in (groups or ()) if isinstance(values, dict)):
+                raise ValueError("a group sets layer_adaptation, the optimizer was built with layer_adaptation=False")
+        self._lamb = (None, None)   # (TrainableSet, its tensor-table route): rebuilt when the set changes
         self._built = False
         if groups is None:
             self._group_of = [0] * len(named)
@@ -170,6 +195,113 @@ class FusedAdam(torch.optim.Optimizer):
                     triples.append((lo, hi, g))
             self._route = (ts, self._route[1], self.model.engine.group_table(triples, len(self.param_groups)))
         return self._route[2]
+
+    # ---- per-tensor tables: layer-wise adaptive steps and grad_norms() -----------------------------
+    def _tensor_route(self, ts):
+        """What the per-tensor calls need for a trainable set, built at its first use and once per set: the ``TensorTable`` with
+        one range per live tensor (buffer order), the statistics buffer, and the names of those tensors in
+        ``named_parameters()`` order with the device permutation that brings table order into it (None: they agree)."""
+        if self._lamb[0] is not ts:
+            eng = self.model.engine
+            rows = []
+            for idx, ((name, _), g, on, (off, n, shape, dead)) in enumerate(zip(self.model.named_parameters(), self._group_of, ts.mask,
+                                                                               self.model._param_slices)):
+                if on and not dead and n > 0:
+                    adapt = self.param_groups[g].get("layer_adaptation")
+                    rows.append((off, off + n, g, int(len(shape) >= 2 if adapt is None else adapt), idx, name))
+            order = sorted(range(len(rows)), key=lambda i: rows[i][0])                 # table row -> position in model order
+            table = eng.tensor_table([rows[i][:4] for i in order], len(self.param_groups))
+            row_of = {i: r for r, i in enumerate(order)}
+            perm = [row_of[i] for i in range(len(rows))]
+            perm_dev = None if perm == list(range(len(rows))) else torch.tensor(perm, dtype=torch.int64, device=eng.flat_params.device)
+            stats = torch.zeros(len(rows), 3, dtype=torch.float32, device=eng.flat_params.device)
+            stats[:, 2] = 1.0
+            self._lamb = (ts, dict(table=table, stats=stats, names=[r[5] for r in rows], adapts=[bool(r[3]) for r in rows], perm=perm_dev,
+                                   sumsq=torch.zeros(len(rows), dtype=torch.float64, device=eng.flat_params.device)))
+        return self._lamb[1]
+
+    def _stat(self, col):
+        if not self.layer_adaptation:
+            raise RuntimeError("this optimizer takes plain Adam steps (layer_adaptation=False)")
+        route = self._lamb[1]
+        if route is None:
+            raise RuntimeError("no step() yet: the per-tensor statistics belong to the tensors of the last step")
+        view = route["stats"][:, col]
+        return view if route["perm"] is None else view[route["perm"]]
+
+    @property
+    def tensor_names(self):
+        """``named_parameters()`` keys of the tensors the per-tensor statistics speak of (the live, non-dead ones of the last
+        ``step()`` or ``grad_norms()``), in their order."""
+        return None if self._lamb[1] is None else list(self._lamb[1]["names"])
+
+    @property
+    def tensor_adapts(self):
+        """One flag per entry of ``tensor_names``: the tensor's step is scaled by its trust ratio (always False without
+        ``layer_adaptation``)."""
+        if self._lamb[1] is None:
+            return None
+        return [a and self.layer_adaptation for a in self._lamb[1]["adapts"]]
+
+    @property
+    def weight_norms(self):
+        """Per tensor ``||w||`` before the last applied step (0 for a tensor that does not adapt)."""
+        return self._stat(0)
+
+    @property
+    def update_norms(self):
+        """Per tensor ``||u||`` of the last applied step (0 for a tensor that does not adapt)."""
+        return self._stat(1)
+
+    @property
+    def trust_ratios(self):
+        """Per tensor the trust ratio of the last applied step (1 for a tensor that does not adapt)."""
+        return self._stat(2)
+
+    @torch.no_grad()
+    def grad_norms(self):
+        """Per-tensor L2 norms of the gradient ``step()`` would read now, a float64 device tensor in the order of
+        ``tensor_names``: two launches for all tensors and no synchronisation."""
+        ts = self.model.trainable(self._gather_grads())
+        if ts.empty:
+            return torch.zeros(0, dtype=torch.float64, device=self.model.engine.flat_params.device)
+        route = self._tensor_route(ts)
+        norms = self.model.engine.tensor_norms(self.model.engine.grads(), route["table"], out=route["sumsq"])
+        return norms.clone() if route["perm"] is None else norms[route["perm"]]
+
+    def _gather_grads(self):
+        """Bring gradients the autograd path left in tensors of their own into the flat gradient buffer; one flag per parameter:
+        it has a gradient (a parameter without one -- frozen, or dropped by the caller -- is left alone, as torch.optim.Adam does)."""
+        flat_g = self.model.engine.grads()
+        lo = flat_g.data_ptr()
+        hi = lo + flat_g.numel() * 4
+        has_grad = []
+        for p, (off, n, shape, dead) in zip(self.model.parameters(), self.model._param_slices):
+            has_grad.append(p.grad is not None)
+            if p.grad is not None and not (lo <= p.grad.data_ptr() < hi):
+                flat_g[off:off + n].copy_(p.grad.reshape(-1))
+        return has_grad
+
+    def _step_lamb(self, ts, m, v, ema):
+        """The layer-wise adaptive step: the norm's two launches on the guarded path, then the three of
+        ``lamb_step`` over the set's tensor table with the values of every group as ``param_groups`` holds them NOW."""
+        eng = self.model.engine
+        route = self._tensor_route(ts)
+        table = route["table"]
+        values = [(g["lr"], g["eps"], g["weight_decay"], g.get("decoupled_weight_decay", False)) for g in self.param_groups]
+        betas = self.param_groups[0]["betas"]
+        decay = 0.0 if ema is None else self.ema_decay
+        state = None
+        if self.guarded:
+            state, scratch = self._guard_buffers()
+            if self._group_scalars is None or self._group_scalars.device != eng.flat_params.device:
+                self._group_scalars = eng.new_group_scalars()
+            eng.grad_norm_groups(state, scratch, self._group_scalars, table, values, self.max_grad_norm, self.skip_nonfinite, betas,
+                                 whole=ts.full)
+        else:
+            self._step += 1
+        eng.lamb_step(m, v, ema, table, route["stats"], values, step=self._step, state=state, betas=betas,
+                      max_trust_ratio=self.max_trust_ratio, ema_decay=decay, ema_warmup=self.ema_warmup)
 
     def _guard_buffers(self):
         eng = self.model.engine
@@ -287,15 +419,8 @@ class FusedAdam(torch.optim.Optimizer):
         eng = self.model.engine
         m, v = self._buffers()
         ema = self.ema
-        flat_g = eng.grads()
         # gradients produced by the autograd path live in separate tensors: gather them
-        lo = flat_g.data_ptr()
-        hi = lo + flat_g.numel() * 4
-        has_grad = []   # a parameter without a gradient -- frozen, or dropped by the caller -- is left alone, as torch.optim.Adam does
-        for p, (off, n, shape, dead) in zip(self.model.parameters(), self.model._param_slices):
-            has_grad.append(p.grad is not None)
-            if p.grad is not None and not (lo <= p.grad.data_ptr() < hi):
-                flat_g[off:off + n].copy_(p.grad.reshape(-1))
+        has_grad = self._gather_grads()
         # every live parameter has one: today's launches over the whole buffer.  Otherwise the same kernels' arithmetic over the
         # live ranges only: what the gradient buffer holds elsewhere is never read, and weights, moments and the
         # average keep their bits there (no weight decay either).
@@ -310,6 +435,9 @@ class FusedAdam(torch.optim.Optimizer):
             self._fold_trained()
             self._set_applied0 = self._step if self._last_set is None else self.steps_applied()
             self._last_set = ts
+        if self.layer_adaptation:
+            self._step_lamb(ts, m, v, ema)
+            return loss
         live_groups, _ = self._group_route(ts)
         group = self.param_groups[live_groups[0]]
         if len(live_groups) > 1 or group.get("decoupled_weight_decay", False):
@@ -410,6 +538,6 @@ class FusedAdam(torch.optim.Optimizer):
         if self.guarded:
             self._guard_buffers()[0][3] = step
         for g, sg in zip(self.param_groups, sd["param_groups"]):
-            for k in ("lr", "betas", "eps", "weight_decay") + (("decoupled_weight_decay",) if "decoupled_weight_decay" in g else ()):
+            for k in ("lr", "betas", "eps", "weight_decay") + tuple(k for k in ("decoupled_weight_decay", "layer_adaptation") if k in g):
                 if k in sg:
                     g[k] = tuple(sg[k]) if k == "betas" else sg[k]
