@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 20
+#define WN_ABI_VERSION 21
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -810,6 +810,31 @@ int wn_decode_layered_steps(const WnConfig* cfg, int B, const float* params, con
  * written to wave_out (B, Ttot) (nullable) and, mu-law encoded with n_quantize levels, to samples.  log_scale_min
  * (since ABI v4; ignored by modes 0/1) is the clamp of the log-scales -- pass the value the model was trained with
  * (wn_mol_loss's log_scale_min) so that sampling and the likelihood agree. */
+
+/* Since ABI v21: temperature, top-k and nucleus (top-p) sampling -- the setting of one decode call, applied to mode 1 (sampling
+ * on the softmax head) inside the decode kernels (csrc/wn_sample.h; up to 512 classes), in this order:
+ *   1. s_q = fp32(logit_q * inv_temperature)      inv_temperature = (float)(1.0 / T), formed by the caller in double
+ *   2. top_k > 0: v_k = the k-th largest s counted with multiplicity, A = {q : s_q >= v_k} (ties at v_k are all kept);
+ *      top_k == 0 or >= the number of classes: off
+ *   3. top_p < 1: with e_q = expf(s_q - s_max), tau = the largest v among {s_q : q in A} for which
+ *      sum_{q in A, s_q >= v} e_q >= top_p * sum_{q in A} e_q, B = {q in A : s_q >= tau} (ties kept; the maximal class is in B)
+ *   4. the draw of mode 1 restricted to B: in index order the first q in B whose running sum of e_q reaches u * total.
+ * logits_out keeps receiving the raw logits.  The *_filtered calls take the arguments of their plain counterparts plus the
+ * setting: NULL or the identity {1, 0, 1} IS the plain call (same launches, same tokens); a setting that is not the identity
+ * together with mode 0 or 2 is an error, so is inv_temperature <= 0 or non-finite, top_k < 0, top_p outside (0, 1]. */
+typedef struct WnSampling {
+    float inv_temperature;
+    int32_t top_k;
+    float top_p;
+} WnSampling;
+int wn_decode_steps_filtered(const WnConfig* cfg, int B, const float* params, const float* wpack, const float* G, int F, int n_pad,
+                             int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end, int p0, int p1,
+                             float* state, const float* uniforms, float* logits_out, int mode, float* wave_out,
+                             float log_scale_min, const WnSampling* sampling, void* stream);
+int wn_decode_layered_steps_filtered(const WnConfig* cfg, int B, const float* params, const float* G, int F, int n_pad,
+                                     int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end, int p0,
+                                     int p1, float* state, int64_t state_floats, const float* uniforms, float* logits_out,
+                                     int mode, float* wave_out, float log_scale_min, const WnSampling* sampling, void* stream);
 
 /* Parallel context walk.  The reference builds the generation buffers with ONE full forward over the padded
  * context (wavenet.py:338-349, 427-441); stepping the decode kernel through those >= receptive-field positions

@@ -72,6 +72,12 @@ MAX_PARAM_GROUPS = 16   # WN_MAX_PARAM_GROUPS
 TENSOR_CHUNK = 8192     # WN_TENSOR_CHUNK: elements per block of a tensor table (ABI v20)
 
 
+class WnSampling(ctypes.Structure):
+    """Mirror of ``struct WnSampling`` (include/wavenet_hip.h, ABI v21): temperature (as its inverse), top-k (0: off) and top-p
+    (1: off) of one sampling decode."""
+    _fields_ = [("inv_temperature", ctypes.c_float), ("top_k", ctypes.c_int32), ("top_p", ctypes.c_float)]
+
+
 class WnAdamGroup(ctypes.Structure):
     """Mirror of ``struct WnAdamGroup`` (include/wavenet_hip.h, ABI v17): the four values of a parameter group."""
     _fields_ = [("lr", ctypes.c_float), ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float), ("decoupled", ctypes.c_int32)]
@@ -139,7 +145,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -160,6 +166,7 @@ EXPORTS = [
     "wn_softmax_distill_scratch_floats", "wn_softmax_distill_loss",
     "wn_softmax_cew_scratch_floats", "wn_softmax_cew_loss",
     "wn_tensor_table", "wn_tensor_blocks", "wn_lamb_scratch_floats", "wn_tensor_sumsq", "wn_lamb_step",
+    "wn_decode_steps_filtered", "wn_decode_layered_steps_filtered",
 ]
 
 
@@ -288,6 +295,11 @@ class WnLibrary(object):
         L.wn_decode_layered_residency.argtypes = [cfgp, i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
         L.wn_decode_layered_prepare.argtypes = [cfgp, i, i, vp, vp, vp, vp, i64, i, vp]
         L.wn_decode_layered_steps.argtypes = [cfgp, i, vp, vp, i, i, vp, i64, vp, vp, i, i, vp, i64, vp, vp, i, vp, f, vp]
+        # temperature / top-k / top-p (ABI v21): the plain calls' arguments, then const WnSampling* (NULL: the plain call), stream
+        L.wn_decode_steps_filtered.argtypes = [cfgp, i, vp, vp, vp, i, i, vp, i64, vp, vp, i, i, vp, vp, vp, i, vp, f,
+                                               ctypes.POINTER(WnSampling), vp]
+        L.wn_decode_layered_steps_filtered.argtypes = [cfgp, i, vp, vp, i, i, vp, i64, vp, vp, i, i, vp, i64, vp, vp, i, vp, f,
+                                                       ctypes.POINTER(WnSampling), vp]
         L.wn_decode_ctx_aux.argtypes = [cfgp, i, i, i, i, i, vp, vp, vp, vp]
         L.wn_decode_prefill_workspace_bytes.argtypes = [cfgp, i, i]
         L.wn_decode_prefill_workspace_bytes.restype = ctypes.c_size_t

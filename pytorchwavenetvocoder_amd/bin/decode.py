@@ -10,7 +10,10 @@ What differs from the reference:
     does the same with ``mp.Process``, decode.py:262,330-338);
   * every utterance of a batch is its own workgroup on the GPU, so batching costs no per-sample speed:
     ``--batch_size`` only bounds how many utterances are resident at once;
-  * soundfile / sklearn / torchvision are not needed (scipy writes the wav, the scaler is two numpy ops).
+  * soundfile / sklearn / torchvision are not needed (scipy writes the wav, the scaler is two numpy ops);
+  * extension flags: ``--weights ema`` decodes from the averaged weights, ``--temperature T --top_k K --top_p P`` draw with a
+    temperature from the k most probable classes / the smallest set holding the probability mass p, inside the decode kernels
+    (defaults 1 / 0 / 1: the reference's plain draw).
 """
 import argparse
 import logging
@@ -51,6 +54,14 @@ def get_parser():
     parser.add_argument("--weights", default="model", choices=["model", "ema"], type=str,
                         help="which weights of the checkpoint to decode from: the last iterate (\"model\") or their "
                              "exponential moving average (\"ema\", written by train.py --ema_decay)")
+    # extensions: temperature, top-k and nucleus (top-p) sampling inside the decode kernels; the defaults are the plain draw
+    parser.add_argument("--temperature", default=1.0, type=float,
+                        help="sampling temperature T > 0: the logits are multiplied by 1 / T (1: off)")
+    parser.add_argument("--top_k", default=0, type=int,
+                        help="draw among the k most probable classes only, ties at the k-th kept (0: off)")
+    parser.add_argument("--top_p", default=1.0, type=float,
+                        help="draw among the smallest set of most probable classes holding this probability mass, taken "
+                             "after --top_k (1: off)")
     return parser
 
 
@@ -160,17 +171,18 @@ def _decode_files(gpu, feat_list, args, config, mean, scale):
         feat_transform=make_feat_transform(mean, scale),
         upsampling_factor=config.upsampling_factor, use_upsampling_layer=config.use_upsampling_layer,
         use_speaker_code=config.use_speaker_code, device=device)
+    sampling = dict(temperature=getattr(args, "temperature", 1.0), top_k=getattr(args, "top_k", 0), top_p=getattr(args, "top_p", 1.0))
     if args.batch_size > 1:
         for feat_ids, (batch_x, batch_h, n_samples_list) in generator:
             logging.info("decoding start")
-            samples_list = model.batch_fast_generate(batch_x, batch_h, n_samples_list, args.intervals)
+            samples_list = model.batch_fast_generate(batch_x, batch_h, n_samples_list, args.intervals, **sampling)
             for feat_id, samples in zip(feat_ids, samples_list):
                 write_wav(args.outdir + "/" + feat_id + ".wav", decode_mu_law(samples, config.n_quantize), args.fs)
                 logging.info("wrote %s.wav in %s." % (feat_id, args.outdir))
     else:
         for feat_id, (x, h, n_samples) in generator:
             logging.info("decoding %s (length = %d)" % (feat_id, n_samples))
-            samples = model.fast_generate(x, h, n_samples, args.intervals)
+            samples = model.fast_generate(x, h, n_samples, args.intervals, **sampling)
             write_wav(args.outdir + "/" + feat_id + ".wav", decode_mu_law(samples, config.n_quantize), args.fs)
             logging.info("wrote %s.wav in %s." % (feat_id, args.outdir))
 

@@ -106,10 +106,26 @@ extern "C" int wn_decode_aux(const WnConfig* cfg, int B, int F, const float* wpa
     return rt_check("wn_decode_aux");
 }
 
-extern "C" int wn_decode_steps(const WnConfig* cfg, int B, const float* params, const float* wpack, const float* G, int F,
-                               int n_pad, int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end,
-                               int p0, int p1, float* state, const float* uniforms, float* logits_out, int mode,
-                               float* wave_out, float log_scale_min, void* stream) {
+// The setting of a *_filtered call as the kernels take it.  0: NULL or the identity (inverse temperature 1, no top-k, top-p 1) --
+// the call IS the plain call; 1: *s holds a setting to filter with (mode 1 only); < 0: refused, the message is set.
+static int sampling_set(const WnSampling* f, int mode, int Qo, WnSampleSet* s) {
+    if (!f) return 0;
+    if (!(f->inv_temperature > 0.0f) || !(f->inv_temperature <= 3.0e38f)) return -fail(1, "sampling: the inverse temperature should be positive and finite");
+    if (f->top_k < 0) return -fail(1, "sampling: top_k should be >= 0 (0: off), got %d", f->top_k);
+    if (!(f->top_p > 0.0f) || !(f->top_p <= 1.0f)) return -fail(1, "sampling: top_p should be in (0, 1] (1: off)");
+    s->inv_t = f->inv_temperature;
+    s->top_k = f->top_k >= Qo ? 0 : f->top_k;
+    s->top_p = f->top_p;
+    if (s->inv_t == 1.0f && s->top_k == 0 && s->top_p >= 1.0f) return 0;
+    if (mode != 1) return -fail(1, "temperature / top_k / top_p apply to mode 1 (sampling on the softmax head) only, got mode %d", mode);
+    if (Qo > WN_SAMPLE_QMAX) return -fail(3, "temperature / top_k / top_p cover up to %d classes, the model has %d", WN_SAMPLE_QMAX, Qo);
+    return 1;
+}
+
+static int decode_steps_impl(const WnConfig* cfg, int B, const float* params, const float* wpack, const float* G, int F,
+                             int n_pad, int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end,
+                             int p0, int p1, float* state, const float* uniforms, float* logits_out, int mode,
+                             float* wave_out, float log_scale_min, const WnSampling* sampling, void* stream) {
     api_enter();
     Dims d;
     WnDecodePlan pl;
@@ -120,6 +136,9 @@ extern "C" int wn_decode_steps(const WnConfig* cfg, int B, const float* params, 
     if (mode != 0 && mode != 1 && mode != 2) return fail(1, "mode should be 0 (argmax), 1 (sampling) or 2 (mixture of logistics)");
     if (mode != 0 && !uniforms) return fail(1, "sampling modes need the uniform draws");
     if (mode == 2 && (d.Qo % 3 != 0 || d.Qo == d.Q)) return fail(1, "mode 2 needs out_channels = 3 * n_mixture");
+    WnSampleSet fs = {1.0f, 0, 1.0f};
+    const int filtered = sampling_set(sampling, mode, d.Qo, &fs);
+    if (filtered < 0) return -filtered;
     if (p1 == p0) return 0;
     const Lay y = make_lay(d);
     WnDecodeArgs a;
@@ -141,8 +160,26 @@ extern "C" int wn_decode_steps(const WnConfig* cfg, int B, const float* params, 
     a.logits_out = logits_out; a.lo_bstride = Ttot * d.Qo;
     a.mode = mode;
     a.wave_out = wave_out; a.w_bstride = Ttot; a.log_scale_min = log_scale_min;
+    a.filtered = filtered; a.filt = fs;
     WN_TRY(wn_decode_launch(&a, B, (wn_stream_t)stream));
     return rt_check("wn_decode_steps");
+}
+
+extern "C" int wn_decode_steps(const WnConfig* cfg, int B, const float* params, const float* wpack, const float* G, int F,
+                               int n_pad, int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end,
+                               int p0, int p1, float* state, const float* uniforms, float* logits_out, int mode,
+                               float* wave_out, float log_scale_min, void* stream) {
+    return decode_steps_impl(cfg, B, params, wpack, G, F, n_pad, samples, Ttot, t_forced, t_end, p0, p1, state, uniforms, logits_out,
+                             mode, wave_out, log_scale_min, nullptr, stream);
+}
+
+// since ABI v21: wn_decode_steps with temperature / top-k / top-p on the sampling mode (csrc/wn_sample.h)
+extern "C" int wn_decode_steps_filtered(const WnConfig* cfg, int B, const float* params, const float* wpack, const float* G, int F,
+                                        int n_pad, int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end,
+                                        int p0, int p1, float* state, const float* uniforms, float* logits_out, int mode,
+                                        float* wave_out, float log_scale_min, const WnSampling* sampling, void* stream) {
+    return decode_steps_impl(cfg, B, params, wpack, G, F, n_pad, samples, Ttot, t_forced, t_end, p0, p1, state, uniforms, logits_out,
+                             mode, wave_out, log_scale_min, sampling, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -348,10 +385,10 @@ extern "C" int wn_decode_layered_prepare(const WnConfig* cfg, int B, int F, cons
     return rt_check("wn_decode_layered_prepare");
 }
 
-extern "C" int wn_decode_layered_steps(const WnConfig* cfg, int B, const float* params, const float* G, int F, int n_pad,
-                                       int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end, int p0,
-                                       int p1, float* state, int64_t state_floats, const float* uniforms, float* logits_out,
-                                       int mode, float* wave_out, float log_scale_min, void* stream) {
+static int decode_layered_steps_impl(const WnConfig* cfg, int B, const float* params, const float* G, int F, int n_pad,
+                                     int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end, int p0,
+                                     int p1, float* state, int64_t state_floats, const float* uniforms, float* logits_out,
+                                     int mode, float* wave_out, float log_scale_min, const WnSampling* sampling, void* stream) {
     api_enter();
     Dims d;
     WN_TRY(check_cfg(cfg, &d));
@@ -363,6 +400,9 @@ extern "C" int wn_decode_layered_steps(const WnConfig* cfg, int B, const float* 
     if (mode != 0 && mode != 1 && mode != 2) return fail(1, "mode should be 0 (argmax), 1 (sampling) or 2 (mixture of logistics)");
     if (mode != 0 && !uniforms) return fail(1, "sampling modes need the uniform draws");
     if (mode == 2 && (d.Qo % 3 != 0 || d.Qo == d.Q)) return fail(1, "mode 2 needs out_channels = 3 * n_mixture");
+    WnSampleSet fs = {1.0f, 0, 1.0f};
+    const int filtered = sampling_set(sampling, mode, d.Qo, &fs);
+    if (filtered < 0) return -filtered;
     DlLay y;
     WN_TRY(dl_layout(cfg, d, B, granules, &y));
     if (state_floats < y.total) return fail(1, "decode state too small: %ld < %ld floats", (long)state_floats, y.total);
@@ -393,6 +433,7 @@ extern "C" int wn_decode_layered_steps(const WnConfig* cfg, int B, const float* 
         a.err = reinterpret_cast<int*>(ws + y.dlp_err);
         a.handoff = y.dlp_flags_on; a.Bp = y.dlp.wide ? ((nb + WN_DLPM_CB - 1) / WN_DLPM_CB) * WN_DLPM_CB : nb;
         a.flags = reinterpret_cast<unsigned long long*>(ws + y.dlp_flags);
+        a.filtered = filtered; a.filt = fs;
         const int rc = y.dlp_flags_on ? wn_dlpf_launch(&a, c.st) : (y.dlp.wide ? wn_dlpm_launch(&a, c.st) : wn_dlp_launch(&a, c.st));
         if (rc == 4)
             return fail(4, "the persistent decode launch needs %d workgroups resident at once, the device keeps %d: "
@@ -479,11 +520,31 @@ extern "C" int wn_decode_layered_steps(const WnConfig* cfg, int B, const float* 
         if (mode == 2)
             WN_TRY(wn_dl_select_mol(ws + y.logits, d.Qo / 3, nb, d.Q, samples, wave_out, Ttot, t_forced, t_end, p, uniforms,
                                     logits_out, log_scale_min, c.st));
+        else if (filtered)
+            WN_TRY(wn_dl_select_filtered(ws + y.logits, d.Qo, nb, samples, Ttot, t_forced, t_end, p, uniforms, logits_out, fs, c.st));
         else
             WN_TRY(wn_dl_select(ws + y.logits, d.Qo, nb, samples, Ttot, t_forced, t_end, p, uniforms, logits_out, mode, c.st));
         WN_TRY(wn_dl_push(&a, c.st));
     }
     return rt_check("wn_decode_layered_steps");
+}
+
+extern "C" int wn_decode_layered_steps(const WnConfig* cfg, int B, const float* params, const float* G, int F, int n_pad,
+                                       int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end, int p0,
+                                       int p1, float* state, int64_t state_floats, const float* uniforms, float* logits_out,
+                                       int mode, float* wave_out, float log_scale_min, void* stream) {
+    return decode_layered_steps_impl(cfg, B, params, G, F, n_pad, samples, Ttot, t_forced, t_end, p0, p1, state, state_floats, uniforms,
+                                     logits_out, mode, wave_out, log_scale_min, nullptr, stream);
+}
+
+// since ABI v21: wn_decode_layered_steps with temperature / top-k / top-p on the sampling mode (csrc/wn_sample.h)
+extern "C" int wn_decode_layered_steps_filtered(const WnConfig* cfg, int B, const float* params, const float* G, int F, int n_pad,
+                                                int64_t* samples, int64_t Ttot, const int32_t* t_forced, const int32_t* t_end,
+                                                int p0, int p1, float* state, int64_t state_floats, const float* uniforms,
+                                                float* logits_out, int mode, float* wave_out, float log_scale_min,
+                                                const WnSampling* sampling, void* stream) {
+    return decode_layered_steps_impl(cfg, B, params, G, F, n_pad, samples, Ttot, t_forced, t_end, p0, p1, state, state_floats, uniforms,
+                                     logits_out, mode, wave_out, log_scale_min, sampling, stream);
 }
 
 // ---- parallel context walk (reference wavenet.py:338-349: the "prepare buffer" pass is a full forward) --------

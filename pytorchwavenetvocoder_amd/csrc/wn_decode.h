@@ -7,6 +7,7 @@
 // utterance at the BASELINE size) in an L2-resident ring buffer per layer.
 #pragma once
 #include "wn_device.h"
+#include "wn_sample.h"
 
 #define WN_DT 512  // threads per decode workgroup (8 waves, 2 per SIMD)
 
@@ -53,6 +54,8 @@ typedef struct WnDecodeArgs {
     float* wave_out;      // mode 2, nullable (B, Ttot): the drawn waveform value of position p+1
     float log_scale_min;  // mode 2: clamp of the mixture log-scales (the value wn_mol_loss was trained with)
     long w_bstride;
+    int filtered;         // mode 1 only: 1 = the temperature / top-k / top-p choice of wn_sample.h with `filt` (its own instantiation)
+    WnSampleSet filt;
 #ifdef WN_TIMING
     long long* dbg;
 #endif

@@ -226,7 +226,10 @@ static __device__ __forceinline__ int wn_opaque(int v) {
     return v;
 }
 
-template <int UD, int UR, int US, int UP1, int UP2>
+// FILT: the sampling mode with temperature / top-k / top-p (wn_sample.h).  A template parameter, not a branch: the step holds the
+// prefetched layer-0 weights in registers across the token choice under a 128-register bound, and the plain instantiation is
+// the code it was (profiles/sampling/resource_usage.txt).
+template <int UD, int UR, int US, int UP1, int UP2, bool FILT>
 __global__ __launch_bounds__(WN_DT) void k_decode(WnDecodeArgs a) {
     constexpr int UL = UD + UR + US;
     constexpr int UP = UP1 + UP2;
@@ -535,7 +538,9 @@ __global__ __launch_bounds__(WN_DT) void k_decode(WnDecodeArgs a) {
                 if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
             }
             int chosen = bi;  // argmax: first maximal index
-            if (a.mode == 1 && a.uniforms != nullptr) {
+            if constexpr (FILT) {  // wave 0 is the utterance's wave: temperature, top-k, top-p, then the same draw
+                chosen = wn_sample_filtered([&](int q) { return lgt[q]; }, Qo, tid, a.filt, a.uniforms[(long)b * a.u_bstride + p + 1]);
+            } else if (a.mode == 1 && a.uniforms != nullptr) {
                 float lsum = 0.f;
                 for (int i = 0; i < per; ++i) {
                     const int q = q0 + i;
@@ -580,27 +585,36 @@ __global__ __launch_bounds__(WN_DT) void k_decode(WnDecodeArgs a) {
     }
 }
 
-template <int UD, int UR, int US, int UP1, int UP2>
+template <int UD, int UR, int US, int UP1, int UP2, bool FILT>
 static int launch_cls(const WnDecodeArgs& a, int B, wn_stream_t st) {
-    if (wn_dyn_lds<k_decode<UD, UR, US, UP1, UP2>>(a.plan.lds_bytes)) return 1;
+    if (wn_dyn_lds<k_decode<UD, UR, US, UP1, UP2, FILT>>(a.plan.lds_bytes)) return 1;
 #ifdef WN_TIMING
     WnDecodeArgs a2 = a;
     a2.dbg = g_dec_dbg;
-    WN_LAUNCH((k_decode<UD, UR, US, UP1, UP2>), dim3((unsigned)B), dim3(WN_DT), a.plan.lds_bytes, st, a2);
+    WN_LAUNCH((k_decode<UD, UR, US, UP1, UP2, FILT>), dim3((unsigned)B), dim3(WN_DT), a.plan.lds_bytes, st, a2);
     return 0;
 #endif
-    WN_LAUNCH((k_decode<UD, UR, US, UP1, UP2>), dim3((unsigned)B), dim3(WN_DT), a.plan.lds_bytes, st, a);
+    WN_LAUNCH((k_decode<UD, UR, US, UP1, UP2, FILT>), dim3((unsigned)B), dim3(WN_DT), a.plan.lds_bytes, st, a);
     return 0;
 }
 
 int wn_decode_launch(const WnDecodeArgs* ap, int B, wn_stream_t st) {
     const WnDecodeArgs& a = *ap;
     if (!a.plan.ok || B <= 0) return 1;
+    if (a.filtered && (a.mode != 1 || a.uniforms == nullptr || a.Qo > WN_SAMPLE_QMAX)) return 1;
     const double steps = (double)(a.p1 - a.p0) * B;
+    if (a.filtered) {
+        WN_PROF("decode_steps_filtered", steps * 8.0 * a.plan.stream_f4, steps * 16.0 * a.plan.stream_f4, st);
+        switch (a.plan.cls) {
+            case 0: return launch_cls<8, 2, 8, 32, 32, true>(a, B, st);
+            case 1: return launch_cls<12, 2, 8, 32, 32, true>(a, B, st);
+            default: return 2;
+        }
+    }
     WN_PROF("decode_steps", steps * 8.0 * a.plan.stream_f4, steps * 16.0 * a.plan.stream_f4, st);
     switch (a.plan.cls) {
-        case 0: return launch_cls<8, 2, 8, 32, 32>(a, B, st);
-        case 1: return launch_cls<12, 2, 8, 32, 32>(a, B, st);
+        case 0: return launch_cls<8, 2, 8, 32, 32, false>(a, B, st);
+        case 1: return launch_cls<12, 2, 8, 32, 32, false>(a, B, st);
         default: return 2;
     }
 }

@@ -7,6 +7,7 @@
 // polls the granules themselves: 0.7 - 0.8 us per hop, profiles/r04/handoff_microbench.txt) -- no grid barrier, no fences.
 #pragma once
 #include "wn_device.h"
+#include "wn_sample.h"
 
 #define WN_DLP_T 512     // threads per workgroup (8 waves: 2 per SIMD, 256 VGPRs each for the stage's weights)
 #define WN_DLP_NW 8
@@ -76,6 +77,8 @@ typedef struct WnDlpArgs {
     int handoff;             // 0: granules (wn_dlp.hip, wn_dlpm.hip), 1: flags (wn_dlpf.hip)
     int Bp;                  // row stride of the plain vectors: 16 * blocks
     unsigned long long* flags;   // [blocks][NU]: the tag of the latest stage the unit has published
+    int filtered;            // mode 1 only: 1 = the temperature / top-k / top-p choice of wn_sample.h with `filt`, a wave per utterance
+    WnSampleSet filt;        // (its own instantiation of the kernel: the plain modes' code is what it was)
 } WnDlpArgs;
 
 struct WnDlpPackArgs {

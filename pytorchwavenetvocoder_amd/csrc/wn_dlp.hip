@@ -191,7 +191,9 @@ static __device__ __forceinline__ long dlp_queue_off(int l, int depth, int K, in
 #define DLP_STAMP(stage, ph)
 #endif
 
-template <int RS, int NSP, int NSX>
+// FILT: the sampling mode with temperature / top-k / top-p (wn_sample.h) -- a template parameter, so that the plain instantiation is
+// the code it was; the choice is made by a wave per utterance of the column block (the other waves are idle there anyway).
+template <int RS, int NSP, int NSX, bool FILT>
 __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlp(WnDlpArgs a) {
     WN_DYN_SMEM(smem_raw);
     if (wn_load_coherent_int(a.err) != 0) return;   // an earlier launch on this state timed out (or this one already has): nothing to continue from
@@ -573,7 +575,26 @@ __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlp(WnDlpArgs a) {
             const int nbc = (B - cb * CB) < CB ? (B - cb * CB) : CB;
             gather_vec(a.gl, Qo, nbc, cb, tag0 + (unsigned)(L + 3));
             __syncthreads();
-            if (tid < CB && cb * CB + tid < B) {
+            if constexpr (FILT) {
+                if (wave < nbc) {   // wave w chooses for utterance w of the block: identical arithmetic in every unit
+                    const int b = cb * CB + wave;
+                    const float* lg = s_in + wave * KPAD;
+                    if (u == 0 && a.logits_out)
+                        for (int q = lane; q < Qo; q += 64) a.logits_out[((long)b * a.Ttot + p) * Qo + q] = lg[q];
+                    const int chosen = wn_sample_filtered([&](int q) { return lg[q]; }, Qo, lane, a.filt, a.uniforms[(long)b * a.Ttot + p + 1]);
+                    if (lane == 0) {
+                        const bool gen = p + 1 >= a.t_forced[b] && p + 1 < a.t_end[b];
+                        long long nxt = chosen;
+                        if (!gen && p + 1 < a.Ttot) {
+                            nxt = a.samples[(long)b * a.Ttot + p + 1] % a.Q;
+                            if (nxt < 0) nxt += a.Q;
+                        }
+                        if (gen && u == 0) a.samples[(long)b * a.Ttot + p + 1] = chosen;
+                        for (int j = 0; j + 1 < K; ++j) s_tok[j * BM + b] = s_tok[(j + 1) * BM + b];
+                        s_tok[(K - 1) * BM + b] = (int)nxt;
+                    }
+                }
+            } else if (tid < CB && cb * CB + tid < B) {
                 const int b = cb * CB + tid;
                 float best = -3.0e38f;
                 int bi = 0;
@@ -614,16 +635,21 @@ __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlp(WnDlpArgs a) {
 }
 
 // LDS limit (wn_dyn_lds) and the number of workgroups of this class the device keeps resident (cached; 0: the query failed)
-template <int RS, int NSP, int NSX>
+template <int RS, int NSP, int NSX, bool FILT = false>
 static int capacity_cls(long lds_bytes) {
-    if (wn_dyn_lds<k_dlp<RS, NSP, NSX>>((size_t)lds_bytes)) return 0;
-    return wn_coop_capacity_cached<k_dlp<RS, NSP, NSX>>(WN_DLP_T, (size_t)lds_bytes);
+    if (wn_dyn_lds<k_dlp<RS, NSP, NSX, FILT>>((size_t)lds_bytes)) return 0;
+    return wn_coop_capacity_cached<k_dlp<RS, NSP, NSX, FILT>>(WN_DLP_T, (size_t)lds_bytes);
 }
 
 template <int RS, int NSP, int NSX>
 static int launch_cls(const WnDlpArgs& a, wn_stream_t st) {
+    if (a.filtered) {
+        if (a.plan.NU > capacity_cls<RS, NSP, NSX, true>(a.plan.lds_bytes)) return 4;
+        WN_LAUNCH_COOP((k_dlp<RS, NSP, NSX, true>), dim3((unsigned)a.plan.NU), dim3(WN_DLP_T), (size_t)a.plan.lds_bytes, st, a);
+        return 0;
+    }
     if (a.plan.NU > capacity_cls<RS, NSP, NSX>(a.plan.lds_bytes)) return 4;   // not all workgroups would be resident: no launch
-    WN_LAUNCH_COOP((k_dlp<RS, NSP, NSX>), dim3((unsigned)a.plan.NU), dim3(WN_DLP_T), (size_t)a.plan.lds_bytes, st, a);
+    WN_LAUNCH_COOP((k_dlp<RS, NSP, NSX, false>), dim3((unsigned)a.plan.NU), dim3(WN_DLP_T), (size_t)a.plan.lds_bytes, st, a);
     return 0;
 }
 
@@ -644,7 +670,8 @@ int wn_dlp_launch(const WnDlpArgs* ap, wn_stream_t st) {
     const WnDlpArgs& a = *ap;
     if (!a.plan.ok || a.B < 1 || a.B > WN_DLP_BMAX || a.p1 < a.p0) return 1;
     if (a.mode != 0 && a.mode != 1) return 2;
-    WN_PROF("dlp_steps", 0.0, 0.0, st);
+    if (a.filtered && (a.mode != 1 || a.uniforms == nullptr || a.Qo > WN_SAMPLE_QMAX)) return 2;
+    WN_PROF(a.filtered ? "dlp_steps_filtered" : "dlp_steps", 0.0, 0.0, st);
     switch (a.plan.cls) {
         case 0: return launch_cls<8, 24, 8>(a, st);
         case 1: return launch_cls<8, 32, 8>(a, st);

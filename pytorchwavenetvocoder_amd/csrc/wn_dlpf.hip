@@ -51,7 +51,8 @@ static __device__ __forceinline__ long dlpf_queue_off(int l, int depth, int K, i
 #define DLPF_STAMP(stage, ph)
 #endif
 
-template <int NSP, int NSX>
+// FILT: the sampling mode with temperature / top-k / top-p (wn_sample.h), its own instantiation (as k_dlp)
+template <int NSP, int NSX, bool FILT>
 __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlpf(WnDlpArgs a) {
     WN_DYN_SMEM(smem_raw);
     if (wn_load_coherent_int(a.err) != 0) return;   // an earlier launch on this state timed out (or this one already has): nothing to continue from
@@ -413,8 +414,28 @@ __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlpf(WnDlpArgs a) {
             }
             WN_WAIT_VMCNT(0);
             __syncthreads();
+            // filtered sampling (wn_sample.h): a wave per utterance column, columns w and w + 8 of the block for wave w; unit 0 writes the logits out
+            if constexpr (FILT) {
+                for (int c = wave; c < nbc; c += WN_DLP_NW) {
+                    const int bb = cblk * CB + c;
+                    if (u == 0 && a.logits_out)
+                        for (int qi = lane; qi < Qo; qi += 64) a.logits_out[((long)bb * a.Ttot + p) * Qo + qi] = s_p[qi * CB + c];
+                    const int chosen = wn_sample_filtered([&](int qi) { return s_p[qi * CB + c]; }, Qo, lane, a.filt, a.uniforms[(long)bb * a.Ttot + p + 1]);
+                    if (lane == 0) {
+                        const bool gen = p + 1 >= a.t_forced[bb] && p + 1 < a.t_end[bb];
+                        long long nxt = chosen;
+                        if (!gen && p + 1 < a.Ttot) {
+                            nxt = a.samples[(long)bb * a.Ttot + p + 1] % a.Q;
+                            if (nxt < 0) nxt += a.Q;
+                        }
+                        if (gen && u == 0) a.samples[(long)bb * a.Ttot + p + 1] = chosen;
+                        for (int j = 0; j + 1 < K; ++j) s_tok[j * CB + c] = s_tok[(j + 1) * CB + c];
+                        s_tok[(K - 1) * CB + c] = (int)nxt;
+                    }
+                }
+            }
             const int nq = (Qo - kk + 31) / 32;   // logit rows kk + 32 j < Qo of this thread
-            {
+            if constexpr (!FILT) {
                 float best = -3.0e38f;
                 int bi = 0x7fffffff;
                 for (int j = 0; j < nq; ++j) {
@@ -426,8 +447,8 @@ __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlpf(WnDlpArgs a) {
                 s_red[(kk * CB + col) * 2] = best;
                 reinterpret_cast<int*>(s_red)[(kk * CB + col) * 2 + 1] = bi;
             }
-            __syncthreads();
-            if (tid < nbc) {
+            if constexpr (!FILT) __syncthreads();
+            if (!FILT && tid < nbc) {
                 const int bb = cblk * CB + tid;
                 float best = -3.0e38f;
                 int bi = 0;
@@ -474,18 +495,23 @@ static constexpr size_t lds_flags() {
     return ((size_t)32 * NSP * 16 + (NSP * 3 <= 160 ? 32 * NSX * 16 : 0) + 4096 + 8 * 16 + 8 * 16 + 4 * 16 + 64) * 4;
 }
 
-template <int NSP, int NSX>
+template <int NSP, int NSX, bool FILT = false>
 static int capacity_flags() {   // as capacity_cls of wn_dlp.hip
     constexpr size_t lds = lds_flags<NSP, NSX>();
-    if (wn_dyn_lds<k_dlpf<NSP, NSX>>(lds)) return 0;
-    return wn_coop_capacity_cached<k_dlpf<NSP, NSX>>(WN_DLP_T, lds);
+    if (wn_dyn_lds<k_dlpf<NSP, NSX, FILT>>(lds)) return 0;
+    return wn_coop_capacity_cached<k_dlpf<NSP, NSX, FILT>>(WN_DLP_T, lds);
 }
 
 template <int NSP, int NSX>
 static int launch_flags(const WnDlpArgs& a, int nblk, wn_stream_t st) {
-    if (a.plan.NU * nblk > capacity_flags<NSP, NSX>()) return 4;   // not all workgroups would be resident: no launch
     constexpr size_t lds = lds_flags<NSP, NSX>();
-    WN_LAUNCH_COOP((k_dlpf<NSP, NSX>), dim3((unsigned)(a.plan.NU * nblk)), dim3(WN_DLP_T), lds, st, a);
+    if (a.filtered) {
+        if (a.plan.NU * nblk > capacity_flags<NSP, NSX, true>()) return 4;
+        WN_LAUNCH_COOP((k_dlpf<NSP, NSX, true>), dim3((unsigned)(a.plan.NU * nblk)), dim3(WN_DLP_T), lds, st, a);
+        return 0;
+    }
+    if (a.plan.NU * nblk > capacity_flags<NSP, NSX>()) return 4;   // not all workgroups would be resident: no launch
+    WN_LAUNCH_COOP((k_dlpf<NSP, NSX, false>), dim3((unsigned)(a.plan.NU * nblk)), dim3(WN_DLP_T), lds, st, a);
     return 0;
 }
 
@@ -502,7 +528,8 @@ int wn_dlpf_launch(const WnDlpArgs* ap, wn_stream_t st) {
     const int nblk = (a.B + WN_DLPM_CB - 1) / WN_DLPM_CB;
     if (a.Bp != nblk * WN_DLPM_CB || a.plan.NU * nblk > WN_DLPM_MAXWG) return 1;
     if (a.mode != 0 && a.mode != 1) return 2;
+    if (a.filtered && (a.mode != 1 || a.uniforms == nullptr || a.Qo > WN_SAMPLE_QMAX)) return 2;
     if ((long)2 * 2 * a.R * a.Bp * 4 > 0x7fffffffL || a.qfloats * a.B * 4 > 0xffffffffL) return 1;
-    WN_PROF("dlpf_steps", 0.0, 0.0, st);
+    WN_PROF(a.filtered ? "dlpf_steps_filtered" : "dlpf_steps", 0.0, 0.0, st);
     return a.plan.NSP == 48 ? launch_flags<48, 16>(a, nblk, st) : launch_flags<64, 16>(a, nblk, st);
 }

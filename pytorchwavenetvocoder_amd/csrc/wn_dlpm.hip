@@ -39,7 +39,8 @@ static __device__ __forceinline__ long dlpm_queue_off(int l, int depth, int K, i
 #define DLPM_STAMP(stage, ph)
 #endif
 
-template <int NSP, int NSX>
+// FILT: the sampling mode with temperature / top-k / top-p (wn_sample.h), its own instantiation (as k_dlp)
+template <int NSP, int NSX, bool FILT>
 __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlpm(WnDlpArgs a) {
     WN_DYN_SMEM(smem_raw);
     if (wn_load_coherent_int(a.err) != 0) return;   // an earlier launch on this state timed out (or this one already has): nothing to continue from
@@ -395,9 +396,29 @@ __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlpm(WnDlpArgs a) {
                     if (live && j0 + jj < nq) s_in[sin_off(kk + 32 * (j0 + jj)) + col] = wn_bits_f32((unsigned)gv[jj]);
             }
             __syncthreads();
+            // filtered sampling (wn_sample.h): a wave per utterance column, columns w and w + 8 of the block for wave w; unit 0 writes the logits out
+            if constexpr (FILT) {
+                for (int c = wave; c < nbc; c += WN_DLP_NW) {
+                    const int bb = cblk * CB + c;
+                    if (u == 0 && a.logits_out)
+                        for (int qi = lane; qi < Qo; qi += 64) a.logits_out[((long)bb * a.Ttot + p) * Qo + qi] = s_in[sin_off(qi) + c];
+                    const int chosen = wn_sample_filtered([&](int qi) { return s_in[sin_off(qi) + c]; }, Qo, lane, a.filt, a.uniforms[(long)bb * a.Ttot + p + 1]);
+                    if (lane == 0) {
+                        const bool gen = p + 1 >= a.t_forced[bb] && p + 1 < a.t_end[bb];
+                        long long nxt = chosen;
+                        if (!gen && p + 1 < a.Ttot) {
+                            nxt = a.samples[(long)bb * a.Ttot + p + 1] % a.Q;
+                            if (nxt < 0) nxt += a.Q;
+                        }
+                        if (gen && u == 0) a.samples[(long)bb * a.Ttot + p + 1] = chosen;
+                        for (int j = 0; j + 1 < K; ++j) s_tok[j * CB + c] = s_tok[(j + 1) * CB + c];
+                        s_tok[(K - 1) * CB + c] = (int)nxt;
+                    }
+                }
+            }
             // first-max argmax: a thread scans its own logit rows kk + 32 j (ascending), the 32 candidates of a column are
             // compared by one thread (larger value, then smaller index); unit 0 writes the logits out, a thread its own rows
-            {
+            if constexpr (!FILT) {
                 float best = -3.0e38f;
                 int bi = 0x7fffffff;
                 for (int j = 0; j < nq; ++j) {
@@ -409,8 +430,8 @@ __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlpm(WnDlpArgs a) {
                 s_red[(kk * CB + col) * 2] = best;
                 reinterpret_cast<int*>(s_red)[(kk * CB + col) * 2 + 1] = bi;
             }
-            __syncthreads();
-            if (tid < nbc) {
+            if constexpr (!FILT) __syncthreads();
+            if (!FILT && tid < nbc) {
                 const int bb = cblk * CB + tid;
                 float best = -3.0e38f;
                 int bi = 0;
@@ -450,17 +471,22 @@ __global__ __launch_bounds__(WN_DLP_T, 2) void k_dlpm(WnDlpArgs a) {
     if (tid == 0 && s_flag[0]) wn_store_coherent_int(a.err, 1);
 }
 
-template <int NSP, int NSX>
+template <int NSP, int NSX, bool FILT = false>
 static int capacity_wide(long lds_bytes) {   // as capacity_cls of wn_dlp.hip
-    if (wn_dyn_lds<k_dlpm<NSP, NSX>>((size_t)lds_bytes)) return 0;
-    return wn_coop_capacity_cached<k_dlpm<NSP, NSX>>(WN_DLP_T, (size_t)lds_bytes);
+    if (wn_dyn_lds<k_dlpm<NSP, NSX, FILT>>((size_t)lds_bytes)) return 0;
+    return wn_coop_capacity_cached<k_dlpm<NSP, NSX, FILT>>(WN_DLP_T, (size_t)lds_bytes);
 }
 
 template <int NSP, int NSX>
 static int launch_wide(const WnDlpArgs& a, wn_stream_t st) {
     const int nblk = (a.B + WN_DLPM_CB - 1) / WN_DLPM_CB;
+    if (a.filtered) {
+        if (a.plan.NU * nblk > capacity_wide<NSP, NSX, true>(a.plan.lds_bytes)) return 4;
+        WN_LAUNCH_COOP((k_dlpm<NSP, NSX, true>), dim3((unsigned)(a.plan.NU * nblk)), dim3(WN_DLP_T), (size_t)a.plan.lds_bytes, st, a);
+        return 0;
+    }
     if (a.plan.NU * nblk > capacity_wide<NSP, NSX>(a.plan.lds_bytes)) return 4;   // not all workgroups would be resident: no launch
-    WN_LAUNCH_COOP((k_dlpm<NSP, NSX>), dim3((unsigned)(a.plan.NU * nblk)), dim3(WN_DLP_T), (size_t)a.plan.lds_bytes, st, a);
+    WN_LAUNCH_COOP((k_dlpm<NSP, NSX, false>), dim3((unsigned)(a.plan.NU * nblk)), dim3(WN_DLP_T), (size_t)a.plan.lds_bytes, st, a);
     return 0;
 }
 
@@ -478,7 +504,8 @@ int wn_dlpm_launch(const WnDlpArgs* ap, wn_stream_t st) {
     if (!a.plan.ok || !a.plan.wide || a.plan.RS != 16 || a.B < 1 || a.B > WN_DLPM_BMAX || a.p1 < a.p0) return 1;
     if (a.plan.NU * ((a.B + WN_DLPM_CB - 1) / WN_DLPM_CB) > WN_DLPM_MAXWG) return 1;   // all workgroups resident at once
     if (a.mode != 0 && a.mode != 1) return 2;
-    WN_PROF("dlpm_steps", 0.0, 0.0, st);
+    if (a.filtered && (a.mode != 1 || a.uniforms == nullptr || a.Qo > WN_SAMPLE_QMAX)) return 2;
+    WN_PROF(a.filtered ? "dlpm_steps_filtered" : "dlpm_steps", 0.0, 0.0, st);
     switch (a.plan.cls) {
         case 2: return launch_wide<48, 16>(a, st);
         case 3: return launch_wide<64, 16>(a, st);

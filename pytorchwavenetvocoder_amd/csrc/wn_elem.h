@@ -2,6 +2,7 @@
 // All tensors are channel-major (B, C, T) fp32 like the reference's; indices are int64.
 #pragma once
 #include "wn_device.h"
+#include "wn_sample.h"
 
 // x0[b][r][t] = bc[r] + sum_tap Wc_f[tap][x[b][t-(K-1-tap)] mod Q][r]   (zero history)
 // == reference OneHot + CausalConv1d(Q->R,K)  (wavenet.py:88-92,513-516,118-121)
@@ -167,6 +168,9 @@ int wn_dl_push(const WnDlArgs* a, wn_stream_t st);
 // Token choice per utterance from logits [Q][nb]: argmax or inverse-CDF draw; teacher forcing below t_forced.
 int wn_dl_select(const float* logits, int Q, int nb, int64_t* samples, long Ttot, const int* t_forced, const int* t_end,
                  int p, const float* uniforms, float* logits_out, int mode, wn_stream_t st);
+// The sampling mode with temperature / top-k / top-p (wn_sample.h), a wave per utterance; Q <= WN_SAMPLE_QMAX.
+int wn_dl_select_filtered(const float* logits, int Q, int nb, int64_t* samples, long Ttot, const int* t_forced, const int* t_end,
+                          int p, const float* uniforms, float* logits_out, WnSampleSet f, wn_stream_t st);
 
 // Skinny contraction of the any-size decode: C[z][m][u] = epi( sum_k A[z](m,k) * B[z][k][u] ), u < nb (tens of
 // utterances), A(m,k) = Az[k*lda + m] (the packed transposed weights).  One workgroup = 32 output rows x 32

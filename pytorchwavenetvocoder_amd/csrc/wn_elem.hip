@@ -1218,6 +1218,28 @@ int wn_dl_select(const float* logits, int Q, int nb, int64_t* samples, long Ttot
     return 0;
 }
 
+// the sampling mode with temperature / top-k / top-p (wn_sample.h): one WAVE per utterance, 4 utterances per workgroup
+__global__ __launch_bounds__(256) void k_dl_select_filtered(const float* __restrict__ logits, int Q, int nb, int64_t* samples, long Ttot,
+                                                            const int* t_forced, const int* t_end, int p, const float* uniforms,
+                                                            float* logits_out, WnSampleSet f) {
+    const int lane = threadIdx.x & 63;
+    const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= nb) return;   // (a whole wave)
+    if (logits_out)
+        for (int q = lane; q < Q; q += 64) logits_out[((long)u * Ttot + p) * Q + q] = logits[(long)q * nb + u];
+    const int chosen = wn_sample_filtered([&](int q) { return logits[(long)q * nb + u]; }, Q, lane, f, uniforms[(long)u * Ttot + p + 1]);
+    if (lane == 0 && p + 1 >= t_forced[u] && p + 1 < t_end[u]) samples[(long)u * Ttot + p + 1] = chosen;
+}
+
+int wn_dl_select_filtered(const float* logits, int Q, int nb, int64_t* samples, long Ttot, const int* t_forced, const int* t_end, int p,
+                          const float* uniforms, float* logits_out, WnSampleSet f, wn_stream_t st) {
+    if (!uniforms || Q > WN_SAMPLE_QMAX) return 1;
+    WN_PROF("dl_select_filtered", 0.0, 0.0, st);
+    WN_LAUNCH(k_dl_select_filtered, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, logits, Q, nb, samples, Ttot, t_forced, t_end, p,
+              uniforms, logits_out, f);
+    return 0;
+}
+
 // NW waves split the K range of a 32 x 32 output tile; every wave requests the operands of up to four 16-k
 // steps before its first MFMA (a launch is a handful of dependent memory round trips, so what counts is how few
 // of them are exposed), partial tiles are summed through LDS in a fixed order.

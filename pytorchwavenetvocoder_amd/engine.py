@@ -1110,8 +1110,29 @@ class WaveNetEngine(object):
     def decode_supported(self):
         return bool(self.lib.wn_decode_supported(ctypes.byref(self.cfg)))
 
+    def sampling_setting(self, mode, temperature=1.0, top_k=None, top_p=None):
+        """``WnSampling`` of a decode with these parameters, or None for the identity (temperature 1, no top-k, top-p 1: the plain
+        call).  ValueError for a temperature that is not positive and finite, top_k < 0, top_p outside (0, 1], and for parameters
+        other than the identity with anything but mode "sampling" on the softmax head."""
+        T = float(temperature)
+        k = 0 if top_k is None else int(top_k)
+        pp = 1.0 if top_p is None else float(top_p)
+        if not (T > 0.0) or T == float("inf") or 1.0 / T > 3.0e38:
+            raise ValueError("temperature should be positive and finite, got %r" % (temperature,))
+        if k < 0:
+            raise ValueError("top_k should be >= 0 (0 or None: off), got %r" % (top_k,))
+        if not (0.0 < pp <= 1.0):
+            raise ValueError("top_p should be in (0, 1] (1 or None: off), got %r" % (top_p,))
+        if T == 1.0 and k == 0 and pp == 1.0:
+            return None
+        if mode != "sampling":
+            raise ValueError("temperature / top_k / top_p apply to mode sampling only, got mode %s" % mode)
+        if self.out_channels != self.cfg.n_quantize:
+            raise ValueError("temperature / top_k / top_p are not defined for the mixture-of-logistics head")
+        return _lib.WnSampling(1.0 / T, k, pp)   # (1.0 / T in double, rounded to float by the structure)
+
     def decode(self, x, h, n_samples_list, mode="argmax", chunk=4096, return_logits=False, progress=None, layered=None,
-               prefill="parallel", prefill_batch=32, log_scale_min=-7.0):
+               prefill="parallel", prefill_batch=32, log_scale_min=-7.0, temperature=1.0, top_k=None, top_p=None):
         """See ``_decode``.  ``layered="granules"``: the any-size path with its persistent launches handing their vectors over
         as 8-byte granules everywhere (csrc/wn_dlp.hip, wn_dlpm.hip) instead of plain vectors + flags where csrc/wn_dlpf.hip
         covers the model -- an A/B and test knob (the mode bit WN_DECODE_GRANULES of every library call of this decode).
@@ -1119,7 +1140,13 @@ class WaveNetEngine(object):
         A persistent launch that gives up waiting between its workgroups (they were not all resident: another kernel held
         compute units) raises ``WnDecodeTimeout`` inside; the decode is then done again by layer-wise launches (HIP kernels
         as well; a warning says so) -- context, aux features and, in the sampling mode, the uniform draws are the same, so
-        the tokens are those the persistent launch would have produced."""
+        the tokens are those the persistent launch would have produced.
+
+        ``temperature``, ``top_k``, ``top_p`` (mode "sampling", softmax head): the logits are multiplied by 1 / temperature, cut to
+        the top_k largest (ties kept), then to the smallest set of largest classes holding top_p of the probability (ties kept),
+        and the draw is made among what is left -- inside the decode kernels (csrc/wn_sample.h); one setting per
+        call, carried through the groups of a large batch and the fall-back.  The defaults are the plain sampling decode."""
+        sampling = self.sampling_setting(mode, temperature, top_k, top_p)
         granules = layered == "granules"
         lay = True if granules else layered
         mbits = _lib.DECODE_GRANULES if granules else 0
@@ -1129,18 +1156,18 @@ class WaveNetEngine(object):
             draws = torch.rand((x.size(0), x.size(1) + n_pad + int(max(n_samples_list))), dtype=torch.float32, device=self.device)
         try:
             return self._decode_groups(x, h, n_samples_list, mode, chunk, return_logits, progress, lay, prefill, prefill_batch,
-                                       log_scale_min, mbits, draws)
+                                       log_scale_min, mbits, draws, sampling)
         except _lib.WnDecodeTimeout as e:
             warnings.warn("%s -- decoding again by layer-wise launches" % e, RuntimeWarning)
             return self._decode_groups(x, h, n_samples_list, mode, chunk, return_logits, progress, "launches", prefill,
-                                       prefill_batch, log_scale_min, 0, draws)
+                                       prefill_batch, log_scale_min, 0, draws, sampling)
 
     def _decode_groups(self, x, h, n_samples_list, mode, chunk, return_logits, progress, lay, prefill, prefill_batch, log_scale_min,
-                       mbits, draws):
+                       mbits, draws, sampling=None):
         groups = self._persistent_groups(x.size(0), lay, mode, mbits)
         if groups is None:
             return self._decode(x, h, n_samples_list, mode, chunk, return_logits, progress, lay, prefill, prefill_batch,
-                                log_scale_min, _uniforms=draws, _mbits=mbits)
+                                log_scale_min, _uniforms=draws, _mbits=mbits, _sampling=sampling)
         # More utterances than ONE persistent launch takes (64 with the flag hand-off: four column blocks = 256 workgroups), up to
         # two launches' worth: the batch goes through it in two groups -- the utterances are independent.
         T0 = x.size(1)
@@ -1153,7 +1180,7 @@ class WaveNetEngine(object):
             u = None if draws is None else draws[g0:g1, :T0 + n_pad + int(max(ns))].contiguous()
             prog = None if progress is None else (lambda d, n, base=done: progress(base + d, total))   # steps over all groups
             r = self._decode(x[g0:g1].contiguous(), h[g0:g1].contiguous(), ns, mode, chunk, return_logits, prog, lay, prefill,
-                             prefill_batch, log_scale_min, _uniforms=u, _mbits=mbits)
+                             prefill_batch, log_scale_min, _uniforms=u, _mbits=mbits, _sampling=sampling)
             done += int(max(ns))
             toks += r[0] if return_logits else r
             if return_logits:
@@ -1196,7 +1223,7 @@ class WaveNetEngine(object):
         return [(g0, min(g0 + gs, B)) for g0 in range(0, B, gs)]
 
     def _decode(self, x, h, n_samples_list, mode="argmax", chunk=4096, return_logits=False, progress=None, layered=None,
-                prefill="parallel", prefill_batch=32, log_scale_min=-7.0, _uniforms=None, _mbits=0):
+                prefill="parallel", prefill_batch=32, log_scale_min=-7.0, _uniforms=None, _mbits=0, _sampling=None):
         """Queue-based sample-by-sample generation on the HIP decode kernel.
 
         x (B,T0) int64 context, h (B, n_aux, frames | samples) aux features covering T0 + max(n)
@@ -1323,11 +1350,13 @@ class WaveNetEngine(object):
             else:
                 Fw, pad_w = F, n_pad
             if layered:
-                rc = self.lib.wn_decode_layered_steps(cfg, B, _ptr(self.flat_params), _ptr(G), Fw, pad_w, _ptr(samples), Ttot,
-                                                      _ptr(t_forced), _ptr(t_end), p, p1, _ptr(state), state.numel(),
-                                                      _ptr(uniforms), _ptr(logits),
-                                                      {"argmax": 0, "sampling": 1, "mol": 2}[mode] | mbits,
-                                                      _ptr(wave), float(log_scale_min), st)
+                largs = (cfg, B, _ptr(self.flat_params), _ptr(G), Fw, pad_w, _ptr(samples), Ttot, _ptr(t_forced), _ptr(t_end), p, p1,
+                         _ptr(state), state.numel(), _ptr(uniforms), _ptr(logits), {"argmax": 0, "sampling": 1, "mol": 2}[mode] | mbits,
+                         _ptr(wave), float(log_scale_min))
+                if _sampling is None:   # the identity setting IS the plain call
+                    rc = self.lib.wn_decode_layered_steps(*(largs + (st,)))
+                else:
+                    rc = self.lib.wn_decode_layered_steps_filtered(*(largs + (ctypes.byref(_sampling), st)))
                 if rc == 4 and eoff >= 0:   # the persistent grid would not be resident at once (the device changed under a cached
                     # layout, a partitioned GPU): the same fall-back as a time-out
                     raise _lib.WnDecodeTimeout("the persistent decode launch was refused: its %s" % self.lib.wn_last_error().decode())
@@ -1338,10 +1367,13 @@ class WaveNetEngine(object):
                     raise _lib.WnDecodeTimeout("the persistent decode launch timed out waiting between its workgroups (not all "
                                                "of them were resident at once: another kernel on the device?)")
             else:
-                rc = self.lib.wn_decode_steps(cfg, B, _ptr(self.flat_params), _ptr(wpack), _ptr(G), Fw, pad_w, _ptr(samples),
-                                              Ttot, _ptr(t_forced), _ptr(t_end), p, p1, _ptr(state), _ptr(uniforms),
-                                              _ptr(logits), {"argmax": 0, "sampling": 1, "mol": 2}[mode], _ptr(wave),
-                                              float(log_scale_min), st)
+                sargs = (cfg, B, _ptr(self.flat_params), _ptr(wpack), _ptr(G), Fw, pad_w, _ptr(samples), Ttot, _ptr(t_forced),
+                         _ptr(t_end), p, p1, _ptr(state), _ptr(uniforms), _ptr(logits), {"argmax": 0, "sampling": 1, "mol": 2}[mode],
+                         _ptr(wave), float(log_scale_min))
+                if _sampling is None:
+                    rc = self.lib.wn_decode_steps(*(sargs + (st,)))
+                else:
+                    rc = self.lib.wn_decode_steps_filtered(*(sargs + (ctypes.byref(_sampling), st)))
                 self.lib.check(rc, "wn_decode_steps")
             p = p1
             if progress is not None:

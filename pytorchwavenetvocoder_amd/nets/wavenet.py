@@ -88,6 +88,23 @@ def decode_mu_law(y, mu=256):
     return x
 
 
+def truncated_probs(logits, inv_temperature, top_k, top_p):
+    """Class probabilities of a temperature / top-k / top-p draw from ``logits`` (Q,): the set rule of the decode kernels
+    (csrc/wn_sample.h) in torch.  s = fp32(logits * inv_temperature); A = the classes whose s is at least the
+    k-th largest (ties kept; k = 0 or k >= Q: all); B = the classes of A whose s is at least tau, the largest value whose upper
+    set holds top_p of A's probability (ties kept); the result is the softmax of s over B and 0 elsewhere."""
+    s = logits.float() * torch.tensor(inv_temperature, dtype=torch.float32, device=logits.device)
+    keep = torch.ones_like(s, dtype=torch.bool)
+    if 0 < top_k < s.numel():
+        keep = s >= torch.topk(s, int(top_k)).values[-1]
+    e = torch.where(keep, torch.exp((s - s.max()).double()), torch.zeros((), dtype=torch.float64, device=s.device))
+    if top_p < 1.0:
+        mass = (e[None, :] * (s[None, :] >= s[:, None])).sum(dim=1)   # mass[q] = probability of A's classes with s >= s_q
+        ok = keep & (mass >= top_p * e.sum())
+        e = torch.where(s >= s[ok].max(), e, torch.zeros_like(e))
+    return (e / e.sum()).float()
+
+
 def initialize(m):
     """Xavier init for Conv1d, ones/zeros for ConvTranspose2d (reference wavenet.py:50-63).
 
@@ -729,7 +746,7 @@ class WaveNet(nn.Module):
             object.__setattr__(self, "_gen_eng", eng)
         return eng
 
-    def generate(self, x, h, n_samples, intervals=None, mode="sampling"):
+    def generate(self, x, h, n_samples, intervals=None, mode="sampling", temperature=1.0, top_k=None, top_p=None):
         """Naive generation (reference wavenet.py:243-307): every new sample is the last output of
         a full forward over the newest ``receptive_field`` samples (activations left of the window
         count as zero, which is what distinguishes it from ``fast_generate``).  Every window runs
@@ -741,6 +758,7 @@ class WaveNet(nn.Module):
             n_samples (int): Number of samples to be generated.
             intervals (int): Log interval.
             mode (str): "sampling" or "argmax".
+            temperature, top_k, top_p: as in ``fast_generate``; the same set rule, applied in torch before the draw.
 
         Returns:
             ndarray: Generated quantized waveform (n_samples,).
@@ -748,6 +766,7 @@ class WaveNet(nn.Module):
         if mode not in ("sampling", "argmax"):
             logging.error("mode should be sampling or argmax")
             sys.exit(1)
+        setting = self._sampling_setting(mode, temperature, top_k, top_p)
         if self.n_mixture > 0:
             # the 3 * n_mixture outputs are mixture parameters, not class logits: a softmax / argmax over them would
             # return meaningless tokens.  The queue-based generators draw from the mixture on the device.
@@ -770,7 +789,8 @@ class WaveNet(nn.Module):
                 if mode == "argmax":
                     tokens[0, end] = logits.argmax()
                 else:
-                    tokens[0, end] = torch.distributions.Categorical(F.softmax(logits, dim=0)).sample()
+                    probs = F.softmax(logits, dim=0) if setting is None else truncated_probs(logits, *setting)
+                    tokens[0, end] = torch.distributions.Categorical(probs).sample()
                 if intervals is not None and (i + 1) % intervals == 0:
                     per = (time.time() - tick) / (i + 1 - done_at_tick)
                     logging.info("%d/%d estimated time = %.3f sec (%.3f sec / sample)" % (
@@ -778,11 +798,25 @@ class WaveNet(nn.Module):
                     tick, done_at_tick = time.time(), i + 1
             return tokens[0, n_ctx:].cpu().numpy()
 
-    def _decode(self, x, h, n_samples_list, intervals, mode):
+    def _sampling_setting(self, mode, temperature, top_k, top_p):
+        """(inverse temperature, top_k, top_p) of a generation call, None for the identity; ValueError for values out of range,
+        for parameters other than the identity with mode "argmax" and with the mixture-of-logistics head."""
+        if self.n_mixture > 0:
+            try:
+                s = self.engine.sampling_setting("argmax", temperature, top_k, top_p)
+            except ValueError:
+                raise ValueError("temperature / top_k / top_p should be a valid setting, and are not defined for the "
+                                 "mixture-of-logistics head (n_mixture = %d)" % self.n_mixture)
+            return None
+        s = self.engine.sampling_setting(mode, temperature, top_k, top_p)
+        return None if s is None else (s.inv_temperature, s.top_k, s.top_p)
+
+    def _decode(self, x, h, n_samples_list, intervals, mode, temperature=1.0, top_k=None, top_p=None):
         """Run the HIP decode kernel (csrc/wn_decode.hip); returns per-utterance LongTensors."""
         if mode not in ("sampling", "argmax"):
             logging.error("mode should be sampling or argmax")
             sys.exit(1)
+        self._sampling_setting(mode, temperature, top_k, top_p)
         if self.n_mixture > 0:  # the mixture head has no argmax: both modes draw from the mixture
             mode = "mol"
         start = [time.time(), 0]
@@ -797,9 +831,9 @@ class WaveNet(nn.Module):
         with torch.no_grad():
             return self.engine.decode(x, h, list(n_samples_list), mode=mode,
                                       chunk=intervals if intervals else 4096, progress=progress,
-                                      log_scale_min=self.log_scale_min)
+                                      log_scale_min=self.log_scale_min, temperature=temperature, top_k=top_k, top_p=top_p)
 
-    def fast_generate(self, x, h, n_samples, intervals=None, mode="sampling"):
+    def fast_generate(self, x, h, n_samples, intervals=None, mode="sampling", temperature=1.0, top_k=None, top_p=None):
         """Generate a waveform with the queue algorithm (reference wavenet.py:309-395) on the HIP
         decode path: one persistent workgroup per utterance for the model sizes the decode kernel
         covers, layer-wise launches on [channels x batch] operands for any other size; the context
@@ -813,13 +847,18 @@ class WaveNet(nn.Module):
             n_samples (int): Number of samples to be generated.
             intervals (int): Log interval.
             mode (str): "sampling" or "argmax".
+            temperature (float): sampling temperature T > 0: the logits are multiplied by 1 / T (mode "sampling").
+            top_k (int): keep the k most probable classes (ties at the k-th kept); 0 or None: off.
+            top_p (float): keep the smallest set of most probable classes holding this probability mass (ties kept), taken
+                after top_k; 1 or None: off.  The defaults are the reference's plain draw; the choice is made inside the
+                decode kernels (csrc/wn_sample.h).
 
         Returns:
             ndarray: Generated quantized waveform (n_samples,).
         """
-        return self._decode(x, h, [n_samples], intervals, mode)[0].cpu().numpy()
+        return self._decode(x, h, [n_samples], intervals, mode, temperature, top_k, top_p)[0].cpu().numpy()
 
-    def batch_fast_generate(self, x, h, n_samples_list, intervals=None, mode="sampling"):
+    def batch_fast_generate(self, x, h, n_samples_list, intervals=None, mode="sampling", temperature=1.0, top_k=None, top_p=None):
         """Batched queue-algorithm generation (reference wavenet.py:397-511): one workgroup per
         utterance, each stops at its own length.  Returns the list of generated waveforms in order
         of completion (shortest first), like the reference.
@@ -830,7 +869,8 @@ class WaveNet(nn.Module):
             n_samples_list (list): List of number of samples to be generated (B,).
             intervals (int): Log interval.
             mode (str): "sampling" or "argmax".
+            temperature, top_k, top_p: as in ``fast_generate``, one setting for the whole batch.
         """
         order = sorted(range(len(n_samples_list)), key=lambda i: (n_samples_list[i], i))
-        toks = self._decode(x, h, n_samples_list, intervals, mode)
+        toks = self._decode(x, h, n_samples_list, intervals, mode, temperature, top_k, top_p)
         return [toks[i].cpu().numpy() for i in order]
