@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define WN_ABI_VERSION 21
+#define WN_ABI_VERSION 22
 
 /* Same fields as the constructor WaveNet(n_quantize, n_aux, n_resch, n_skipch, dilation_depth,
  * dilation_repeat, kernel_size, upsampling_factor)  -- reference wavenet.py:172-173. */
@@ -664,6 +664,44 @@ int wn_lamb_step(float* params, const float* grads, float* exp_avg, float* exp_a
                  int n_ranges, int64_t n_live, int64_t step, const WnAdamGroup* groups, int n_groups, float beta1, float beta2,
                  float max_trust, const WnOptState* state, double ema_decay, int ema_warmup, float* scratch, float* stats,
                  void* stream);
+
+/* Low-rank adapters over the flat buffers (since ABI v22): W = W0 + scale B A for a table of matrices, as two fused operations.
+ * An entry names a row-major [rows, cols] matrix W at w_off of the MODEL's flat buffers (a conv weight (out, in, K) is
+ * [out, in K]) and its factors in the ADAPTER's flat buffer: A [rank, cols] at a_off, B [rows, rank] at b_off.  Offsets are in
+ * elements and need no alignment beyond the element's; the kernels use 16-byte accesses on the runs of a row whose addresses allow
+ * it, with a scalar head and tail.
+ *
+ * wn_lora_table (host only, no launch) checks the entries -- 1 <= rank <= WN_LORA_MAX_RANK, rank <= min(rows, cols), a finite
+ * scale (as a float), every range inside its buffer (n_model / n_adapter elements), no two ranges overlapping in either buffer --
+ * and lays out the blocks: 64 x 64 tiles of every matrix and chunks of 256 adapter-gradient elements, so the grids and every
+ * summation order are functions of the entries alone, never of the device: data-parallel ranks derive the same bits.  Returns the
+ * int64 words the table takes, and writes them when table != NULL and table_words is at least that (call it with NULL first);
+ * -1 on an error.  The calls below take the host table AND a device copy of the same words.
+ * wn_lora_scratch_floats(table): floats of scratch wn_lora_project needs for a HOST table; -1 when it is none.
+ *
+ *   wn_lora_merge    params[i] = fmaf(scale, acc, base[i]) with acc = 0, acc = fmaf(B[o,k], A[k,c], acc) for k = 0 .. rank - 1, on
+ *                    every element of every entry: ONE launch.  base and params hold n_model elements and must not overlap;
+ *                    an element outside every entry is neither read nor written in any buffer.
+ *   wn_lora_project  adapter_grads: dA[k,c] = scale sum_o B[o,k] g[o,c] at a_off, dB[o,k] = scale sum_c g[o,c] A[k,c] at b_off,
+ *                    g the entry's matrix in `grads`.  fp32 fma chains inside a tile (rows / columns ascending), the tiles'
+ *                    shares added in tile order, one multiplication by scale; no atomics.  TWO launches: one over the tiles of
+ *                    g -- each read from memory once -- that writes the shares into scratch, one that sums them.  grads and
+ *                    adapter are only read; adapter_grads outside the ranges of A and B is not written.
+ * Errors (wn_last_error): NULL or misaligned pointers (4 bytes; the tables 8), a table wn_lora_table did not write or that does
+ * not fit n_model / n_adapter, scratch_floats below wn_lora_scratch_floats, base overlapping params, adapter overlapping
+ * adapter_grads. */
+#define WN_LORA_MAX_RANK 64
+typedef struct WnLoraEntry {
+    int64_t w_off, rows, cols, rank, a_off, b_off;
+    double scale; /* alpha / rank; used as a float */
+} WnLoraEntry;
+int64_t wn_lora_table(const WnLoraEntry* entries, int n_entries, int64_t n_model, int64_t n_adapter, int64_t* table,
+                      int64_t table_words);
+int64_t wn_lora_scratch_floats(const int64_t* table);
+int wn_lora_merge(const float* base, float* params, int64_t n_model, const float* adapter, int64_t n_adapter, const int64_t* table,
+                  const int64_t* dev_table, void* stream);
+int wn_lora_project(const float* grads, int64_t n_model, const float* adapter, float* adapter_grads, int64_t n_adapter,
+                    const int64_t* table, const int64_t* dev_table, float* scratch, int64_t scratch_floats, void* stream);
 
 /* ---- op-level entry points (used by the composite calls above; exported for parity tests) ---- */
 

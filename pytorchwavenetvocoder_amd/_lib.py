@@ -83,6 +83,15 @@ class WnAdamGroup(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_float), ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float), ("decoupled", ctypes.c_int32)]
 
 
+class WnLoraEntry(ctypes.Structure):
+    """Mirror of ``struct WnLoraEntry`` (include/wavenet_hip.h, ABI v22): one adapted matrix of a low-rank adapter table."""
+    _fields_ = [("w_off", ctypes.c_int64), ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("rank", ctypes.c_int64),
+                ("a_off", ctypes.c_int64), ("b_off", ctypes.c_int64), ("scale", ctypes.c_double)]
+
+
+LORA_MAX_RANK = 64
+
+
 class WnGroupScalars(ctypes.Structure):
     """Mirror of ``struct WnGroupScalars``: what the Adam launch reads per group (the guarded path's device block holds
     ``MAX_PARAM_GROUPS`` of them)."""
@@ -145,7 +154,7 @@ def flag_dw_flush(n):
     return (int(n) & 0xff) << 8
 
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 # every symbol include/wavenet_hip.h declares
 EXPORTS = [
@@ -167,6 +176,7 @@ EXPORTS = [
     "wn_softmax_cew_scratch_floats", "wn_softmax_cew_loss",
     "wn_tensor_table", "wn_tensor_blocks", "wn_lamb_scratch_floats", "wn_tensor_sumsq", "wn_lamb_step",
     "wn_decode_steps_filtered", "wn_decode_layered_steps_filtered",
+    "wn_lora_table", "wn_lora_scratch_floats", "wn_lora_merge", "wn_lora_project",
 ]
 
 
@@ -300,6 +310,15 @@ class WnLibrary(object):
                                                ctypes.POINTER(WnSampling), vp]
         L.wn_decode_layered_steps_filtered.argtypes = [cfgp, i, vp, vp, i, i, vp, i64, vp, vp, i, i, vp, i64, vp, vp, i, vp, f,
                                                        ctypes.POINTER(WnSampling), vp]
+        # low-rank adapters (ABI v22): (host WnLoraEntry array, n_entries, n_model, n_adapter, host table | NULL, table_words) -> words;
+        # merge (base, params, n_model, adapter, n_adapter, host table, device table, stream); project (grads, n_model, adapter,
+        # adapter_grads, n_adapter, host table, device table, scratch, scratch_floats, stream)
+        L.wn_lora_table.argtypes = [vp, i, i64, i64, vp, i64]
+        L.wn_lora_table.restype = i64
+        L.wn_lora_scratch_floats.argtypes = [vp]
+        L.wn_lora_scratch_floats.restype = i64
+        L.wn_lora_merge.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp]
+        L.wn_lora_project.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, i64, vp]
         L.wn_decode_ctx_aux.argtypes = [cfgp, i, i, i, i, i, vp, vp, vp, vp]
         L.wn_decode_prefill_workspace_bytes.argtypes = [cfgp, i, i]
         L.wn_decode_prefill_workspace_bytes.restype = ctypes.c_size_t

@@ -62,7 +62,21 @@ def get_parser():
     parser.add_argument("--top_p", default=1.0, type=float,
                         help="draw among the smallest set of most probable classes holding this probability mass, taken "
                              "after --top_k (1: off)")
+    # extension: low-rank adapters of train.py --adapter_rank on top of --checkpoint, the base they were trained on
+    parser.add_argument("--adapter", default=None, type=str,
+                        help="a checkpoint of train.py --adapter_rank (its \"adapter\" entry): the adapters are merged into the "
+                             "weights of --checkpoint once, then generation runs as ever")
     return parser
+
+
+def attach_adapter(model, path):
+    """Merge the adapters of ``path`` into ``model`` (already on its device): one ``lora_merge`` launch; the model is a plain
+    model afterwards.  KeyError / ValueError with the reason when the file holds none or they do not fit the model."""
+    from pytorchwavenetvocoder_amd.adapters import LowRankAdapters
+    checkpoint = torch.load(path, map_location="cpu", weights_only=False)
+    if "adapter" not in checkpoint:
+        raise KeyError("--adapter: %s holds no \"adapter\" entry (train.py --adapter_rank writes it)." % path)
+    LowRankAdapters.from_state_dict(model, checkpoint["adapter"]).fold()
 
 
 def checkpoint_weights(path, which="model"):
@@ -164,6 +178,9 @@ def _decode_files(gpu, feat_list, args, config, mean, scale):
     model.load_state_dict(checkpoint_weights(args.checkpoint, getattr(args, "weights", "model")))
     model.eval()
     model.to(device)
+    if getattr(args, "adapter", None):
+        attach_adapter(model, args.adapter)
+        logging.info("adapters from %s merged into the weights." % args.adapter)
     generator = decode_generator(
         feat_list, batch_size=args.batch_size, feature_type=config.feature_type,
         wav_transform=lambda x: encode_mu_law(x, config.n_quantize),
@@ -215,6 +232,10 @@ def main(argv=None):
             checkpoint_weights(args.checkpoint, "ema")
         except KeyError as e:
             logging.error(e.args[0])
+            sys.exit(1)
+    if args.adapter:   # fail here, with the reason, not in a worker process
+        if not os.path.isfile(args.adapter) or "adapter" not in torch.load(args.adapter, map_location="cpu", weights_only=False):
+            logging.error("--adapter %s: no such file, or it holds no \"adapter\" entry (train.py --adapter_rank writes it)." % args.adapter)
             sys.exit(1)
     if os.path.isdir(args.feats):
         feat_list = sorted(find_files(args.feats, "*.h5"))

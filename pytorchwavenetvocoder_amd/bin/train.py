@@ -27,6 +27,7 @@ import time
 import numpy as np
 import torch
 
+from pytorchwavenetvocoder_amd.adapters import AdapterAdam, LowRankAdapters
 from pytorchwavenetvocoder_amd.nets import WaveNet, encode_mu_law, initialize
 from pytorchwavenetvocoder_amd.utils import background, extend_time, find_files, make_feat_transform, read_hdf5, read_txt
 
@@ -503,11 +504,14 @@ def dev_loss(model, dev, rank, world, device):
     return (nll / npos if npos > 0 else float("nan")), len(wav_list), int(npos)
 
 
-def save_checkpoint(checkpoint_dir, model, optimizer, iterations, dev=None):
+def save_checkpoint(checkpoint_dir, model, optimizer, iterations, dev=None, adapters=None):
     """``checkpoint-%d.pkl`` = {"model", "optimizer", "iterations"} (reference train.py:315-332); with a held-out set
     (--dev_waveforms) also "dev" = {"best_loss", "best_iterations"}; with a moving average of the weights (--ema_decay) also
-    "ema" = the averaged weights under the keys of "model"."""
+    "ema" = the averaged weights under the keys of "model".  With low-rank adapters (--adapter_rank) "adapter" takes the place of
+    "model": the base stays in the --pretrained file."""
     checkpoint = {"model": model.state_dict(), "optimizer": optimizer.state_dict(), "iterations": iterations}
+    if adapters is not None:
+        checkpoint = {"adapter": adapters.state_dict(), "optimizer": optimizer.state_dict(), "iterations": iterations}
     if dev is not None:
         checkpoint["dev"] = dict(dev)
     if getattr(optimizer, "ema_decay", None) is not None:
@@ -639,7 +643,40 @@ def get_parser():
     parser.add_argument("--loss_normalize", default="weights", type=str,
                         help="weights: divide the weighted loss by the sum of the targets' weights (torch's mean); positions: by "
                              "the number of loss positions (exact over ranks, --accum_steps and uneven batches)")
+    # extension (not reference flags): low-rank adapters on a pretrained model: one base, a small file per voice
+    parser.add_argument("--adapter_rank", default=0, type=int,
+                        help="train low-rank adapters W0 + (alpha / rank) B A of this rank on the --pretrained model instead of its "
+                             "weights (0: off); checkpoints then hold \"adapter\" and no \"model\"")
+    parser.add_argument("--adapter_alpha", default=None, type=float, help="adapter scale numerator (default: the rank, scale 1)")
+    parser.add_argument("--adapter_targets", default=None, type=str,
+                        help="regular expression (re.search on the parameter names) of the adapted weights; default: the dilated, "
+                             "skip and residual convolutions of every layer")
+    parser.add_argument("--adapter_save_merged", default=False, type=strtobool,
+                        help="checkpoint-final.pkl also holds \"model\", the merged weights, for tools that know no adapters")
     return parser
+
+
+def check_adapter_args(args):
+    """The refusals of --adapter_rank, made while main() looks at the arguments.  ValueError with the reason."""
+    rank = int(getattr(args, "adapter_rank", 0) or 0)
+    if rank < 0:
+        raise ValueError("--adapter_rank %d: a positive rank, or 0 for none." % rank)
+    if rank == 0:
+        for flag in ("adapter_alpha", "adapter_targets", "adapter_save_merged"):
+            if getattr(args, flag, None):
+                raise ValueError("--%s needs --adapter_rank." % flag)
+        if args.pretrained and args.resume:
+            raise ValueError("--pretrained starts iteration 0 from a checkpoint's weights, --resume continues a run: give one of "
+                             "them (both only with --adapter_rank: the base from one file, the adapters from the other).")
+        return
+    if not args.pretrained:
+        raise ValueError("--adapter_rank needs --pretrained: adapters are trained on a trained model.")
+    for flag, on in (("--freeze", bool(args.freeze)), ("--train_only", bool(args.train_only)),
+                     ("--ema_decay", float(args.ema_decay or 0.0) > 0.0), ("--param_group", bool(args.param_group)),
+                     ("--layer_adaptation", bool(args.layer_adaptation))):
+        if on:
+            raise ValueError("--adapter_rank cannot go with %s: the adapters are the trainable set, and the weight average, "
+                             "parameter groups and layer adaptation are not defined for them." % flag)
 
 
 def check_criterion_args(args):
@@ -880,12 +917,14 @@ def _worker(rank, world, args, port):
     layer_adaptation = bool(getattr(args, "layer_adaptation", False))
     max_trust_ratio = float(getattr(args, "max_trust_ratio", 0.0) or 0.0)
     lamb = {"layer_adaptation": True, "max_trust_ratio": max_trust_ratio if max_trust_ratio > 0.0 else None} if layer_adaptation else {}
+    adapter_rank, adapters = int(getattr(args, "adapter_rank", 0) or 0), None
     try:
-        optimizer = FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay,
+        optimizer = None if adapter_rank > 0 else \
+                    FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay,
                               max_grad_norm=max_grad_norm if max_grad_norm > 0.0 else None,
                               skip_nonfinite=bool(getattr(args, "skip_nonfinite_steps", False)),
                               ema_decay=ema_decay if ema_decay > 0.0 else None, ema_warmup=bool(getattr(args, "ema_warmup", True)),
-                              **dict({"groups": groups} if groups else {}, **lamb))
+                              **dict({"groups": groups} if groups else {}, **lamb))   # noqa: E127
     except ValueError as err:
         if not groups:
             raise
@@ -896,7 +935,7 @@ def _worker(rank, world, args, port):
             "%g" % max_trust_ratio if max_trust_ratio > 0.0 else "none",
             "".join("; group %d (%r) adapt=%s" % (i, groups[i - 1][0], g["layer_adaptation"])
                     for i, g in enumerate(optimizer.param_groups) if "layer_adaptation" in g)))
-    for i, g in enumerate(optimizer.param_groups if groups else []):
+    for i, g in enumerate(optimizer.param_groups if groups and optimizer is not None else []):
         logging.info("parameter group %d (%s): lr=%g weight_decay=%g eps=%g decoupled=%s, %d tensors, %d elements" % (
             i, "default" if i == 0 else repr(groups[i - 1][0]), g["lr"], g["weight_decay"], g["eps"],
             bool(g["decoupled_weight_decay"]), len(g["params"]), sum(p.numel() for p in g["params"])))
@@ -904,6 +943,18 @@ def _worker(rank, world, args, port):
     if pretrained:   # (main() has refused --pretrained beside --resume and --freeze beside --train_only)
         model.load_state_dict(torch.load(pretrained, map_location=lambda storage, loc: storage, weights_only=False)["model"])
         logging.info("model weights from %s (iteration 0, fresh optimizer)." % pretrained)
+    if adapter_rank > 0:   # (main() has made the refusals) the adapters become the trainable set; the base stays as loaded
+        try:
+            adapters = LowRankAdapters(model, rank=adapter_rank, alpha=getattr(args, "adapter_alpha", None),
+                                       targets=getattr(args, "adapter_targets", None) or None, seed=args.seed)
+        except (ValueError, re.error) as err:
+            logging.error("--adapter_rank / --adapter_targets: %s" % err)
+            sys.exit(1)
+        optimizer = AdapterAdam(adapters, lr=args.lr, weight_decay=args.weight_decay,
+                                max_grad_norm=max_grad_norm if max_grad_norm > 0.0 else None,
+                                skip_nonfinite=bool(getattr(args, "skip_nonfinite_steps", False)))
+        logging.info("low-rank adapters: rank %d, alpha %g, %d tensors, %d adapter parameters (the model has %d)" % (
+            adapters.rank, adapters.alpha, len(adapters.entries), adapters.n_adapter, sum(p.numel() for p in model.parameters())))
     if freeze or train_only:
         if freeze:
             model.freeze(freeze)
@@ -916,7 +967,16 @@ def _worker(rank, world, args, port):
     if args.resume is not None and len(args.resume) != 0:
         checkpoint = torch.load(args.resume, map_location=lambda storage, loc: storage, weights_only=False)
         iterations = checkpoint["iterations"]
-        model.load_state_dict(checkpoint["model"])
+        if adapters is not None:   # the base came from --pretrained, the adapters and their optimizer come from this file
+            try:
+                if "adapter" not in checkpoint:
+                    raise ValueError("%s holds no \"adapter\" entry (it was not written by a run with --adapter_rank)" % args.resume)
+                adapters.load_state_dict(checkpoint["adapter"])
+            except ValueError as err:
+                logging.error("--resume: %s" % err)
+                sys.exit(1)
+        else:
+            model.load_state_dict(checkpoint["model"])
         optimizer.load_state_dict(checkpoint["optimizer"])
         if dev is not None:
             dev_best = dev_best_from_checkpoint(checkpoint)
@@ -932,6 +992,8 @@ def _worker(rank, world, args, port):
     reducer = GradientReducer(model)
     if world > 1:
         dist.broadcast(model.engine.flat_params, src=0)
+    if adapters is not None:
+        adapters.merge()   # the model holds the merged weights from here on (fresh adapters: the pretrained ones, B = 0)
 
     loss_acc = torch.zeros(1, device=device)
     # --label_smoothing / --class_weights: the weighted criterion (main() has made the refusals); its plain cross-entropy part is logged
@@ -997,6 +1059,8 @@ def _worker(rank, world, args, port):
             batch_loss = reducer.loss_and_backward(batch_x, batch_h, batch_t, y=item[2] if args.n_mixture > 0 else None,
                                                    grad_scale=share, **ragged)
             if k == accum_steps - 1:
+                if adapters is not None:   # behind the reduction: every rank projects the same reduced dW
+                    adapters.project()
                 optimizer.step()
             loss_acc += batch_loss.detach() * (share * world)
             if distilling:
@@ -1068,6 +1132,10 @@ def _worker(rank, world, args, port):
                 dev_best = (loss_dev, i + 1)
                 if is_main:
                     best = {"model": model.state_dict(), "iterations": i + 1, "dev_loss": loss_dev}
+                    if adapters is not None:   # what was scored is base + adapters: the small file, the merged weights on request
+                        best = {"adapter": adapters.state_dict(), "iterations": i + 1, "dev_loss": loss_dev}
+                        if getattr(args, "adapter_save_merged", False):
+                            best["model"] = model.state_dict()
                     if optimizer.ema_decay is not None:   # "model" = what was scored: the reference's decode tool reads it as it is
                         best["model"] = optimizer.ema_state_dict()
                         best["ema_decay"] = ema_decay
@@ -1075,13 +1143,17 @@ def _worker(rank, world, args, port):
                     logging.info("best checkpoint created (dev loss %.6f)." % loss_dev)
         if (i + 1) % args.checkpoint_interval == 0 and is_main:
             if dev is None:
-                save_checkpoint(args.expdir, model, optimizer, i + 1)
+                save_checkpoint(args.expdir, model, optimizer, i + 1, adapters=adapters)
             else:
-                save_checkpoint(args.expdir, model, optimizer, i + 1, dev=dev_best_state(dev_best))
+                save_checkpoint(args.expdir, model, optimizer, i + 1, dev=dev_best_state(dev_best), adapters=adapters)
 
     generator.close()   # stop the producer thread before the interpreter tears the runtime down under it
     if is_main:
         final = {"model": model.state_dict()}
+        if adapters is not None:
+            final = {"adapter": adapters.state_dict()}
+            if getattr(args, "adapter_save_merged", False):
+                final["model"] = model.state_dict()
         if optimizer.ema_decay is not None:
             final["ema"] = optimizer.ema_state_dict()
         torch.save(final, args.expdir + "/checkpoint-final.pkl")
@@ -1115,10 +1187,8 @@ def main(argv=None):
     if not args.layer_adaptation and any("layer_adaptation" in parse_param_group(spec)[1] for spec in args.param_group or []):
         logging.error("--param_group ...:adapt= needs --layer_adaptation true.")
         sys.exit(1)
-    if args.pretrained and args.resume:
-        logging.error("--pretrained starts iteration 0 from a checkpoint's weights, --resume continues a run: give one of them.")
-        sys.exit(1)
     try:
+        check_adapter_args(args)
         check_teacher_args(args)
         check_criterion_args(args)
     except ValueError as err:

@@ -14,8 +14,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 # the ONE list of what the library is made of: the emulator build (tests/emu/build_emu.py) and the instrumented / variant builds
 # under tools/ import it (each keeps its own flags); tests/test_source_lists.py holds it against the directory
-SOURCES = ["wn_gemm.hip", "wn_gemm6.hip", "wn_elem.hip", "wn_distill.hip", "wn_cew.hip", "wn_fused.hip", "wn_decode.hip", "wn_dlp.hip", "wn_dlpm.hip", "wn_dlpf.hip", "wn_prof.hip", "wn_api.hip"]
-HEADERS = ["wn_api_backward.inl", "wn_auxdh.inl", "wn_optim.inl", "wn_api_ops.inl", "wn_api_decode.inl", "wn_device.h", "wn_gemm.h", "wn_gemm6.h", "wn_elem.h", "wn_distill.h", "wn_cew.h", "wn_optim.h", "wn_fused.h", "wn_decode.h", "wn_dlp.h", "wn_sample.h", "wn_prof.h", "../../include/wavenet_hip.h", "../../include/wavenet_hip_gemm.h"]
+SOURCES = ["wn_gemm.hip", "wn_gemm6.hip", "wn_elem.hip", "wn_distill.hip", "wn_cew.hip", "wn_lora.hip", "wn_fused.hip", "wn_decode.hip", "wn_dlp.hip", "wn_dlpm.hip", "wn_dlpf.hip", "wn_prof.hip", "wn_api.hip"]
+HEADERS = ["wn_api_backward.inl", "wn_auxdh.inl", "wn_optim.inl", "wn_api_ops.inl", "wn_api_decode.inl", "wn_device.h", "wn_gemm.h", "wn_gemm6.h", "wn_elem.h", "wn_distill.h", "wn_cew.h", "wn_lora.h", "wn_optim.h", "wn_fused.h", "wn_decode.h", "wn_dlp.h", "wn_sample.h", "wn_prof.h", "../../include/wavenet_hip.h", "../../include/wavenet_hip_gemm.h"]
 LIB = os.path.join(HERE, "libwavenet_hip.so")
 STAMP = os.path.join(HERE, ".libwavenet_hip.stamp")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

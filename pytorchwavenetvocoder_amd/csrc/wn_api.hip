@@ -17,6 +17,7 @@
 #include "wn_fused.h"
 #include "wn_gemm.h"
 #include "wn_gemm6.h"
+#include "wn_lora.h"
 #include "wn_optim.h"
 #include "wn_prof.h"
 

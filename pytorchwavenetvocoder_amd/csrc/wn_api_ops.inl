@@ -163,3 +163,47 @@ extern "C" int wn_op_accumulate(float* acc, float* grad, int64_t n, int mode, vo
     WN_TRY(wn_grad_accumulate(acc, grad, (long)n, mode, (wn_stream_t)stream));
     return rt_check("wn_op_accumulate");
 }
+
+// ------------------------------------------------------------------------------------------
+// Low-rank adapters (ABI v22): the host table and the two fused operations of wn_lora.hip.
+extern "C" int64_t wn_lora_table(const WnLoraEntry* entries, int n_entries, int64_t n_model, int64_t n_adapter, int64_t* table,
+                                 int64_t table_words) {
+    g_err[0] = 0;   // pure host code: no runtime call to clear
+    if (table && (reinterpret_cast<uintptr_t>(table) & 7)) return fail(1, "wn_lora_table: table needs 8-byte alignment"), -1;
+    return wn_lora_build_table(entries, n_entries, n_model, n_adapter, table, table_words, g_err, sizeof(g_err));
+}
+
+extern "C" int64_t wn_lora_scratch_floats(const int64_t* table) {
+    g_err[0] = 0;
+    if (const char* why = wn_lora_table_error(table, INT64_MAX, INT64_MAX)) return fail(1, "wn_lora_scratch_floats: %s", why), -1;
+    return table[4];
+}
+
+extern "C" int wn_lora_merge(const float* base, float* params, int64_t n_model, const float* adapter, int64_t n_adapter,
+                             const int64_t* table, const int64_t* dev_table, void* stream) {
+    api_enter();
+    if (!base || !params || !adapter || !dev_table || n_model <= 0 || n_adapter <= 0) return fail(1, "bad wn_lora_merge argument (NULL pointer or a length <= 0)");
+    if ((reinterpret_cast<uintptr_t>(base) & 3) || (reinterpret_cast<uintptr_t>(params) & 3) || (reinterpret_cast<uintptr_t>(adapter) & 3) ||
+        (reinterpret_cast<uintptr_t>(dev_table) & 7))
+        return fail(1, "wn_lora_merge: the buffers need 4-byte, the tables 8-byte alignment");
+    if (const char* why = wn_lora_table_error(table, n_model, n_adapter)) return fail(1, "wn_lora_merge: %s", why);
+    if (ranges_overlap(base, params, n_model)) return fail(1, "wn_lora_merge: base overlaps params");
+    WN_TRY(wn_lora_merge_launch(base, params, adapter, table, reinterpret_cast<const long*>(dev_table), (wn_stream_t)stream));
+    return rt_check("wn_lora_merge");
+}
+
+extern "C" int wn_lora_project(const float* grads, int64_t n_model, const float* adapter, float* adapter_grads, int64_t n_adapter,
+                               const int64_t* table, const int64_t* dev_table, float* scratch, int64_t scratch_floats, void* stream) {
+    api_enter();
+    if (!grads || !adapter || !adapter_grads || !dev_table || !scratch || n_model <= 0 || n_adapter <= 0)
+        return fail(1, "bad wn_lora_project argument (NULL pointer or a length <= 0)");
+    if ((reinterpret_cast<uintptr_t>(grads) & 3) || (reinterpret_cast<uintptr_t>(adapter) & 3) || (reinterpret_cast<uintptr_t>(adapter_grads) & 3) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 3) || (reinterpret_cast<uintptr_t>(dev_table) & 7))
+        return fail(1, "wn_lora_project: the buffers need 4-byte, the tables 8-byte alignment");
+    if (const char* why = wn_lora_table_error(table, n_model, n_adapter)) return fail(1, "wn_lora_project: %s", why);
+    if (scratch_floats < table[4]) return fail(1, "wn_lora_project: scratch holds %lld floats, wn_lora_scratch_floats asks for %lld", (long long)scratch_floats, (long long)table[4]);
+    if (ranges_overlap(adapter, adapter_grads, n_adapter)) return fail(1, "wn_lora_project: adapter overlaps adapter_grads");
+    WN_TRY(wn_lora_project_launch(grads, adapter, adapter_grads, table, reinterpret_cast<const long*>(dev_table), scratch,
+                                  (wn_stream_t)stream));
+    return rt_check("wn_lora_project");
+}
